@@ -14,9 +14,20 @@ deep (rtamd.dist.FramePipeline(readback=True), rt_scene_set_frame_slots): frame 
 another stream and starts on the CUs that the previous frames' longest pixel groups leave idle,
 frame k's gather runs on the collective stream meanwhile, and each host copy is issued once its
 frame has completed.  The timed region ends when the last frame is on the host.
-The same frames left in HBM are timed afterwards as `device_resident`; `frame_latency_ms` is
-one host-readable frame issued alone and waited for, `cold_frame_ms` the first one after the
-scene is loaded; `--no-overlap` times serial frames.
+`cold_frame_ms` is the first host-readable frame after the scene is loaded; `--no-overlap`
+times serial frames.
+
+A plain run does only what the headline needs: set-up, one counted frame (the rays `value`
+counts), the warm-up, the K timed frames, `--dump-outputs`, the result line.  `--full` adds every
+other figure, each measured after the headline: the same frames left in HBM (`device_resident`),
+`frame_latency_ms` (one host-readable frame issued alone and waited for) with the event-timed
+kernels and the roofline, the copy-engine rate, the moving camera, the fast kernels' own work
+counts and the CPU baseline; the `--no-*` switches drop single legs of a `--full` run.
+
+`--dump-outputs DIR` (rank 0) writes what the last timed step delivered to its caller, the
+host-readable RGBA8 frame, as DIR/rgba.npy: float32 (H, W, 4), the four bytes of every packed
+pixel in memory order.  Scene, camera and sampling are fixed (no RNG), so two builds run with the
+same arguments can be compared value for value.
 
 Units.  `value` counts rays in the reference's units (every cast_ray call of
 propagate_ray, taken from a counted render of the same frame): reference-equivalent rays.
@@ -24,7 +35,7 @@ The fast kernels skip work the reference does when it provably cannot change the
 (unlit shadow rays, pruned subtrees); `queries_traced_per_frame` (rt_frame_work) is what they
 actually issue, reported beside it.
 
-Launch: python bench.py [--gpus N --steps K --warmup W]; for N > 1 the driver
+Launch: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]; for N > 1 the driver
 uses torch.distributed.run (one process per GPU, RCCL over xGMI).
 """
 import argparse
@@ -67,6 +78,12 @@ def parse():
     p.add_argument("--width", type=int, default=1920)
     p.add_argument("--height", type=int, default=1080)
     p.add_argument("--spp", type=int, default=8)
+    p.add_argument("--full", action="store_true",
+                   help="after the headline also measure the device-resident frames, the lone frame's latency and "
+                        "kernels (roofline), the copy-engine rate, the moving camera, the fast kernels' work counts "
+                        "and the CPU baseline (a plain run times the headline only)")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="rank 0 writes the last timed step's host-readable frame as DIR/rgba.npy (float32)")
     p.add_argument("--brute", action="store_true", help="reference -r: no BVH")
     p.add_argument("--textures", action="store_true",
                    help="build-defined textured shading with the scene's atlas (e.g. --scene world16_tex, config 5)")
@@ -244,8 +261,26 @@ def camera_move(scene):
     scene.rotate_camera(rot)
 
 
+DUMP_LIMIT = 64 << 20          # --dump-outputs writes at most this many bytes
+
+
+def dump_outputs(out_dir, frame):
+    """The (H, W) packed RGBA8 frame as out_dir/rgba.npy, float32 (H, W, 4); a frame above
+    DUMP_LIMIT as float32 (n, 4): a fixed, seeded sample of its pixels (row-major indices, sorted)."""
+    import numpy as np
+    px = np.ascontiguousarray(frame).view(np.uint8).reshape(frame.shape[0], frame.shape[1], 4)
+    n_max = DUMP_LIMIT // 16
+    if px.shape[0] * px.shape[1] > n_max:
+        idx = np.sort(np.random.default_rng(0).choice(px.shape[0] * px.shape[1], n_max, replace=False))
+        px = px.reshape(-1, 4)[idx]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "rgba.npy"), px.astype(np.float32))
+
+
 def main():
     args = parse()
+    if not args.full:                     # a plain run: the headline alone
+        args.no_device_resident = args.no_camera_path = args.no_cpu_baseline = True
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -418,6 +453,8 @@ def main():
     if args.dump_frame and rank == 0:
         import numpy as np
         np.save(args.dump_frame, host_read(f_last).numpy().view(np.uint32) if overlap else fb.frame.cpu().numpy().view(np.uint32))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, (host_read(f_last) if overlap else fb.frame.cpu()).numpy())
 
     # ---- the same frames left in HBM (no host copy): the device-resident figure ----
     dev_s = None
@@ -448,7 +485,7 @@ def main():
     # host, waited for); with frames in flight the kernels' event-timed durations come from these
     # lone frames (a launch that overlaps other frames' kernels runs longer than its cost)
     lat = []
-    for _ in range(max(3, args.steps // 2)):
+    for _ in range(max(3, args.steps // 2) if args.full else 0):
         if dist:
             dist.barrier()
         torch.cuda.synchronize()
@@ -460,12 +497,12 @@ def main():
             host_read(k)
         torch.cuda.synchronize()
         lat.append(time.perf_counter() - t3)
-    lat_ms = sorted(lat)[len(lat) // 2] * 1e3
+    lat_ms = sorted(lat)[len(lat) // 2] * 1e3 if lat else None
     tm = scene.timing_collect()
     # this box's copy-engine rate for one full frame to pinned host memory, alone (rank 0; the
     # rate is a property of the box at the time of the call -- 29 or 53 GB/s seen)
     copy_rate = None
-    if overlap and rank == 0 and fbr is not None and fbr.copy_stream is not None:
+    if args.full and overlap and rank == 0 and fbr is not None and fbr.copy_stream is not None:
         src = torch.zeros((H, W), dtype=torch.int32, device="cuda")
         hb = rtamd.HostBuffer((H, W), "int32")
         cs = fbr.copy_stream
@@ -510,7 +547,7 @@ def main():
     # what the fast kernels actually do for this rank's rows (profiling run, untimed)
     try:
         work = scene.frame_work(spp=args.spp, row0=rank, row_step=world, compact=True) \
-            if (use_bvh and not args.textures and args.spp <= 64) else None
+            if (args.full and use_bvh and not args.textures and args.spp <= 64) else None
     except rtamd.RtError:
         work = None
 
@@ -538,6 +575,43 @@ def main():
 
     ms_per_step = elapsed / args.steps * 1e3
     value = rays * args.steps / elapsed / 1e6
+    out = {
+        "metric": METRIC, "value": round(value, 3), "unit": "Mrays/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "strong",
+        "vs_baseline": None, "dtype": "f32",
+        "data": "procedural scene from the reference's %s.json (deterministic, no RNG at render time)" % args.scene,
+        "config": {"workload": "%s.json %dx%d %dspp %s%s" % (args.scene, W, H, args.spp, "brute" if args.brute else "BVH",
+                                                          " textured" if args.textures else ""),
+                   "scene": args.scene, "width": W, "height": H, "spp": args.spp, "bvh": use_bvh,
+                   "parallelism": ("row-cyclic x%d + %s gather" % (world, "gloo host-staged" if gloo else "RCCL"))
+                                  if world > 1 else "single GPU",
+                   # HIP hardware queues per process (HIP's default is 4; bench.py sets 16
+                   # so that four render streams + main + collective + copy each get a queue, DESIGN.md §4.1)
+                   "gpu_max_hw_queues": int(os.environ["GPU_MAX_HW_QUEUES"]), "frames_in_flight": depth if overlap else 1,
+                   "grid_timed_frames": args.grid if overlap else "full"},
+        "build": {"lib_sha16": lib_sha16()}, "pmc_window": args.pmc_window,
+        "rays_unit": "reference-equivalent rays: every cast_ray of the reference's propagate_ray (SURVEY 8d), "
+                     "counted by the counted kernel on the same frame",
+        "frame_ms": round(ms_per_step, 4),
+        "timed_to": "host-readable frames: every timed frame (rank 0: gathered and un-permuted) copied to pinned "
+                    "host memory by a copy engine and read by a host consumer; the window ends when the last "
+                    "frame is on the host (the reference's update_scene post-condition, raytracer.cu:102-120)",
+        "cold_frame_ms": round(cold_ms, 4), "scene_load_ms": round(load_ms, 3),
+        "cold_frame_note": "the first host-readable frame after scene load (main.cc:210-216's bench: the first "
+                           "update_scene after generate); scene_load_ms = load + upload + one untimed warm frame",
+        "frames_in_flight": depth if overlap else 1,
+        "rays_per_frame": int(rays), "nodes_per_frame": int(nodes), "leaves_per_frame": int(leaves),
+        "tri_tests_per_frame": int(tris), "full": args.full,
+    }
+    if args.frame_crcs:
+        out["frame_crcs"] = timed_crcs
+    if args.dump_outputs:
+        out["outputs"] = {"dir": args.dump_outputs, "arrays": ["rgba"]}
+    if not args.full:                     # a plain run ends here: the headline alone
+        print(json.dumps(out), flush=True)
+        if dist:
+            dist.destroy_process_group()
+        return
     # Dominant kernel: the trace stage (sky pre-pass + trace kernel) of a lone frame, event-timed
     # on the launch stream (with frames in flight a launch that overlaps other frames' kernels
     # runs longer than its cost).  This rank's rows.
@@ -582,43 +656,14 @@ def main():
         "note": "SURVEY 8d uncached model in the reference's units (28 B per BVH node test + 816 B per leaf, "
                 "counts of the reference traversal) -- not HBM traffic: frac exceeds 1, so the kernel cannot be "
                 "doing this work from HBM; LDS residency of the tree and scene and the exact pruning serve it"}
-    out = {
-        "metric": METRIC, "value": round(value, 3), "unit": "Mrays/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "strong",
-        "vs_baseline": None, "dtype": "f32",
-        "data": "procedural scene from the reference's %s.json (deterministic, no RNG at render time)" % args.scene,
-        "config": {"workload": "%s.json %dx%d %dspp %s%s" % (args.scene, W, H, args.spp, "brute" if args.brute else "BVH",
-                                                          " textured" if args.textures else ""),
-                   "scene": args.scene, "width": W, "height": H, "spp": args.spp, "bvh": use_bvh,
-                   "parallelism": ("row-cyclic x%d + %s gather" % (world, "gloo host-staged" if gloo else "RCCL"))
-                                  if world > 1 else "single GPU",
-                   # HIP hardware queues per process (HIP's and the pool's default is 4; bench.py sets 16
-                   # so that four render streams + main + collective + copy each get a queue, DESIGN.md §4.1)
-                   "gpu_max_hw_queues": int(os.environ["GPU_MAX_HW_QUEUES"]), "frames_in_flight": depth if overlap else 1,
-                   "grid_timed_frames": args.grid if overlap else "full"},
-        "build": {"lib_sha16": lib_sha16()}, "pmc_window": args.pmc_window,
-        "rays_unit": "reference-equivalent rays: every cast_ray of the reference's propagate_ray (SURVEY 8d), "
-                     "counted by the counted kernel on the same frame",
-        "frame_ms": round(ms_per_step, 4),
-        "timed_to": "host-readable frames: every timed frame (rank 0: gathered and un-permuted) copied to pinned "
-                    "host memory by a copy engine and read by a host consumer; the window ends when the last "
-                    "frame is on the host (the reference's update_scene post-condition, raytracer.cu:102-120)",
-        "cold_frame_ms": round(cold_ms, 4), "scene_load_ms": round(load_ms, 3),
-        "cold_frame_note": "the first host-readable frame after scene load (main.cc:210-216's bench: the first "
-                           "update_scene after generate); scene_load_ms = load + upload + one untimed warm frame",
-        "frame_latency_ms": round(lat_ms, 4), "frames_in_flight": depth if overlap else 1,
-        "rays_per_frame": int(rays), "nodes_per_frame": int(nodes), "leaves_per_frame": int(leaves),
-        "tri_tests_per_frame": int(tris), "trace_kernel_ms": round(trace_ms, 4), "bvh_build_ms": round(bvh_ms, 4),
-        "roofline": roof,
-    }
+    out.update(frame_latency_ms=round(lat_ms, 4), trace_kernel_ms=round(trace_ms, 4), bvh_build_ms=round(bvh_ms, 4),
+               roofline=roof)
     if dev_s is not None:
         out["device_resident"] = {
             "ms_per_step": round(dev_s / args.steps * 1e3, 4), "value": round(rays * args.steps / dev_s / 1e6, 3),
             "unit": "Mrays/s", "note": "the same K frames left in HBM (no host copy), measured after the headline"}
     if copy_rate:
         out["copy_engine"] = copy_rate
-    if args.frame_crcs and rank == 0:
-        out["frame_crcs"] = timed_crcs
     if work:
         out["queries_traced_per_frame"] = int(queries)
         out["queries_traced_Mrays_s"] = round(queries * args.steps / elapsed / 1e6, 3)

@@ -9,7 +9,7 @@ while [ $# -gt 0 ] && [ "$1" != "--" ]; do LIBS+=("$1"); shift; done
 [ "$1" == "--" ] && shift
 for r in $(seq 1 $ROUNDS); do
   for L in "${LIBS[@]}"; do
-    RTAMD_LIB=$L timeout -k 10 120 python3 "$R/bench.py" --no-cpu-baseline --steps ${AB_STEPS:-20} --warmup 3 --no-camera-path "$@" > /tmp/ab_out.txt 2>&1 || { cat /tmp/ab_out.txt; exit 1; }
+    RTAMD_LIB=$L timeout -k 10 120 python3 "$R/bench.py" --full --no-cpu-baseline --steps ${AB_STEPS:-20} --warmup 3 --no-camera-path "$@" > /tmp/ab_out.txt 2>&1 || { cat /tmp/ab_out.txt; exit 1; }
     python3 - "$L" <<'PY'
 import json, sys
 line = [l for l in open('/tmp/ab_out.txt') if l.startswith('{')][-1]

@@ -9,7 +9,7 @@ O=$R/gpurun_out/${TAG:-ab_counters}
 mkdir -p "$O"
 export TMPDIR=/tmp
 cd /tmp || exit 1
-ARGS="--steps 20 --warmup 5 --no-cpu-baseline --no-camera-path --pmc-window device"
+ARGS="--steps 20 --warmup 5 --full --no-cpu-baseline --no-camera-path --pmc-window device"
 for L in "$@"; do
   n=$(basename "$L" .so)
   RTAMD_LIB=$R/$L timeout -k 10 300 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_LDS SQ_WAIT_INST_ANY SQ_BUSY_CYCLES SQ_WAVE_CYCLES --output-format csv -d "$O/$n" -o sq -- python3 "$R/bench.py" $ARGS > "$O/$n.log" 2>&1 || { echo "pmc $n failed"; tail "$O/$n.log"; exit 1; }

@@ -9,7 +9,7 @@ OUT=$R/gpurun_out/$TAG
 mkdir -p "$OUT"
 for i in $(seq 1 "$ROUNDS"); do
   for q in 8 4; do
-    RT_BENCH_HW_QUEUES=$q timeout -k 10 240 python3 -u "$R/bench.py" --steps 60 --warmup 5 --no-cpu-baseline \
+    RT_BENCH_HW_QUEUES=$q timeout -k 10 240 python3 -u "$R/bench.py" --steps 60 --warmup 5 --full --no-cpu-baseline \
       > "$OUT/bench_q${q}_$i.log" 2>&1 || { echo "bench q=$q round $i failed"; exit 1; }
     python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print('q=%s round %s frame_ms %.4f readback %.4f' % (sys.argv[2], sys.argv[3], d['frame_ms'], d['ms_per_step_with_readback']))" "$OUT/bench_q${q}_$i.log" $q $i
   done

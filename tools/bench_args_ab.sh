@@ -11,7 +11,7 @@ for r in $(seq 1 $ROUNDS); do
   i=0
   for A in "$@"; do
     i=$((i + 1))
-    timeout -k 10 150 python3 "$R/bench.py" --no-cpu-baseline --no-camera-path $A > $O/a${i}_$r.json 2> $O/a${i}_$r.err || { tail $O/a${i}_$r.err; exit 1; }
+    timeout -k 10 150 python3 "$R/bench.py" --full --no-cpu-baseline --no-camera-path $A > $O/a${i}_$r.json 2> $O/a${i}_$r.err || { tail $O/a${i}_$r.err; exit 1; }
     python3 - $O/a${i}_$r.json "$A" <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1])

@@ -7,7 +7,7 @@ TAG=$1; shift
 OUT=$R/gpurun_out/$TAG; mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd /tmp || exit 1
-ARGS="--steps 3 --warmup 1 --no-cpu-baseline --no-overlap --no-camera-path"
+ARGS="--steps 3 --warmup 1 --full --no-cpu-baseline --no-overlap --no-camera-path"
 for lib in "$@"; do
   n=$(basename "$lib" .so)
   RTAMD_LIB=$R/$lib timeout -k 10 200 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_VMEM_RD --output-format csv -d "$OUT/${n}_sq" -o s -- python3 "$R/bench.py" $ARGS > "$OUT/${n}_sq.log" 2>&1 || { echo "$n sq failed"; exit 1; }

@@ -8,7 +8,7 @@ OUT=$R/gpurun_out/$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd /tmp || exit 1
-ARGS="--steps 3 --warmup 1 --no-cpu-baseline --no-overlap --no-camera-path $*"
+ARGS="--steps 3 --warmup 1 --full --no-cpu-baseline --no-overlap --no-camera-path $*"
 run() { local name=$1; shift; timeout -k 10 200 rocprofv3 "$@" --output-format csv -d "$OUT/$name" -o "$name" -- python3 "$R/bench.py" $ARGS > "$OUT/$name.log" 2>&1; }
 run lds1 --kernel-trace --pmc SQ_INSTS_LDS_LOAD_BANDWIDTH SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT SQ_LDS_DATA_FIFO_FULL SQ_LDS_CMD_FIFO_FULL SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS SQ_INST_CYCLES_SALU || { echo "pmc lds1 failed"; exit 1; }
 run lds2 --kernel-trace --pmc SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_VALU2 SQ_INSTS_BRANCH SQ_INSTS_VALU_TRANS_F32 SQ_INSTS_VALU_FMA_F64 SQ_BUSY_CU_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU || { echo "pmc lds2 failed"; exit 1; }

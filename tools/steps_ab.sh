@@ -9,7 +9,7 @@ mkdir -p $O
 ROUNDS=$1; shift
 for r in $(seq 1 $ROUNDS); do
   for K in 20 60; do
-    timeout -k 10 150 python3 "$R/bench.py" --no-cpu-baseline --steps $K --no-camera-path "$@" > $O/k${K}_$r.json 2> $O/k${K}_$r.err || { tail $O/k${K}_$r.err; exit 1; }
+    timeout -k 10 150 python3 "$R/bench.py" --full --no-cpu-baseline --steps $K --no-camera-path "$@" > $O/k${K}_$r.json 2> $O/k${K}_$r.err || { tail $O/k${K}_$r.err; exit 1; }
     python3 - $O/k${K}_$r.json $K <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1])
