@@ -1,0 +1,191 @@
+// rt_device.h — what the host runtime (rt_runtime.cpp, rt_multi.cpp, rt_copy.cpp) and the
+// kernel translation unit (rt_kernels.hip) share: the kernel argument structs, the launch
+// geometry the host sizes buffers and grids by, and the launch layer's declarations.  The
+// launch layer is defined at the end of rt_kernels.hip; its functions are the only ones that
+// name a kernel, so every kernel is instantiated in that one translation unit.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+
+#include "rt_bvh.h"
+#include "rt_math.h"
+#include "rt_scene.h"
+
+// Tuning parameters (build switches; the A/B logs under profiles/ record the values tried).
+#ifndef RT_BLOCK
+#define RT_BLOCK 1024
+#endif
+#ifndef RT_NQ
+#define RT_NQ 8
+#endif
+#ifndef RT_HIST_GROUPS_PER_WAVE
+#define RT_HIST_GROUPS_PER_WAVE 12  // longest-first history only at <= this many groups per wave
+#endif
+#ifndef RT_SMALL_FRAME_GPW
+#define RT_SMALL_FRAME_GPW 48       // groups per wave (half grid) below which overlapping frames take a quarter of the CUs
+#endif
+#ifndef RT_HEAVY_Q_DEFAULT
+#define RT_HEAVY_Q_DEFAULT 6        // hist = 2: a group of >= this many wave queries is heavy
+#endif
+#ifndef RT_HEAVY_STATIC
+#define RT_HEAVY_STATIC 1    // frames issued alone: heavy-list tickets assigned statically (trace_kernel)
+#endif
+#ifndef RT_TPC_WIDE
+#define RT_TPC_WIDE 16       // live-list tickets of one-pixel groups (spp >= 64, M_PART): 16 consecutive pixels
+#endif
+#ifndef RT_LDS_SUM
+#define RT_LDS_SUM 1         // spp >= 16 in parked kernels: per-channel in-order sample sums through LDS
+#endif
+#ifndef RT_TPC
+#define RT_TPC 3             // work indices claimed per ticket (trace_kernel's group loop) over all
+                             // groups; 3 vs 2: -0.8% world8_stress, -1.3% world8 (profiles/r01/ab_tpc_v33.log)
+#endif
+#ifndef RT_TPC_LIVE
+#define RT_TPC_LIVE 1        // the same over live-group lists (sky pre-pass): ~8x fewer groups per
+                             // wave, one per ticket balances them (profiles/r02/sky_live_tpc.log)
+#endif
+#ifndef RT_SKY_WAVES
+#define RT_SKY_WAVES 4       // waves per sky_kernel block (64 groups per block)
+#endif
+
+namespace rtd {
+
+constexpr int MAX_FRAMES = 10;           // renv::gpu::MAX_DEPTH (scene.cu:25)
+constexpr int BVH_WG_LEAVES = 8192;      // single-workgroup BVH build (LDS keys); above: bvh_build_large
+constexpr int TRACE_BLOCK_P = RT_BLOCK;  // persistent block: 16 waves (4 per SIMD, 128-VGPR budget) sharing one LDS BVH copy
+constexpr int NQ = RT_NQ;                    // work queues (one per XCD dispatch slot), 64-B apart
+// work counters: [16 q] queue q's tickets, [16 NQ] the heavy list's, [16 (NQ + 1 + q)] the
+// length of live-group list q (sky_kernel), [16 (2 NQ + 1)] the length of this frame's heavy
+// live list (hist = 2)
+constexpr int WORK_INTS = 16 * (2 * NQ + 2);
+// Statistics / profiling counters (d_stats): [0, 22) rt_stats and the PROF step counts and
+// cycle split (rt_experiment), [22, 24) spare, [24, 64) the PROF variant's query-occupancy
+// counters (PROF_* below, rt_frame_work).
+constexpr int STATS_N = 64;
+enum : int {
+    PROF_LANES_PRIMARY = 24, PROF_LANES_SECONDARY = 25, PROF_LANES_SHADOW = 26, PROF_LANES_UNLIT = 27,
+    PROF_LIVE_WQ = 28, PROF_LIVE_LANES = 29,
+    PROF_HIST_WQ = 30,      // [8] live wave queries by active lanes, buckets of 8 (1-8, 9-16, ..., 57-64)
+    PROF_HIST_PAIR = 38,    // [8] their child-pair steps
+    PROF_HIST_LEAF = 46,    // [8] their leaf visits
+    PROF_END = 54
+};
+constexpr int TPC = RT_TPC;
+constexpr int SKY_THREADS = 64 * RT_SKY_WAVES;
+
+// Unsigned division by a launch constant d with host-computed magic numbers (round-up
+// method: l = ceil(log2 d), m = floor(2^32 (2^l - d) / d) + 1, q = (t + ((n - t) >> 1)) >> (l - 1),
+// t = mulhi(n, m); exact for every 32-bit n; d = 1 passes through).  Wave-uniform operands stay
+// on the scalar unit (the compiler's own sequence keeps a VGPR reciprocal live across the
+// group loop, which was spilled and reloaded from scratch at every group).
+struct UDiv { unsigned m, d; int s; };
+__host__ inline UDiv udiv_make(unsigned d) {
+    UDiv r{0u, d, 0};
+    if (d <= 1) return r;
+    int l = 0;
+    while ((1ull << l) < d) l++;
+    r.m = (unsigned)((((1ull << l) - d) << 32) / d + 1);
+    r.s = l - 1;
+    return r;
+}
+
+struct SceneView {           // read-only scene data (HBM, L2-resident)
+    const rt::DTri* __restrict__ tris;
+    const rt::DMesh* __restrict__ meshes;
+    const rt::DInst* __restrict__ insts;
+    const rt::DMat* __restrict__ mats;
+    const rt::DLight* __restrict__ lights;
+    const float4* node_pair;  // BVH child pairs, heap order (written by bvh_build_kernel), see BvhRefs
+    const float4* fnode;      // ordered LBVH of the fast kernel (bvh_build_kernel)
+    int n_real, ftree;        // its leaf count; 1 if usable (>= 2 leaves, depth <= 31)
+    const int* leaf_inst;
+    const float4* inst4;      // compact instance records
+    int n_leaf, n_inst, n_lights, use_bvh;
+    int n_mats, n_tris, n_meshes;   // record counts (LDS shading cache, M_SHADE)
+    int ident_all;            // every instance and mesh rotation is the identity (cube worlds)
+    float prune_abs;          // distance-pruning slack M0 (< 0: pruning off), see closest_hit
+    const rtm::TriAx* tri_ax; // axis-plane triangle records (fast kernel; null unless ident_all)
+};
+
+struct TraceParams {
+    rt::DCamera cam;
+    rtm::V3 dist_atten;
+    rtm::V4 ambience;
+    int W, H, row0, row_step, n_rows, compact, spp, depth;
+    float spp_recip;          // 2^-k when spp = 2^k (exact reciprocal), else 0
+    int lanes_per_px, px_per_wave, gw, gh, n_gx, n_groups;   // sample-parallel lane mapping
+    int l_shift, gw_shift;    // log2(lanes_per_px), log2(gw) when powers of two, else -1
+    UDiv div_ngx, div_perq;   // g / n_gx and ticket permutation mod per-queue length
+    int scramble;             // ticket -> group permutation factor (coprime with the queue length)
+    int scramble_small;       // 1: ticket * scramble < 2^32 for every ticket (32-bit modulo)
+    const float2* __restrict__ spp_off;
+    uint32_t* rgba;
+    float4* radiance;
+    int* hit_inst;
+    int* hit_tri;
+    unsigned long long* stats;
+    int* work;                // persistent-wave work counters (zeroed before each launch); work[16 NQ]: heavy list
+    // Longest-first scheduling history (fast frames only, hist = 1): the previous frame's
+    // heavy groups (hl_prev[0, *hc_prev)) run first and are skipped in the normal queues
+    // (hf_prev); this frame records its own into the *_next buffers.  hs_* = summed group
+    // durations (100 MHz ticks) for the threshold (4x the mean group).
+    int hist, heavy_cap;      // heavy_cap: most heavy groups recorded per frame
+    // hist = 2 (whole frames with the sky pre-pass): heavy = a group that took >= heavy_q wave
+    // queries (counted, no clock); hf_next[g] = 1 records it, and the next frame's sky pre-pass
+    // puts the groups flagged in hf_prev on a heavy live list the trace kernel drains first
+    int heavy_q;
+    const int* hl_prev; int* hl_next;
+    const unsigned char* hf_prev; unsigned char* hf_next;
+    const unsigned long long* hctl_prev; unsigned long long* hctl_next;   // {count, sum}
+    int occl_exit;            // shadow-ray occlusion early exit (all-opaque scene, no statistics)
+    const float4* atlas;      // textured mode: atlas texels, byte / 255 (rt_scene_set_atlas)
+    int atlas_w, atlas_h;
+    int* dbg_log;             // debug_cast event log (NULL in normal frames)
+    int dbg_x, dbg_y;
+    unsigned* gdur;           // profiling (rt_profile_groups): per-group duration, 100 MHz ticks; NULL normally
+    // Sky pre-pass (sky_kernel, fast frames): gsky[g] = 1 when no primary of group g enters
+    // the tree's root -- its outputs are written already and the trace kernel skips it.
+    // NULL: no pre-pass (the trace kernel runs the same test itself).
+    const unsigned char* gsky;
+    // Live-group lists (sky_kernel): queue q's groups are live[q * live_cap + i] for i below
+    // work[16 (NQ + 1 + q)], in arrival order.  NULL: queue q's groups are q + NQ j.
+    const int* live; int live_cap;
+    int tpc;                  // work indices per ticket (normal queues)
+    int grid_waves;           // waves of this launch (the heavy list's static rounds)
+    int heavy_static;         // 1: heavy-list tickets assigned statically (frames issued alone)
+    int unlit_skip;           // fast frames: no shadow segments for a light whose phong factor is zero (1),
+                              // and no phong term for it either (2)
+};
+
+// ---------------------------------------------------------------------------
+// Launch layer (defined in rt_kernels.hip)
+// ---------------------------------------------------------------------------
+// The trace kernel variant for a frame: which instantiation, its dynamic LDS, the blocks of it
+// a CU holds, and the decisions the host's launch set-up depends on.
+struct TraceVariant {
+    const void* fn;
+    size_t shm;
+    int per_cu;
+    bool part_k;              // partial parking (M_PART): wide live-list tickets at 64 lanes per pixel
+    bool sky, sky_brute;      // sky pre-pass before the trace kernel; over the instances' grown boxes
+};
+// ns: suspended frames a sample needs (0: no refractive material).  Sets the function's dynamic
+// LDS limit and queries its occupancy.
+TraceVariant choose_trace_variant(const SceneView& S, int spp, bool tex, bool want_stats, bool prof, int ns);
+// e0 / e1 (optional): timestamps taken by the dispatch itself, no marker packets
+hipError_t launch_sky(bool brute, int blocks, TraceParams& P, SceneView& S, unsigned char* gsky, int* live,
+                      const rtm::Box* mesh_box, float slack_a, float slack_b, hipStream_t st, hipEvent_t e0);
+hipError_t launch_trace_kernel(const TraceVariant& v, int blocks, TraceParams& P, SceneView& S, hipStream_t st,
+                               hipEvent_t e0, hipEvent_t e1);
+// The single-workgroup BVH build (A.n <= BVH_WG_LEAVES) with `lds` bytes of dynamic LDS.
+hipError_t launch_bvh_build(rtb::BvhArgs& A, bool lds_tree, size_t lds, hipStream_t st, hipEvent_t e0, hipEvent_t e1);
+size_t scene_image_bytes(const SceneView& S);   // the scene image a fast kernel's block stages in LDS
+void launch_unpermute(const uint32_t* g, uint32_t* out, int W, int H, int N, int rows_max, hipStream_t st);
+void launch_profile_marker(int tag, hipStream_t st);
+void launch_copy_gate(const unsigned* flag, unsigned long long max_ticks, hipStream_t st);
+void launch_kat(int op, int n, const float* a, const float* b, const float* c, float* of, int* oi, unsigned long long* ou);
+
+}  // namespace rtd

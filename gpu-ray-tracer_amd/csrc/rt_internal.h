@@ -1,0 +1,165 @@
+// rt_internal.h — the scene object and what the host translation units share: rt_runtime.cpp
+// (scene, upload, frame slots, frames, most of the C ABI), rt_multi.cpp (multi-device frames)
+// and rt_copy.cpp (copy-engine entries).  Internal functions live in namespace rti: the
+// library's rt_* C symbols (rt_amd.h) stay its only interface.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <cstdlib>
+#include <string>
+#include <vector>
+
+#include "rt_device.h"
+#include "../../include/rt_amd.h"
+
+struct MultiDev;   // rt_multi.cpp
+
+namespace rti {
+
+int fail(int code, const std::string& msg);   // records the thread's error text (rt_last_error)
+extern thread_local int g_device;             // rt_set_device: the device new scenes upload to
+
+template <class T> void dfree(T*& p) { if (p) { (void)hipFree(p); p = nullptr; } }
+template <class T> void hfree(T*& p) { if (p) { (void)hipHostFree(p); p = nullptr; } }
+
+// Host framebuffer in pinned memory: rt_update_scene's device-to-host copy of the frame (the
+// reference's post-condition, raytracer.cu:102-120) is then one direct transfer; into pageable
+// memory HIP stages it in chunks through a bounce buffer.  Pageable fallback when pinning fails
+// (no HIP device: the scene is still built and exported, nothing is rendered).
+struct HostCanvas {
+    uint32_t* p = nullptr;
+    size_t n = 0;
+    bool pinned = false;
+    HostCanvas() = default;
+    HostCanvas(const HostCanvas&) = delete;
+    HostCanvas& operator=(const HostCanvas&) = delete;
+    ~HostCanvas() { release(); }
+    void release() {
+        if (p) { if (pinned) (void)hipHostFree(p); else free(p); }
+        p = nullptr; n = 0; pinned = false;
+    }
+    void assign(size_t m, uint32_t v) {
+        release();
+        if (!m) return;
+        if (hipHostMalloc((void**)&p, m * sizeof(uint32_t), hipHostMallocDefault) == hipSuccess) {
+            pinned = true;
+        } else {
+            (void)hipGetLastError();
+            p = static_cast<uint32_t*>(malloc(m * sizeof(uint32_t)));
+            if (!p) return;
+        }
+        n = m;
+        std::fill(p, p + m, v);
+    }
+    uint32_t* data() { return p; }
+    const uint32_t* data() const { return p; }
+    size_t size() const { return n; }
+    uint32_t operator[](size_t i) const { return p[i]; }
+};
+
+// The per-frame state, one record per frame slot (rt_scene_set_frame_slots): with n > 1 slots,
+// consecutive frames rotate through n of these (BVH, work counters, scheduling history), so a
+// frame on another stream can start on CUs freed by the previous frames' tails.
+// Instance arrays are per-slot state too (rt_builder_set_trans after finish): a frame in
+// flight keeps the poses its BVH was built from, and the next frame of a slot receives the
+// current poses by a stream-ordered copy (sync_slot_insts) from the slot's pinned staging.
+struct FrameSlot {
+    rtm::Box* d_tree = nullptr; float4* d_node_pair = nullptr; int* d_leaf = nullptr;
+    float4* d_fnode = nullptr;                   // ordered LBVH (fast kernel)
+    void* d_bscratch = nullptr;                  // bvh_build_large's sort buffers (scenes above BVH_WG_LEAVES)
+    int* d_work = nullptr;                       // null: the slot is not allocated yet
+    bool work_zeroed = false;                    // bvh_build_kernel zeroed d_work for the next trace launch
+    bool bvh_valid = false;
+    // longest-first scheduling history (TraceParams::hist): double-buffered by frame parity
+    int* d_hlist[2] = {nullptr, nullptr};
+    unsigned char* d_hflag[2] = {nullptr, nullptr};
+    unsigned long long* d_hctl = nullptr;        // [2][count, sum]
+    int hist_cap = 0, hist_parity = 0;
+    int hctl_zeroed = -1;                        // heavy-list slot the pending bvh_build_kernel zeroes (-1: none)
+    long long hist_key[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
+    unsigned char* d_gsky = nullptr; int gsky_cap = 0;   // sky pre-pass flags (TraceParams::gsky)
+    int* d_live = nullptr; int live_cap = 0;             // sky pre-pass live-group lists [NQ][live_cap]
+    rt::DInst* d_insts = nullptr; float4* d_inst4 = nullptr;
+    rt::DInst* h_insts_pin = nullptr; float4* h_inst4_pin = nullptr;   // pinned staging of the two
+    unsigned inst_gen = 0;                       // instance generation the slot's arrays hold
+    // Last frame of the slot (recorded on its stream, also with one slot): the next frame of
+    // the slot, and side entries (debug_cast, experiments), wait for it stream-ordered.
+    hipEvent_t done = nullptr;
+    bool pending = false;
+
+    void release() {
+        dfree(d_tree); dfree(d_node_pair); dfree(d_leaf); dfree(d_fnode); dfree(d_bscratch); dfree(d_work);
+        for (int p = 0; p < 2; p++) { dfree(d_hlist[p]); dfree(d_hflag[p]); }
+        dfree(d_hctl); dfree(d_gsky); dfree(d_live);
+        dfree(d_insts); dfree(d_inst4);
+        hfree(h_insts_pin); hfree(h_inst4_pin);
+        if (done) { (void)hipEventDestroy(done); done = nullptr; }
+    }
+};
+
+}  // namespace rti
+
+#ifndef RT_OVERLAP_DEFAULT
+#define RT_OVERLAP_DEFAULT RT_OVERLAP_HALF   // (RT_OVERLAP_FULL: the A/B arm of round 3's policy)
+#endif
+#ifndef RT_MAX_SLOTS
+#define RT_MAX_SLOTS 8
+#endif
+
+struct rt_scene {
+    rt::Scene h;
+    MultiDev* multi = nullptr;                   // rt_scene_set_devices: frames split over several GPUs
+    bool finished = false;
+    int device = -1;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    // device buffers shared by every frame slot
+    rt::DTri* d_tris = nullptr; rt::DMesh* d_meshes = nullptr; rt::DMat* d_mats = nullptr;
+    rt::DLight* d_lights = nullptr; rtm::Box* d_mesh_box = nullptr;
+    int n_real = 0, fdepth = 0;                  // ordered LBVH (fast kernel): leaves, depth
+    rtm::TriAx* d_tri_ax = nullptr;              // axis-plane triangle records (tri_axis_records)
+    int n_cu = 0;
+    float2* d_spp = nullptr; int spp_cap = 0;
+    unsigned long long* d_stats = nullptr;
+    uint32_t* d_canvas = nullptr;
+    int* d_dbg = nullptr;
+    float4* d_atlas = nullptr;                   // atlas texels (float4, byte / 255)
+    bool atlas_dirty = false;
+    void* d_out[4] = {nullptr, nullptr, nullptr, nullptr};   // staging for host_outputs
+    std::vector<hipEvent_t> tev;      // timing=1 events, 4 per frame: bvh start/stop, trace start/stop (pool)
+    size_t tev_used = 0;
+    size_t d_out_px = 0;
+    int n_leaf = 0;
+    bool uploaded = false;
+    rti::HostCanvas canvas;          // host framebuffer (Canvas buffer, canvas.cu:7), pinned
+    int overlap = RT_OVERLAP_DEFAULT;            // rt_scene_set_overlap
+    int ranks_per_device = 1;                    // > 1: virtual ranks of rt_scene_set_devices share this device
+    unsigned inst_gen = 1;                       // generation of the host instance array (set_trans bumps it)
+    unsigned shape_gen = 0;                      // generation n_real / fdepth were computed for
+    static constexpr int MAX_SLOTS = RT_MAX_SLOTS;
+    rti::FrameSlot slots[MAX_SLOTS];             // slots[0, n_slots) are in rotation (FrameSlot)
+    int n_slots = 1, cur_slot = 0;
+    rti::FrameSlot& cur() { return slots[cur_slot]; }
+    const rti::FrameSlot& cur() const { return slots[cur_slot]; }
+    ~rt_scene();
+};
+
+#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return rti::fail(RT_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
+#define CHECK_SCENE(s) do { if (!(s)) return rti::fail(RT_ERR_ARG, "null scene"); } while (0)
+#define CHECK_BUILDING(s) do { CHECK_SCENE(s); if ((s)->finished) return rti::fail(RT_ERR_STATE, "scene already finished"); } while (0)
+#define CHECK_FINISHED(s) do { CHECK_SCENE(s); if (!(s)->finished) return rti::fail(RT_ERR_STATE, "scene not finished (call rt_builder_finish)"); } while (0)
+
+namespace rti {
+
+// rt_runtime.cpp
+int upload(rt_scene* s);          // device buffers of a finished scene on g_device (once)
+void invalidate(rt_scene* s);     // every slot's BVH is stale (instances moved)
+// rt_multi.cpp
+int render_multi(rt_scene* s, const rt_render_opts* o, rt_stats* stats);
+void free_multi(rt_scene* s);
+void set_multi_overlap(rt_scene* s, int policy);   // the replicas of rt_scene_set_devices
+
+}  // namespace rti

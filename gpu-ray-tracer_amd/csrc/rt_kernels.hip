@@ -1,4 +1,6 @@
-// rt_kernels.hip — gfx950 kernels of the ray-tracing core + the C ABI (rt_amd.h).
+// rt_kernels.hip — gfx950 kernels of the ray-tracing core and their launch layer (rt_device.h).
+// Device code only: the scene object, the frame slots and the C ABI are rt_runtime.cpp,
+// rt_multi.cpp and rt_copy.cpp.
 //
 // Hot path (BASELINE.json north_star): rtracer::gpu::update_scene
 // (src/raytracer.cu:102-120) = per-frame BVH build + the per-pixel `trace`
@@ -24,29 +26,23 @@
 //    the traversal does not read is parked in LDS during the query.  Every filter and pruning
 //    is exact: hit ids equal the reference's single-ray semantics and
 //    radiance its float32 operations.
-#include <dlfcn.h>
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
-#include <rccl/rccl.h>   // types only: RCCL is opened at run time (MultiDev), never linked
 
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
-#include <numeric>
-#include <fstream>
-#include <memory>
-#include <mutex>
-#include <string>
-#include <vector>
 
 #include "rt_bvh.h"
+#include "rt_device.h"
 #include "rt_math.h"
 #include "rt_scene.h"
-#include "../../include/rt_amd.h"
 
 using namespace rtm;
 using namespace rtb;
+using namespace rtd;
 using rt::DCamera;
 using rt::DInst;
 using rt::DLight;
@@ -57,36 +53,11 @@ using rt::DTri;
 
 namespace {
 
-constexpr int MAX_FRAMES = 10;           // renv::gpu::MAX_DEPTH (scene.cu:25)
-constexpr int BVH_WG_LEAVES = 8192;      // single-workgroup BVH build (LDS keys); above: bvh_build_large
-constexpr int BVH_MAX_LEAVES = 1 << 24;  // padded leaves (int indexing of the 12n-float pair records)
-#ifndef RT_BLOCK
-#define RT_BLOCK 1024
-#endif
-constexpr int TRACE_BLOCK_P = RT_BLOCK;  // persistent block: 16 waves (4 per SIMD, 128-VGPR budget) sharing one LDS BVH copy
+// (launch geometry, tuning macros and the kernel argument structs the host shares: rt_device.h)
 constexpr int LDS_LIMIT = 150 * 1024;    // above this the BVH is read from global memory
 constexpr int PARK_LDS_LIMIT = 158 * 1024;   // BVH image + parking area (160 KB per CU)
-#ifndef RT_NQ
-#define RT_NQ 8
-#endif
-constexpr int NQ = RT_NQ;                    // work queues (one per XCD dispatch slot), 64-B apart
-// work counters: [16 q] queue q's tickets, [16 NQ] the heavy list's, [16 (NQ + 1 + q)] the
-// length of live-group list q (sky_kernel), [16 (2 NQ + 1)] the length of this frame's heavy
-// live list (hist = 2)
-constexpr int WORK_INTS = 16 * (2 * NQ + 2);
+// (work counter layout: WORK_INTS, rt_device.h)
 constexpr int WORK_HEAVY_LEN = 16 * (2 * NQ + 1);
-// Statistics / profiling counters (d_stats): [0, 22) rt_stats and the PROF step counts and
-// cycle split (rt_experiment), [22, 24) spare, [24, 64) the PROF variant's query-occupancy
-// counters (PROF_* below, rt_frame_work).
-constexpr int STATS_N = 64;
-enum : int {
-    PROF_LANES_PRIMARY = 24, PROF_LANES_SECONDARY = 25, PROF_LANES_SHADOW = 26, PROF_LANES_UNLIT = 27,
-    PROF_LIVE_WQ = 28, PROF_LIVE_LANES = 29,
-    PROF_HIST_WQ = 30,      // [8] live wave queries by active lanes, buckets of 8 (1-8, 9-16, ..., 57-64)
-    PROF_HIST_PAIR = 38,    // [8] their child-pair steps
-    PROF_HIST_LEAF = 46,    // [8] their leaf visits
-    PROF_END = 54
-};
 // PROF kernels keep the occupancy counters [24, PROF_END) per wave in LDS (a global atomic per wave
 // query on a few shared addresses serialised and perturbed the profile 30x) and add them to d_stats
 // once per wave at the end
@@ -123,44 +94,12 @@ __device__ __forceinline__ float pow_fast(float x, float y) {
 
 
 
-// Unsigned division by a launch constant d with host-computed magic numbers (round-up
-// method: l = ceil(log2 d), m = floor(2^32 (2^l - d) / d) + 1, q = (t + ((n - t) >> 1)) >> (l - 1),
-// t = mulhi(n, m); exact for every 32-bit n; d = 1 passes through).  Wave-uniform operands stay
-// on the scalar unit (the compiler's own sequence keeps a VGPR reciprocal live across the
-// group loop, which was spilled and reloaded from scratch at every group).
-struct UDiv { unsigned m, d; int s; };
-__host__ inline UDiv udiv_make(unsigned d) {
-    UDiv r{0u, d, 0};
-    if (d <= 1) return r;
-    int l = 0;
-    while ((1ull << l) < d) l++;
-    r.m = (unsigned)((((1ull << l) - d) << 32) / d + 1);
-    r.s = l - 1;
-    return r;
-}
+// UDiv (rt_device.h): unsigned division by a launch constant through host-computed magic numbers
 __device__ __forceinline__ unsigned udiv(unsigned n, const UDiv& D) {
     if (D.d <= 1) return n;
     const unsigned t = __umulhi(n, D.m);
     return (t + ((n - t) >> 1)) >> D.s;
 }
-
-struct SceneView {           // read-only scene data (HBM, L2-resident)
-    const DTri* __restrict__ tris;
-    const DMesh* __restrict__ meshes;
-    const DInst* __restrict__ insts;
-    const DMat* __restrict__ mats;
-    const DLight* __restrict__ lights;
-    const float4* node_pair;  // BVH child pairs, heap order (written by bvh_build_kernel), see BvhRefs
-    const float4* fnode;      // ordered LBVH of the fast kernel (bvh_build_kernel)
-    int n_real, ftree;        // its leaf count; 1 if usable (>= 2 leaves, depth <= 31)
-    const int* leaf_inst;
-    const float4* inst4;      // compact instance records
-    int n_leaf, n_inst, n_lights, use_bvh;
-    int n_mats, n_tris, n_meshes;   // record counts (LDS shading cache, M_SHADE)
-    int ident_all;            // every instance and mesh rotation is the identity (cube worlds)
-    float prune_abs;          // distance-pruning slack M0 (< 0: pruning off), see closest_hit
-    const TriAx* tri_ax;      // axis-plane triangle records (fast kernel; null unless ident_all)
-};
 
 // Parts of a DTri (rt_scene.h): the plane filter's 32-B head and the rest of the test.
 struct TriHot { V3 pn, a; float b_x, b_y; };
@@ -208,35 +147,6 @@ struct BvhRefs {
     const DTri* tris;
     const DMesh* meshes;
 };
-
-// Tuning parameters (build switches; the A/B logs under profiles/ record the values tried).
-#ifndef RT_HIST_GROUPS_PER_WAVE
-#define RT_HIST_GROUPS_PER_WAVE 12  // longest-first history only at <= this many groups per wave
-#endif
-#ifndef RT_SMALL_FRAME_GPW
-#define RT_SMALL_FRAME_GPW 48       // groups per wave (half grid) below which overlapping frames take a quarter of the CUs
-#endif
-#ifndef RT_HEAVY_Q_DEFAULT
-#define RT_HEAVY_Q_DEFAULT 6        // hist = 2: a group of >= this many wave queries is heavy
-#endif
-#ifndef RT_HEAVY_STATIC
-#define RT_HEAVY_STATIC 1    // frames issued alone: heavy-list tickets assigned statically (trace_kernel)
-#endif
-#ifndef RT_TPC_WIDE
-#define RT_TPC_WIDE 16       // live-list tickets of one-pixel groups (spp >= 64, M_PART): 16 consecutive pixels
-#endif
-#ifndef RT_LDS_SUM
-#define RT_LDS_SUM 1         // spp >= 16 in parked kernels: per-channel in-order sample sums through LDS
-#endif
-#ifndef RT_TPC
-#define RT_TPC 3             // work indices claimed per ticket (trace_kernel's group loop) over all
-                             // groups; 3 vs 2: -0.8% world8_stress, -1.3% world8 (profiles/r01/ab_tpc_v33.log)
-#endif
-#ifndef RT_TPC_LIVE
-#define RT_TPC_LIVE 1        // the same over live-group lists (sky pre-pass): ~8x fewer groups per
-                             // wave, one per ticket balances them (profiles/r02/sky_live_tpc.log)
-#endif
-constexpr int TPC = RT_TPC;
 
 // One child box's slab interval [lo, hi] against a ray through its reciprocals (ray_inv):
 // fma(m - o, 1/d, -+bias) per face, the bias carrying the zero-direction skip (ray_inv).
@@ -359,7 +269,8 @@ __device__ __forceinline__ void pair_hit_tt2c(const float4* rec, const Ray& r, c
         "s_andn2_b64 %[m0], %[m1], %[m0]"                   // active, some outcome uncertain
         : [h0] "=&s"(h0), [h1] "=&s"(h1), [m0] "=&s"(m0), [m1] "=&s"(m1), [ta] "=&v"(ta), [tb] "=&v"(tb)
         : [a0] "v"(a0), [b0] "v"(b0), [a1] "v"(a1), [b1] "v"(b1), [c0] "v"(c0), [e0] "v"(e0), [c1] "v"(c1),
-          [e1] "v"(e1), [d0] "v"(d0), [d1] "v"(d1), [nan] "v"(QNAN), [ct] "v"(ct));
+          [e1] "v"(e1), [d0] "v"(d0), [d1] "v"(d1), [nan] "v"(QNAN), [ct] "v"(ct)
+        : "scc");
     if (__builtin_expect(m0 != 0, 0)) {
         const bool active = ct == ct;
         const bool k0 = a0 <= b0 || c0 > e0, k1 = a1 <= b1 || c1 > e1;
@@ -833,56 +744,6 @@ struct Frame {
     int last_mat, type, depth, in_obj;
 };
 struct SavedFrame { Frame f; V3 hit_pt, norm; };   // suspended under its reflection child
-
-struct TraceParams {
-    DCamera cam;
-    V3 dist_atten;
-    V4 ambience;
-    int W, H, row0, row_step, n_rows, compact, spp, depth;
-    float spp_recip;          // 2^-k when spp = 2^k (exact reciprocal), else 0
-    int lanes_per_px, px_per_wave, gw, gh, n_gx, n_groups;   // sample-parallel lane mapping
-    int l_shift, gw_shift;    // log2(lanes_per_px), log2(gw) when powers of two, else -1
-    UDiv div_ngx, div_perq;   // g / n_gx and ticket permutation mod per-queue length
-    int scramble;             // ticket -> group permutation factor (coprime with the queue length)
-    int scramble_small;       // 1: ticket * scramble < 2^32 for every ticket (32-bit modulo)
-    const float2* __restrict__ spp_off;
-    uint32_t* rgba;
-    float4* radiance;
-    int* hit_inst;
-    int* hit_tri;
-    unsigned long long* stats;
-    int* work;                // persistent-wave work counters (zeroed before each launch); work[16 NQ]: heavy list
-    // Longest-first scheduling history (fast frames only, hist = 1): the previous frame's
-    // heavy groups (hl_prev[0, *hc_prev)) run first and are skipped in the normal queues
-    // (hf_prev); this frame records its own into the *_next buffers.  hs_* = summed group
-    // durations (100 MHz ticks) for the threshold (4x the mean group).
-    int hist, heavy_cap;      // heavy_cap: most heavy groups recorded per frame
-    // hist = 2 (whole frames with the sky pre-pass): heavy = a group that took >= heavy_q wave
-    // queries (counted, no clock); hf_next[g] = 1 records it, and the next frame's sky pre-pass
-    // puts the groups flagged in hf_prev on a heavy live list the trace kernel drains first
-    int heavy_q;
-    const int* hl_prev; int* hl_next;
-    const unsigned char* hf_prev; unsigned char* hf_next;
-    const unsigned long long* hctl_prev; unsigned long long* hctl_next;   // {count, sum}
-    int occl_exit;            // shadow-ray occlusion early exit (all-opaque scene, no statistics)
-    const float4* atlas;      // textured mode: atlas texels, byte / 255 (rt_scene_set_atlas)
-    int atlas_w, atlas_h;
-    int* dbg_log;             // debug_cast event log (NULL in normal frames)
-    int dbg_x, dbg_y;
-    unsigned* gdur;           // profiling (rt_profile_groups): per-group duration, 100 MHz ticks; NULL normally
-    // Sky pre-pass (sky_kernel, fast frames): gsky[g] = 1 when no primary of group g enters
-    // the tree's root -- its outputs are written already and the trace kernel skips it.
-    // NULL: no pre-pass (the trace kernel runs the same test itself).
-    const unsigned char* gsky;
-    // Live-group lists (sky_kernel): queue q's groups are live[q * live_cap + i] for i below
-    // work[16 (NQ + 1 + q)], in arrival order.  NULL: queue q's groups are q + NQ j.
-    const int* live; int live_cap;
-    int tpc;                  // work indices per ticket (normal queues)
-    int grid_waves;           // waves of this launch (the heavy list's static rounds)
-    int heavy_static;         // 1: heavy-list tickets assigned statically (frames issued alone)
-    int unlit_skip;           // fast frames: no shadow segments for a light whose phong factor is zero (1),
-                              // and no phong term for it either (2)
-};
 
 // The launch's TraceParams read in place from the kernel-argument segment (constant address
 // space: scalar loads) through a pointer made fresh at each use site.  Passed by value and
@@ -1998,10 +1859,6 @@ __device__ __forceinline__ bool cone_misses_boxes(const TraceParams& P, int g, c
 // appended to list (block % NQ) with one atomic.  Small blocks keep ~8 per CU resident: the
 // per-ray tests are latency-bound chains (measured: 1024-group blocks, 102 -> 71 us per
 // 1080p frame; per-ray tests of every group, 108 us).
-#ifndef RT_SKY_WAVES
-#define RT_SKY_WAVES 4       // waves per sky_kernel block (64 groups per block)
-#endif
-constexpr int SKY_THREADS = 64 * RT_SKY_WAVES;
 // the heavy-list append runs on threads 64..127 beside the live list's 0..63 (one wave: after it)
 constexpr int SKY_HOFF = SKY_THREADS >= 128 ? 64 : 0;
 template <bool BRUTE>
@@ -2420,750 +2277,51 @@ __global__ void kat_kernel(int op, int n, const float* a, const float* b, const 
     }
 }
 
+// ---------------------------------------------------------------------------
+// Small kernels of the host runtime's side paths
+// ---------------------------------------------------------------------------
+// Multi-device frames (rt_multi.cpp): the gathered row-cyclic slices back into frame order.
+__global__ __launch_bounds__(256) void unpermute_kernel(const uint32_t* __restrict__ g, uint32_t* __restrict__ out, int W,
+                                                        int H, int N, int rows_max) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)W * H) return;
+    const int y = (int)(i / W), x = (int)(i - (long long)y * W);
+    out[i] = g[((size_t)(y % N) * rows_max + y / N) * W + x];         // frame row y = slice y % N, row y / N
+}
+
+extern "C" {   // (unmangled names: profiler traces are searched for them, tools/pmc_step.py)
+// Profile marker (rt_profile_marker): an empty kernel whose grid (64 x tag threads) tells a
+// rocprofv3 trace where a caller's timed region begins and ends (tools/pmc_step.py).
+__global__ __launch_bounds__(64) void profile_marker_kernel(int tag) { (void)tag; }
+
+// rt_copy_engines_warm's gate: one wave that holds the copies queued behind it pending until the
+// host opens the gate (a flag in coherent host memory) or `max_ticks` of the wall clock pass, so
+// that every queued copy finds the engines of the copies before it busy.  Vector loads only.
+__global__ __launch_bounds__(64) void copy_gate_kernel(const unsigned* flag, unsigned long long max_ticks) {
+    const unsigned long long t0 = wall_clock64();
+    while (__hip_atomic_load(flag, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM) == 0u && wall_clock64() - t0 < max_ticks)
+        __builtin_amdgcn_s_sleep(32);
+}
+}  // extern "C"
+
 }  // namespace
 
 // ===========================================================================
-// Host side: scene object and the C ABI
+// Launch layer (rt_device.h): the only functions that name a kernel
 // ===========================================================================
-struct MultiDev;
-// Host framebuffer in pinned memory: rt_update_scene's device-to-host copy of the frame (the
-// reference's post-condition, raytracer.cu:102-120) is then one direct transfer; into pageable
-// memory HIP stages it in chunks through a bounce buffer.  Pageable fallback when pinning fails
-// (no HIP device: the scene is still built and exported, nothing is rendered).
-struct HostCanvas {
-    uint32_t* p = nullptr;
-    size_t n = 0;
-    bool pinned = false;
-    HostCanvas() = default;
-    HostCanvas(const HostCanvas&) = delete;
-    HostCanvas& operator=(const HostCanvas&) = delete;
-    ~HostCanvas() { release(); }
-    void release() {
-        if (p) { if (pinned) (void)hipHostFree(p); else free(p); }
-        p = nullptr; n = 0; pinned = false;
-    }
-    void assign(size_t m, uint32_t v) {
-        release();
-        if (!m) return;
-        if (hipHostMalloc((void**)&p, m * sizeof(uint32_t), hipHostMallocDefault) == hipSuccess) {
-            pinned = true;
-        } else {
-            (void)hipGetLastError();
-            p = static_cast<uint32_t*>(malloc(m * sizeof(uint32_t)));
-            if (!p) return;
-        }
-        n = m;
-        std::fill(p, p + m, v);
-    }
-    uint32_t* data() { return p; }
-    const uint32_t* data() const { return p; }
-    size_t size() const { return n; }
-    uint32_t operator[](size_t i) const { return p[i]; }
-};
+namespace rtd {
 
-struct rt_scene {
-    rt::Scene h;
-    MultiDev* multi = nullptr;                   // rt_scene_set_devices: frames split over several GPUs
-    bool finished = false;
-    int device = -1;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    // device buffers
-    DTri* d_tris = nullptr; DMesh* d_meshes = nullptr; DInst* d_insts = nullptr; DMat* d_mats = nullptr;
-    DLight* d_lights = nullptr; Box* d_mesh_box = nullptr; Box* d_tree = nullptr;
-    float4* d_node_pair = nullptr; int* d_leaf = nullptr;
-    float4* d_fnode = nullptr; int n_real = 0, fdepth = 0;   // ordered LBVH (fast kernel)
-    void* d_bscratch = nullptr;                  // bvh_build_large's sort buffers (scenes above BVH_WG_LEAVES)
-    float4* d_inst4 = nullptr;
-    TriAx* d_tri_ax = nullptr;                   // axis-plane triangle records (tri_axis_records)
-    int* d_work = nullptr; int n_cu = 0;
-    bool work_zeroed = false;                    // bvh_build_kernel zeroed d_work for the next trace launch
-    // longest-first scheduling history (TraceParams::hist): double-buffered by frame parity
-    int* d_hlist[2] = {nullptr, nullptr};
-    unsigned char* d_hflag[2] = {nullptr, nullptr};
-    unsigned long long* d_hctl = nullptr;        // [2][count, sum]
-    int hist_cap = 0, hist_parity = 0;
-    int hctl_zeroed = -1;                        // heavy-list slot the pending bvh_build_kernel zeroes (-1: none)
-    long long hist_key[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
-    unsigned char* d_gsky = nullptr; int gsky_cap = 0;   // sky pre-pass flags (TraceParams::gsky)
-    int* d_live = nullptr; int live_cap = 0;             // sky pre-pass live-group lists [NQ][live_cap]
-    float2* d_spp = nullptr; int spp_cap = 0;
-    unsigned long long* d_stats = nullptr;
-    uint32_t* d_canvas = nullptr;
-    int* d_dbg = nullptr;
-    float4* d_atlas = nullptr;                   // atlas texels (float4, byte / 255)
-    bool atlas_dirty = false;
-    void* d_out[4] = {nullptr, nullptr, nullptr, nullptr};   // staging for host_outputs
-    std::vector<hipEvent_t> tev;      // timing=1 events, 4 per frame: bvh start/stop, trace start/stop (pool)
-    size_t tev_used = 0;
-    size_t d_out_px = 0;
-    int n_leaf = 0;
-    bool uploaded = false, bvh_valid = false;
-    HostCanvas canvas;               // host framebuffer (Canvas buffer, canvas.cu:7), pinned
-    // Frame slots (rt_scene_set_frame_slots): with n > 1 slots, consecutive frames rotate
-    // through n copies of the per-frame state (BVH, work counters, scheduling history), so a
-    // frame on another stream can start on CUs freed by the previous frames' tails.  The
-    // fields above always hold the current slot; store[i] the others (store[cur] is stale).
-    // Instance arrays are per-slot state too (rt_builder_set_trans after finish): a frame in
-    // flight keeps the poses its BVH was built from, and the next frame of a slot receives the
-    // current poses by a stream-ordered copy (sync_slot_insts) from the slot's pinned staging.
-    DInst* h_insts_pin = nullptr; float4* h_inst4_pin = nullptr;   // current slot's staging (pinned)
-#ifndef RT_OVERLAP_DEFAULT
-#define RT_OVERLAP_DEFAULT RT_OVERLAP_HALF   // (RT_OVERLAP_FULL: the A/B arm of round 3's policy)
-#endif
-    int overlap = RT_OVERLAP_DEFAULT;                                // rt_scene_set_overlap
-    int ranks_per_device = 1;                    // > 1: virtual ranks of rt_scene_set_devices share this device
-    unsigned slot_inst_gen = 0;                  // instance generation the current slot's arrays hold
-    unsigned inst_gen = 1;                       // generation of the host instance array (set_trans bumps it)
-    unsigned shape_gen = 0;                      // generation n_real / fdepth were computed for
-#ifndef RT_MAX_SLOTS
-#define RT_MAX_SLOTS 8
-#endif
-    static constexpr int MAX_SLOTS = RT_MAX_SLOTS;
-    struct Slot {
-        Box* d_tree = nullptr; float4* d_node_pair = nullptr; int* d_leaf = nullptr; float4* d_fnode = nullptr;
-        void* d_bscratch = nullptr;
-        int* d_work = nullptr; bool work_zeroed = false, bvh_valid = false;
-        int* d_hlist[2] = {nullptr, nullptr}; unsigned char* d_hflag[2] = {nullptr, nullptr};
-        unsigned long long* d_hctl = nullptr;
-        int hist_cap = 0, hist_parity = 0, hctl_zeroed = -1;
-        long long hist_key[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
-        unsigned char* d_gsky = nullptr; int gsky_cap = 0;
-        int* d_live = nullptr; int live_cap = 0;
-        DInst* d_insts = nullptr; float4* d_inst4 = nullptr;
-        DInst* h_insts_pin = nullptr; float4* h_inst4_pin = nullptr;
-        unsigned slot_inst_gen = 0;
-    } store[MAX_SLOTS];
-    int n_slots = 1, cur_slot = 0;
-    // Last frame of each slot (recorded on its stream, also with one slot): the next frame of
-    // the slot, and side entries (debug_cast, experiments), wait for it stream-ordered.
-    hipEvent_t slot_done[MAX_SLOTS] = {};
-    bool slot_pending[MAX_SLOTS] = {};
-    ~rt_scene();
-};
+size_t scene_image_bytes(const SceneView& S) { return lds_bytes(S, true, true); }
 
-// Move the current per-frame state into store[cur_slot] and load slot i's.
-void select_slot(rt_scene* s, int i) {
-    if (i == s->cur_slot) return;
-    auto xfer = [](auto& a, auto& b) { a = b; };
-    auto move = [&](rt_scene::Slot& o, bool save) {
-        auto f = [&](auto& field, auto& slot) { if (save) xfer(slot, field); else xfer(field, slot); };
-        f(s->d_tree, o.d_tree); f(s->d_node_pair, o.d_node_pair); f(s->d_leaf, o.d_leaf); f(s->d_fnode, o.d_fnode);
-        f(s->d_bscratch, o.d_bscratch);
-        f(s->d_work, o.d_work); f(s->work_zeroed, o.work_zeroed); f(s->bvh_valid, o.bvh_valid);
-        for (int p = 0; p < 2; p++) { f(s->d_hlist[p], o.d_hlist[p]); f(s->d_hflag[p], o.d_hflag[p]); }
-        f(s->d_hctl, o.d_hctl); f(s->hist_cap, o.hist_cap); f(s->hist_parity, o.hist_parity);
-        f(s->hctl_zeroed, o.hctl_zeroed);
-        for (int k = 0; k < 8; k++) f(s->hist_key[k], o.hist_key[k]);
-        f(s->d_gsky, o.d_gsky); f(s->gsky_cap, o.gsky_cap); f(s->d_live, o.d_live); f(s->live_cap, o.live_cap);
-        f(s->d_insts, o.d_insts); f(s->d_inst4, o.d_inst4);
-        f(s->h_insts_pin, o.h_insts_pin); f(s->h_inst4_pin, o.h_inst4_pin);
-        f(s->slot_inst_gen, o.slot_inst_gen);
-    };
-    move(s->store[s->cur_slot], true);
-    move(s->store[i], false);
-    s->cur_slot = i;
-}
-
-namespace {
-thread_local std::string g_err;
-thread_local int g_device = 0;
-
-int fail(int code, const std::string& msg) { g_err = msg; return code; }
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail(RT_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
-
-template <class T> void dfree(T*& p) { if (p) { (void)hipFree(p); p = nullptr; } }
-
-int padded(int n_t) {   // raytracer.cu:79: 1 << ceil(log2(n))
-    if (n_t <= 0) return 0;
-    int n = 1;
-    while (n < n_t) n <<= 1;
-    return n;
-}
-
-int upload_inst4(rt_scene* s);
-int ensure_other_slot(rt_scene* s);
-int mirror_slot_caps(rt_scene* s);
-
-// TriAx records (rt_math.h) of the axis-plane triangle path: axis, plane coordinate,
-// shared-plane flag and the in-plane reject box with its host-checked error bound.
-std::vector<TriAx> tri_axis_records(const rt::Scene& h) {
-    const double u = 0x1p-24;
-    std::vector<TriAx> out(h.d_tris.size());
-    auto c3 = [](V3 v, int a) { return a == 0 ? v.x : a == 1 ? v.y : v.z; };
-    for (size_t i = 0; i < h.d_tris.size(); i++) {
-        const DTri& T = h.d_tris[i];
-        TriAx x{};
-        x.code = 3;
-        int ax = -1, zeros = 0;
-        for (int a = 0; a < 3; a++) {
-            const float c = c3(T.pn, a);
-            if (c == 0.0f) zeros++;                          // +0 or -0
-            else if (c == 1.0f || c == -1.0f) ax = a;
-        }
-        if (zeros == 2 && ax >= 0 && c3(T.b, ax) == c3(T.a, ax) && c3(T.c, ax) == c3(T.a, ax)) {
-            x.code = ax;
-            x.a_ax = c3(T.a, ax);
-            const int au = (ax + 1) % 3, av = (ax + 2) % 3;
-            const V3 P[3] = {T.a, T.b, T.c};
-            double D = 0, lo[2] = {INFINITY, INFINITY}, hi[2] = {-INFINITY, -INFINITY};
-            for (int k = 0; k < 3; k++) {
-                const V3 p = P[k], q = P[(k + 1) % 3];
-                const double dx = (double)p.x - q.x, dy = (double)p.y - q.y, dz = (double)p.z - q.z;
-                D = std::max(D, std::sqrt(dx * dx + dy * dy + dz * dz));
-                const double pc[2] = {c3(p, au), c3(p, av)};
-                for (int j = 0; j < 2; j++) { lo[j] = std::min(lo[j], pc[j]); hi[j] = std::max(hi[j], pc[j]); }
-            }
-            // exact (double) doubled area vs the stored float area
-            const double e1[3] = {(double)T.b.x - T.a.x, (double)T.b.y - T.a.y, (double)T.b.z - T.a.z};
-            const double e2[3] = {(double)T.c.x - T.a.x, (double)T.c.y - T.a.y, (double)T.c.z - T.a.z};
-            const double cx = e1[1] * e2[2] - e1[2] * e2[1], cy = e1[2] * e2[0] - e1[0] * e2[2], cz = e1[0] * e2[1] - e1[1] * e2[0];
-            const double A = std::sqrt(cx * cx + cy * cy + cz * cz);
-            const double m = 1e-4 * D, win = 1e3 * D, off = m;
-            bool ok = A > 0 && D > 0 && std::isfinite(A) && std::isfinite(D) && std::isfinite(win);
-            if (ok) {
-                const double eta = std::fabs((double)T.area - A) / A + 1e-12;
-                auto margin = [&](double e) {
-                    return (e / D) * (1 - 5.6 * u - eta) - (5.6 * u + eta) - 41.8 * u * (D + e + off) * (D + e + off) / A - 1.01e-5;
-                };
-                ok = margin(m) > 0 && margin(win) > 0;
-            }
-            if (ok) {
-                // bounds rounded outwards to float
-                x.ulo = std::nextafter((float)(lo[0] - m), -INFINITY); x.uhi = std::nextafter((float)(hi[0] + m), INFINITY);
-                x.vlo = std::nextafter((float)(lo[1] - m), -INFINITY); x.vhi = std::nextafter((float)(hi[1] + m), INFINITY);
-                x.win = std::nextafter((float)win, 0.0f);
-                x.off = std::nextafter((float)off, 0.0f);
-                x.code |= 8;
-            }
-        }
-        out[i] = x;
-    }
-    // shared plane with the next triangle of the same mesh
-    for (const DMesh& M : h.d_meshes)
-        for (int t = M.tri_begin; t + 1 < M.tri_begin + M.tri_count; t++) {
-            const TriAx &x = out[t], &y = out[t + 1];
-            if ((x.code & 3) != 3 && (x.code & 3) == (y.code & 3)) {
-                uint32_t bx, by;
-                memcpy(&bx, &x.a_ax, 4); memcpy(&by, &y.a_ax, 4);
-                if (bx == by) out[t].code |= 4;
-            }
-        }
-    return out;
-}
-
-// Leaf count and depth (internal nodes on the longest root-leaf path) of the ordered
-// LBVH bvh_build_kernel will build: the same box, Morton and sort arithmetic on the
-// host (RT_HD functions).  The fast traversal's stack holds <= FT_MAX_DEPTH entries.
-constexpr int FT_MAX_DEPTH = 31;
-// Mesh boxes: Trimesh::compute_bounding_box (trimesh.cu:21-32, sequential fit order) and
-// the mesh pose.  They depend only on the immutable mesh data, so they are computed once
-// here; the per-frame build (bvh_build_kernel) redoes everything per instance.
-std::vector<Box> mesh_boxes(const rt::Scene& h) {
-    std::vector<Box> mbox(h.d_meshes.size());
-    for (size_t m = 0; m < h.d_meshes.size(); m++) {
-        Box b; b.nd = 0; b.mn = b.mx = v3(0, 0, 0);
-        const DMesh& mesh = h.d_meshes[m];
-        for (int t = mesh.tri_begin; t < mesh.tri_begin + mesh.tri_count; t++) {
-            fit_vertex(b, h.d_tris[t].a); fit_vertex(b, h.d_tris[t].b); fit_vertex(b, h.d_tris[t].c);
-        }
-        mbox[m] = from_local(b, mesh.pose);
-    }
-    return mbox;
-}
-// n_real and the deepest internal node's depth (root = 1).
-void ordered_tree_shape(const rt::Scene& h, int* n_real, int* depth) {
-    const std::vector<Box> mbox = mesh_boxes(h);
-    std::vector<std::pair<unsigned long long, int>> kv;
-    bool ordered = true;                                      // every real box finite with mn <= mx
-    for (size_t i = 0; i < h.d_insts.size(); i++) {
-        const Box b = from_local(mbox[h.d_insts[i].mesh], h.d_insts[i].pose);
-        if (b.nd) {
-            kv.push_back({z_order(neg(box_center(b))), (int)i});
-            const float c[6] = {b.mn.x, b.mn.y, b.mn.z, b.mx.x, b.mx.y, b.mx.z};
-            for (float x : c) ordered = ordered && std::isfinite(x);
-            ordered = ordered && b.mn.x <= b.mx.x && b.mn.y <= b.mx.y && b.mn.z <= b.mx.z;
-        }
-    }
-    std::stable_sort(kv.begin(), kv.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
-    const int nr = (int)kv.size();
-    *n_real = nr;
-    *depth = 0;
-    // The fast traversal takes every record of the ordered tree as a proper box (no
-    // degenerate / NaN test per child, pair_hit_tt): a pose that makes a box non-finite
-    // leaves the frame to the heap kernels.
-    if (!ordered) { *depth = 1 << 20; return; }
-    if (nr < 2) return;
-    std::vector<unsigned long long> keys(nr);
-    for (int i = 0; i < nr; i++) keys[i] = kv[i].first;
-    std::vector<int> child(2 * (nr - 1));                   // internal children (-1: leaf)
-    for (int i = 0; i < nr - 1; i++) {
-        int first, last, gamma;
-        fnode_split(keys.data(), nr, i, first, last, gamma);
-        child[2 * i] = gamma + 1 == last ? -1 : gamma + 1;
-        child[2 * i + 1] = gamma == first ? -1 : gamma;
-    }
-    std::vector<std::pair<int, int>> todo{{0, 1}};
-    while (!todo.empty()) {
-        const auto [node, d] = todo.back();
-        todo.pop_back();
-        *depth = std::max(*depth, d);
-        if (d > nr) { *depth = 1 << 20; return; }          // malformed: disable the fast tree
-        for (int c = 0; c < 2; c++) if (child[2 * node + c] >= 0) todo.push_back({child[2 * node + c], d + 1});
-    }
-}
-void free_atlas(rt_scene* s);
-int ensure_atlas(rt_scene* s);
-
-// The scene's own stream, created on first use: a caller passing its own streams (frame
-// pipelining) keeps every HIP stream of the process on a hardware queue of its own
-// (GPU_MAX_HW_QUEUES = 4; streams beyond that share queues and serialise).
-hipStream_t sstream(rt_scene* s) {
-    if (!s->stream) (void)hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking);
-    return s->stream;
-}
-
-int upload(rt_scene* s) {
-    if (s->uploaded) return RT_OK;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(RT_ERR_NODEV, "no HIP device available");
-    s->device = g_device;
-    HIPCHK(hipSetDevice(s->device));
-    hipDeviceProp_t prop;
-    HIPCHK(hipGetDeviceProperties(&prop, s->device));
-    if (std::string(prop.gcnArchName).find("gfx950") == std::string::npos)
-        return fail(RT_ERR_NODEV, std::string("device is ") + prop.gcnArchName + ", this build targets gfx950");
-    for (auto& e : s->ev) HIPCHK(hipEventCreate(&e));
-    const rt::Scene& h = s->h;
-    auto up = [&](auto*& dst, const auto& vec) -> int {
-        using T = typename std::remove_reference<decltype(vec)>::type::value_type;
-        size_t bytes = std::max<size_t>(1, vec.size()) * sizeof(T);
-        HIPCHK(hipMalloc((void**)&dst, bytes));
-        if (!vec.empty()) HIPCHK(hipMemcpy(dst, vec.data(), vec.size() * sizeof(T), hipMemcpyHostToDevice));
-        return RT_OK;
-    };
-    int r;
-    if ((r = up(s->d_tris, h.d_tris)) || (r = up(s->d_meshes, h.d_meshes)) || (r = up(s->d_insts, h.d_insts)) ||
-        (r = up(s->d_mats, h.d_mats)) || (r = up(s->d_lights, h.d_lights)))
-        return r;
-    s->n_leaf = padded((int)h.d_insts.size());
-    if (s->n_leaf > BVH_MAX_LEAVES) return fail(RT_ERR_LIMIT, "more than 2^24 padded instances");
-    s->n_cu = prop.multiProcessorCount;
-    size_t nl = std::max(1, s->n_leaf);
-    HIPCHK(hipMalloc((void**)&s->d_node_pair, 3 * nl * sizeof(float4)));
-    ordered_tree_shape(h, &s->n_real, &s->fdepth);
-    s->shape_gen = s->inst_gen;
-    HIPCHK(hipMalloc((void**)&s->d_fnode, 4 * (size_t)std::max(1, s->n_real - 1) * sizeof(float4)));
-    HIPCHK(hipMalloc((void**)&s->d_leaf, nl * sizeof(int)));
-    HIPCHK(hipMalloc((void**)&s->d_inst4, std::max<size_t>(1, h.d_insts.size()) * sizeof(float4)));
-    HIPCHK(hipMalloc((void**)&s->d_work, WORK_INTS * sizeof(int)));
-    if ((r = upload_inst4(s)) != RT_OK) return r;
-    if ((r = up(s->d_tri_ax, tri_axis_records(h))) != RT_OK) return r;
-    if ((r = up(s->d_mesh_box, mesh_boxes(h))) != RT_OK) return r;
-    HIPCHK(hipMalloc((void**)&s->d_tree, 2 * nl * sizeof(Box)));
-    if (s->n_leaf > BVH_WG_LEAVES) HIPCHK(hipMalloc(&s->d_bscratch, bvh_large_scratch_bytes(s->n_leaf)));
-    HIPCHK(hipMalloc((void**)&s->d_stats, STATS_N * sizeof(unsigned long long)));
-    HIPCHK(hipMalloc((void**)&s->d_canvas, (size_t)h.cam.W * h.cam.H * sizeof(uint32_t)));
-    HIPCHK(hipMalloc((void**)&s->d_dbg, 4096 * sizeof(int)));
-    for (auto& e : s->slot_done) if (!e) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    s->slot_inst_gen = s->inst_gen;
-    s->uploaded = true;
-    if (s->n_slots > 1) return ensure_other_slot(s);
-    return RT_OK;
-}
-
-// compact instance records for the trace kernel: (p, mesh | 0x80000000 when the pose is not identity)
-void fill_inst4(const rt::Scene& h, float4* v) {
-    for (size_t i = 0; i < h.d_insts.size(); i++) {
-        const DInst& d = h.d_insts[i];
-        uint32_t w = (uint32_t)d.mesh | (d.pose.identity ? 0u : 0x80000000u);
-        float fw; memcpy(&fw, &w, 4);
-        v[i] = make_float4(d.pose.p.x, d.pose.p.y, d.pose.p.z, fw);
-    }
-}
-int upload_inst4(rt_scene* s) {
-    std::vector<float4> v(s->h.d_insts.size());
-    fill_inst4(s->h, v.data());
-    if (!v.empty()) HIPCHK(hipMemcpy(s->d_inst4, v.data(), v.size() * sizeof(float4), hipMemcpyHostToDevice));
-    return RT_OK;
-}
-
-// Bring the current slot's instance arrays to the host's generation, stream-ordered on `st`
-// (after the slot's previous frame, which the caller has made `st` wait for).  The pinned
-// staging is rewritten only once the copy that last read it has run (the slot's last frame,
-// recorded after that copy).
-int sync_slot_insts(rt_scene* s, hipStream_t st) {
-    if (s->slot_inst_gen == s->inst_gen) return RT_OK;
-    const size_t n = s->h.d_insts.size();
-    if (n) {
-        if (!s->h_insts_pin) {
-            HIPCHK(hipHostMalloc((void**)&s->h_insts_pin, n * sizeof(DInst), hipHostMallocDefault));
-            HIPCHK(hipHostMalloc((void**)&s->h_inst4_pin, n * sizeof(float4), hipHostMallocDefault));
-            int r;
-            if (s->n_slots > 1 && (r = mirror_slot_caps(s)) != RT_OK) return r;
-        } else if (s->slot_pending[s->cur_slot]) {
-            HIPCHK(hipEventSynchronize(s->slot_done[s->cur_slot]));
-        }
-        memcpy(s->h_insts_pin, s->h.d_insts.data(), n * sizeof(DInst));
-        fill_inst4(s->h, s->h_inst4_pin);
-        HIPCHK(hipMemcpyAsync(s->d_insts, s->h_insts_pin, n * sizeof(DInst), hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(s->d_inst4, s->h_inst4_pin, n * sizeof(float4), hipMemcpyHostToDevice, st));
-        HIPCHK(hipEventRecord(s->slot_done[s->cur_slot], st));   // covers the staging until the frame records it again
-        s->slot_pending[s->cur_slot] = true;
-    }
-    s->slot_inst_gen = s->inst_gen;
-    return RT_OK;
-}
-
-// Ordered-LBVH shape (leaf count, depth) for the current host poses: instances that moved
-// change the Morton order and with it the tree depth the fast traversal's stack must hold.
-void refresh_shape(rt_scene* s) {
-    if (s->shape_gen == s->inst_gen) return;
-    int nr = 0;
-    ordered_tree_shape(s->h, &nr, &s->fdepth);
-    s->shape_gen = s->inst_gen;
-}
-
-// Begin a frame on the current slot: `st` waits for the slot's previous frame (all slots'
-// last frames for side entries that do not rotate slots), then the slot's instances are
-// brought up to date.  end_frame records the slot's completion.
-int begin_frame(rt_scene* s, hipStream_t st, bool all_slots) {
-    for (int i = 0; i < rt_scene::MAX_SLOTS; i++)
-        if (s->slot_pending[i] && (all_slots || i == s->cur_slot)) HIPCHK(hipStreamWaitEvent(st, s->slot_done[i], 0));
-    refresh_shape(s);
-    return sync_slot_insts(s, st);
-}
-int end_frame(rt_scene* s, hipStream_t st) {
-    HIPCHK(hipEventRecord(s->slot_done[s->cur_slot], st));
-    s->slot_pending[s->cur_slot] = true;
-    return RT_OK;
-}
-
-// Buffers of the frame slots other than the current one (sizes as in upload), slot events.
-int ensure_other_slot(rt_scene* s) {
-    const size_t nl = std::max(1, s->n_leaf);
-    for (int i = 0; i < s->n_slots; i++) {
-        rt_scene::Slot& o = s->store[i];
-        if (i == s->cur_slot || o.d_work) continue;
-        HIPCHK(hipMalloc((void**)&o.d_node_pair, 3 * nl * sizeof(float4)));
-        HIPCHK(hipMalloc((void**)&o.d_fnode, 4 * (size_t)std::max(1, s->n_real - 1) * sizeof(float4)));
-        HIPCHK(hipMalloc((void**)&o.d_leaf, nl * sizeof(int)));
-        HIPCHK(hipMalloc((void**)&o.d_tree, 2 * nl * sizeof(Box)));
-        HIPCHK(hipMalloc((void**)&o.d_work, WORK_INTS * sizeof(int)));
-        HIPCHK(hipMalloc((void**)&o.d_insts, std::max<size_t>(1, s->h.d_insts.size()) * sizeof(DInst)));
-        HIPCHK(hipMalloc((void**)&o.d_inst4, std::max<size_t>(1, s->h.d_insts.size()) * sizeof(float4)));
-        // the grid-wide build's sort buffers now, not at the slot's first frame inside a pipeline
-        if (s->n_leaf > BVH_WG_LEAVES && !o.d_bscratch) HIPCHK(hipMalloc(&o.d_bscratch, bvh_large_scratch_bytes(s->n_leaf)));
-        // the current poses now (blocking copies, here rather than at the slot's first frame: an
-        // asynchronous copy on a frame's stream may start a new SDMA engine, ~7 ms of host time
-        // the first time, profiles/r06/rblog/); later pose changes reach the slot through
-        // sync_slot_insts, stream-ordered
-        const size_t n = s->h.d_insts.size();
-        if (n) {
-            std::vector<float4> v4(n);
-            fill_inst4(s->h, v4.data());
-            HIPCHK(hipMemcpy(o.d_insts, s->h.d_insts.data(), n * sizeof(DInst), hipMemcpyHostToDevice));
-            HIPCHK(hipMemcpy(o.d_inst4, v4.data(), n * sizeof(float4), hipMemcpyHostToDevice));
-        }
-        o.slot_inst_gen = s->inst_gen;
-        o.work_zeroed = false; o.bvh_valid = false;
-    }
-    return mirror_slot_caps(s);                              // the current slot's grown buffers too
-}
-
-// The current slot grew a per-frame buffer (sky flags, live lists, history, pinned instance
-// staging) at its first frame of a new layout: give every other allocated slot the same
-// capacity now, so that their first frames -- possibly inside a steady pipeline -- allocate
-// nothing (an allocation there cost the first 8 frames of a run up to ~1 ms: hipFree waits for
-// the device, pinned allocations take milliseconds).  The slots' contents are reset on first
-// use as before (history key, instance generation).  Only growth reaches here: waiting for the
-// device before freeing a smaller buffer is a one-time cost per layout.
-int mirror_slot_caps(rt_scene* s) {
-    bool synced = false;
-    auto sync_once = [&]() -> hipError_t { if (synced) return hipSuccess; synced = true; return hipDeviceSynchronize(); };
-    for (int i = 0; i < s->n_slots; i++) {
-        if (i == s->cur_slot) continue;
-        rt_scene::Slot& o = s->store[i];
-        if (!o.d_work) continue;                              // not allocated (ensure_other_slot)
-        if (s->d_gsky && o.gsky_cap < s->gsky_cap) {
-            if (o.d_gsky) { HIPCHK(sync_once()); dfree(o.d_gsky); }
-            HIPCHK(hipMalloc((void**)&o.d_gsky, s->gsky_cap));
-            o.gsky_cap = s->gsky_cap;
-        }
-        if (s->d_live && o.live_cap < s->live_cap) {
-            if (o.d_live) { HIPCHK(sync_once()); dfree(o.d_live); }
-            HIPCHK(hipMalloc((void**)&o.d_live, (size_t)s->live_cap * sizeof(int)));
-            o.live_cap = s->live_cap;
-        }
-        if (s->d_hctl && o.hist_cap < s->hist_cap) {
-            if (o.d_hctl) {
-                HIPCHK(sync_once());
-                for (int q = 0; q < 2; q++) { dfree(o.d_hlist[q]); dfree(o.d_hflag[q]); }
-                dfree(o.d_hctl);
-            }
-            for (int q = 0; q < 2; q++) {
-                HIPCHK(hipMalloc((void**)&o.d_hlist[q], (size_t)s->hist_cap * sizeof(int)));
-                HIPCHK(hipMalloc((void**)&o.d_hflag[q], s->hist_cap));
-            }
-            HIPCHK(hipMalloc((void**)&o.d_hctl, 4 * sizeof(unsigned long long)));
-            o.hist_cap = s->hist_cap;
-            o.hist_key[0] = -1;                               // reset at the slot's first use
-        }
-        const size_t n = s->h.d_insts.size();
-        if (s->h_insts_pin && !o.h_insts_pin && n) {
-            HIPCHK(hipHostMalloc((void**)&o.h_insts_pin, n * sizeof(DInst), hipHostMallocDefault));
-            HIPCHK(hipHostMalloc((void**)&o.h_inst4_pin, n * sizeof(float4), hipHostMallocDefault));
-        }
-    }
-    return RT_OK;
-}
-
-// Atlas -> float4 texels (byte / 255, as assets.cc:61-81) in HBM; the reference's CUDA
-// texture (gputils TextureBuffer4D, alloc.h:24-80: point sampling, clamp) is sampled
-// explicitly by hit_kd, since gfx950 has no texture units.
-void free_atlas(rt_scene* s) {
-    if (s->d_atlas) (void)hipFree(s->d_atlas);
-    s->d_atlas = nullptr;
-}
-int ensure_atlas(rt_scene* s) {
-    const rt::Scene& h = s->h;
-    if (h.atlas_rgba.empty()) return fail(RT_ERR_STATE, "textured rendering needs an atlas: rt_scene_load_atlas / rt_scene_set_atlas");
-    if (!s->atlas_dirty && s->d_atlas) return RT_OK;
-    free_atlas(s);
-    const size_t n = (size_t)h.atlas_w * h.atlas_h;
-    std::vector<float4> texels(n);
-    for (size_t i = 0; i < n; i++)
-        texels[i] = make_float4((float)h.atlas_rgba[4 * i] / 255, (float)h.atlas_rgba[4 * i + 1] / 255,
-                                (float)h.atlas_rgba[4 * i + 2] / 255, (float)h.atlas_rgba[4 * i + 3] / 255);
-    HIPCHK(hipMalloc((void**)&s->d_atlas, n * sizeof(float4)));
-    HIPCHK(hipMemcpy(s->d_atlas, texels.data(), n * sizeof(float4), hipMemcpyHostToDevice));
-    s->atlas_dirty = false;
-    return RT_OK;
-}
-
-// A factor coprime with the queue length, so t -> t * f mod len is a permutation
-// (checked with gcd; f near len * 0.618 spreads consecutive tickets across the image).
-int ticket_scramble(int len) {
-    if (len <= 2) return 1;
-    int f = (int)(len * 0.6180339887) | 1;
-    while (std::gcd(f % len, len) != 1) f++;
-    return f % len;
-}
-
-// (Re)allocate / reset the scheduling history when the launch layout changes.
-int ensure_history(rt_scene* s, int n_groups, const long long* key, hipStream_t st) {
-    if (n_groups > s->hist_cap) {
-        for (int p = 0; p < 2; p++) { dfree(s->d_hlist[p]); dfree(s->d_hflag[p]); }
-        dfree(s->d_hctl);
-        const int cap = (std::max(n_groups, 1024) + 3) & ~3;   // whole dwords (flag() reads scalar dwords)
-        for (int p = 0; p < 2; p++) {
-            HIPCHK(hipMalloc((void**)&s->d_hlist[p], cap * sizeof(int)));
-            HIPCHK(hipMalloc((void**)&s->d_hflag[p], cap));
-        }
-        HIPCHK(hipMalloc((void**)&s->d_hctl, 4 * sizeof(unsigned long long)));
-        s->hist_cap = cap;
-        s->hist_key[0] = -1;
-    }
-    if (memcmp(key, s->hist_key, sizeof s->hist_key) != 0) {
-        for (int p = 0; p < 2; p++) HIPCHK(hipMemsetAsync(s->d_hflag[p], 0, s->hist_cap, st));
-        HIPCHK(hipMemsetAsync(s->d_hctl, 0, 4 * sizeof(unsigned long long), st));
-        memcpy(s->hist_key, key, sizeof s->hist_key);
-        s->hist_parity = 0;
-    }
-    return RT_OK;
-}
-
-// Per-frame buffers (sky flags, live lists, scheduling history) sized for a layout of n_groups
-// pixel groups in the current slot and every allocated one, ahead of the first frame that needs
-// them (warm_scene: the whole frame at 2-8 pixels per wave, the layouts of spp 8-32).  Contents
-// are reset at first use as before (the history key); only capacity is reserved here.
-int reserve_layout(rt_scene* s, int n_groups) {
-    const int cap = (std::max(n_groups, 1024) + 3) & ~3;
-    bool grew = false;
-    if (cap > s->gsky_cap) {
-        dfree(s->d_gsky);
-        HIPCHK(hipMalloc((void**)&s->d_gsky, cap));
-        s->gsky_cap = cap; grew = true;
-    }
-    const int sblocks = (n_groups + 63) / 64;
-    const int need = (sblocks + NQ - 1) / NQ * 64 * NQ + n_groups;
-    if (need > s->live_cap) {
-        dfree(s->d_live);
-        HIPCHK(hipMalloc((void**)&s->d_live, (size_t)need * sizeof(int)));
-        s->live_cap = need; grew = true;
-    }
-    if (cap > s->hist_cap) {
-        for (int p = 0; p < 2; p++) { dfree(s->d_hlist[p]); dfree(s->d_hflag[p]); }
-        dfree(s->d_hctl);
-        for (int p = 0; p < 2; p++) {
-            HIPCHK(hipMalloc((void**)&s->d_hlist[p], cap * sizeof(int)));
-            HIPCHK(hipMalloc((void**)&s->d_hflag[p], cap));
-        }
-        HIPCHK(hipMalloc((void**)&s->d_hctl, 4 * sizeof(unsigned long long)));
-        s->hist_cap = cap;
-        s->hist_key[0] = -1;
-        grew = true;
-    }
-    return (grew && s->n_slots > 1) ? mirror_slot_caps(s) : RT_OK;
-}
-
-int ensure_spp(rt_scene* s, int spp) {
-    if (spp <= s->spp_cap) return RT_OK;
-    int cap = std::max(spp, 64);
-    std::vector<float2> tab(cap);
-    for (int k = 0; k < cap; k++) rt::spp_offset(k, &tab[k].x, &tab[k].y);
-    dfree(s->d_spp);
-    HIPCHK(hipMalloc((void**)&s->d_spp, cap * sizeof(float2)));
-    HIPCHK(hipMemcpy(s->d_spp, tab.data(), cap * sizeof(float2), hipMemcpyHostToDevice));
-    s->spp_cap = cap;
-    return RT_OK;
-}
-
-int build_bvh(rt_scene* s, hipStream_t st, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr) {
-    if (s->n_leaf == 0) {
-        if (e0) { HIPCHK(hipEventRecord(e0, st)); HIPCHK(hipEventRecord(e1, st)); }
-        s->bvh_valid = true;
-        return RT_OK;
-    }
-    BvhArgs A;
-    A.insts = s->d_insts; A.n_inst = (int)s->h.d_insts.size();
-    A.mesh_box = s->d_mesh_box; A.n = s->n_leaf;
-    A.tree = s->d_tree;
-    A.node_pair = reinterpret_cast<float*>(s->d_node_pair); A.leaf_inst = s->d_leaf;
-    A.fnode = s->d_fnode; A.n_real = s->n_real;
-    A.work = s->d_work; A.n_work = WORK_INTS;
-    // the slot the next fast frame records its heavy list into (launch_trace skips its memset)
-    A.hctl = s->d_hctl ? s->d_hctl + 2 * (1 - s->hist_parity) : nullptr;
-    s->hctl_zeroed = s->d_hctl ? 1 - s->hist_parity : -1;
-    if (A.n > BVH_WG_LEAVES) {                                // above one workgroup's LDS: the grid-wide build
-        if (!s->d_bscratch) HIPCHK(hipMalloc(&s->d_bscratch, bvh_large_scratch_bytes(A.n)));
-        HIPCHK(bvh_build_large(A, s->d_bscratch, st, e0, e1));
-        s->bvh_valid = true;
-        s->work_zeroed = true;
-        return RT_OK;
-    }
-    const bool lds_tree = bvh_lds_bytes(A.n, true) <= 160 * 1024;       // n <= 2048
-    const size_t lds = bvh_lds_bytes(A.n, lds_tree);
-    if (lds > 160 * 1024) return fail(RT_ERR_LIMIT, "BVH build needs more LDS than one CU has");
-    const void* fn = lds_tree ? (const void*)bvh_build_kernel<true> : (const void*)bvh_build_kernel<false>;
-    if (lds > 64 * 1024) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    void* args[] = {&A};
-    // e0/e1 (timing=1): timestamps taken by the dispatch itself, no marker packets
-    HIPCHK(hipExtLaunchKernel(fn, dim3(1), dim3(1024), args, lds, st, e0, e1, 0));
-    HIPCHK(hipGetLastError());
-    s->bvh_valid = true;
-    s->work_zeroed = true;
-    return RT_OK;
-}
-
-SceneView view_of(const rt_scene* s, bool use_bvh) {
-    SceneView v;
-    v.tris = s->d_tris; v.meshes = s->d_meshes; v.insts = s->d_insts; v.mats = s->d_mats; v.lights = s->d_lights;
-    v.node_pair = s->d_node_pair; v.leaf_inst = s->d_leaf;
-    v.fnode = s->d_fnode; v.n_real = s->n_real;
-    v.ftree = (s->n_real >= 2 && s->fdepth <= FT_MAX_DEPTH) ? 1 : 0; v.inst4 = s->d_inst4;
-    v.n_leaf = s->n_leaf; v.n_inst = (int)s->h.d_insts.size();
-    v.n_lights = (int)s->h.d_lights.size(); v.use_bvh = use_bvh ? 1 : 0;
-    v.n_mats = (int)s->h.d_mats.size(); v.n_tris = (int)s->h.d_tris.size(); v.n_meshes = (int)s->h.d_meshes.size();
-    v.ident_all = 1;
-    for (const auto& i : s->h.d_insts) v.ident_all &= i.pose.identity ? 1 : 0;
-    for (const auto& m : s->h.d_meshes) v.ident_all &= m.pose.identity ? 1 : 0;
-    // Distance pruning (closest_hit): boxes provably contain their triangles only for
-    // pure translations with zero mesh offsets (the BVH boxes ignore the mesh pose,
-    // raytracer.cu:54-89).  Slack: 1e-4 x mesh size + 2^-14 x scene radius.
-    bool prune_ok = v.ident_all != 0;
-    float vmax = 0.0f, pmax = 0.0f;
-    for (const auto& m : s->h.d_meshes) prune_ok = prune_ok && m.pose.p.x == 0 && m.pose.p.y == 0 && m.pose.p.z == 0;
-    auto amax = [](rtm::V3 a) { return std::max(std::fabs(a.x), std::max(std::fabs(a.y), std::fabs(a.z))); };
-    for (const auto& t : s->h.d_tris) vmax = std::max(vmax, std::max(amax(t.a), std::max(amax(t.b), amax(t.c))));
-    for (const auto& i : s->h.d_insts) pmax = std::max(pmax, amax(i.pose.p));
-    const float radius = pmax + vmax + amax(s->h.d_cam.pos) + 1.0f;
-    prune_ok = prune_ok && std::isfinite(radius);
-    v.prune_abs = prune_ok ? 4e-4f * vmax + 0x1p-14f * radius : -1.0f;
-    v.tri_ax = (v.ident_all && !s->h.d_tris.empty()) ? s->d_tri_ax : nullptr;
-    return v;
-}
-
-bool opaque_scene(const rt_scene* s) {
-    for (const DMat& m : s->h.d_mats) if (m.refractive) return false;
-    return true;
-}
-
-int launch_trace(rt_scene* s, const rt_render_opts& o, hipStream_t st, uint32_t* rgba, int* dbg, int dbg_x, int dbg_y,
-                 bool want_stats, int occl_force = -1, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr,
-                 bool prof = false, unsigned* gdur = nullptr, int* geo = nullptr) {
-    TraceParams P{};
-    P.gdur = gdur;
-    const rt::Scene& h = s->h;
-    P.cam = h.d_cam; P.dist_atten = h.dist_atten; P.ambience = h.ambience;
-    P.W = h.cam.W; P.H = h.cam.H; P.row0 = o.row0; P.row_step = o.row_step;
-    P.n_rows = (P.H - o.row0 + o.row_step - 1) / o.row_step;
-    if (P.n_rows <= 0) {
-        if (e0) { HIPCHK(hipEventRecord(e0, st)); HIPCHK(hipEventRecord(e1, st)); }
-        return RT_OK;
-    }
-    P.compact = o.compact; P.spp = o.spp; P.depth = h.depth;
-    P.spp_recip = (o.spp & (o.spp - 1)) == 0 ? 1.0f / (float)o.spp : 0.0f;
-    P.spp_off = s->d_spp;
-    P.rgba = rgba; P.radiance = reinterpret_cast<float4*>(o.radiance); P.hit_inst = o.hit_inst; P.hit_tri = o.hit_tri;
-    P.stats = (want_stats || prof) ? s->d_stats : nullptr; P.dbg_log = dbg; P.dbg_x = dbg_x; P.dbg_y = dbg_y;
-    if (o.textures) {
-        int r;
-        if ((r = ensure_atlas(s)) != RT_OK) return r;
-        P.atlas = s->d_atlas; P.atlas_w = s->h.atlas_w; P.atlas_h = s->h.atlas_h;
-    }
-    SceneView S = view_of(s, o.use_bvh != 0);
-    // sample-parallel mapping: L lanes per pixel (one sample each per round), 64/L pixels per wave
-    P.lanes_per_px = std::min(o.spp, 64);
-    P.px_per_wave = 64 / P.lanes_per_px;
-    int gw = 1;
-    if ((P.px_per_wave & (P.px_per_wave - 1)) == 0) { while (gw * gw < P.px_per_wave) gw <<= 1; }
-    else gw = P.px_per_wave;
-    // Row slices with rows >= 8 frame rows apart (N >= 8 ranks): a 2-row group would pair
-    // rows that far apart, so groups are one row (8 x 1 at 8 spp).  Measured with four frames
-    // in flight: 8-way slice 0.234 -> 0.229 ms; whole frames and 2-way slices keep 4 x 2
-    // (8 x 1 there: +3.4% / +2%; profiles/r01/ab_group_shape_v31.log).
-    if (o.row_step >= 8) gw = P.px_per_wave;
-    P.gw = gw; P.gh = P.px_per_wave / gw;
-    auto log2_exact = [](int v) { int k = 0; while ((1 << k) < v) k++; return (1 << k) == v ? k : -1; };
-    P.l_shift = log2_exact(P.lanes_per_px); P.gw_shift = log2_exact(P.gw);
-    P.n_gx = (P.W + P.gw - 1) / P.gw;
-    P.n_groups = P.n_gx * ((P.n_rows + P.gh - 1) / P.gh);
-    if (geo) { geo[0] = P.n_groups; geo[1] = P.gw; geo[2] = P.gh; geo[3] = P.n_gx; }
-    P.scramble = ticket_scramble((P.n_groups + NQ - 1) / NQ);
-    P.scramble_small = (unsigned long long)((P.n_groups + NQ - 1) / NQ + TPC) * (unsigned long long)P.scramble < (1ull << 32);
-    P.div_ngx = udiv_make((unsigned)P.n_gx);
-    P.div_perq = udiv_make((unsigned)((P.n_groups + NQ - 1) / NQ));
-    P.work = s->d_work; P.tpc = TPC;
-    {   // unlit skip (trace_sample, ST_LIGHT): every incoming light must be >= +0 and finite
-        bool ok = !want_stats && !dbg;                        // (the PROF variant profiles the fast frame: on)
-        auto pos0 = [](float v) { return std::isfinite(v) && !std::signbit(v); };
-        for (const DLight& l : h.d_lights) ok = ok && pos0(l.col.x) && pos0(l.col.y) && pos0(l.col.z) && pos0(l.col.w);
-        for (const DMat& m : h.d_mats)
-            ok = ok && pos0(m.Kt.x) && pos0(m.Kt.y) && pos0(m.Kt.z) && pos0(m.Kt.w) && m.Kt.x <= 1.0f && m.Kt.y <= 1.0f &&
-                 m.Kt.z <= 1.0f && m.Kt.w <= 1.0f;
-        bool start_ok = true;                                  // no -0 channel in Ke + Ka * ambience (org_light)
-        for (const DMat& m : h.d_mats) {
-            const V4 o = m.Ke + m.Ka * h.ambience;
-            for (float v : {o.x, o.y, o.z, o.w}) start_ok = start_ok && !(v == 0.0f && std::signbit(v));
-        }
-        P.unlit_skip = ok ? (start_ok ? 2 : 1) : 0;
-    }
-    P.occl_exit = (opaque_scene(s) && (occl_force == 1 || (occl_force < 0 && !want_stats))) ? 1 : 0;
-    if (!s->work_zeroed) HIPCHK(hipMemsetAsync(s->d_work, 0, WORK_INTS * sizeof(int), st));
-    const bool tex = o.textures != 0;
-    const int mode0 = (o.spp > 64 ? M_MULTI : 0) | (want_stats ? M_STATS : 0);
+TraceVariant choose_trace_variant(const SceneView& S, int spp, bool tex, bool want_stats, bool prof, int ns) {
+    const int mode0 = (spp > 64 ? M_MULTI : 0) | (want_stats ? M_STATS : 0);
     // brute force (the reference's -r): no tree kernel (closest_hit's FT path assumes a tree)
     const bool brute = !S.use_bvh || S.n_leaf == 0;
     const bool ft = !brute && mode0 == 0 && S.ftree && lds_bytes(S, true) <= (size_t)LDS_LIMIT;
     const size_t lds = lds_bytes(S, ft);
     const bool use_lds = lds <= (size_t)LDS_LIMIT;
-    // suspended frames needed (<= MAX_FRAMES - 1); none without a refractive material, where a
-    // reflection child replaces its parent (trace_sample, F_REFLECT)
-    // (NS = 0 kernels assume that: a depth-0 scene with refraction takes the NS = 2 bucket)
-    const int ns = opaque_scene(s) ? 0 : std::max(h.depth, 1);
     const void* fn;
-    const int mode = (o.spp > 64 ? M_MULTI : 0) | (want_stats ? M_STATS : 0);
+    const int mode = (spp > 64 ? M_MULTI : 0) | (want_stats ? M_STATS : 0);
     constexpr int NG = MAX_FRAMES - 1;                     // generic frame-stack depth
     static const void* const generic[2][4] = {
         {(const void*)trace_kernel<NG, false, 0>, (const void*)trace_kernel<NG, false, 1>,
@@ -3234,1309 +2392,45 @@ int launch_trace(rt_scene* s, const rt_render_opts& o, hipStream_t st, uint32_t*
     if (shm > 64 * 1024) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
     int per_cu = 1;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, TRACE_BLOCK_P, shm) != hipSuccess || per_cu < 1) per_cu = 1;
-    const int waves_needed = P.n_groups;
-    // Frames in flight: a launch issued while the scene's previous frame is still running takes
-    // half the CUs.  A persistent block holds its CU (the LDS image) until its slowest wave
-    // ends; fewer blocks, each running twice the groups, leave fewer CUs held by one wave's last
-    // group, and two frames' blocks still cover the GPU.  Measured with four in flight
-    // (tools/pipe_slices.py, per-rank ms per frame at N = 1/2/4/8, same box): 0.655-0.665 /
-    // 0.374 / 0.226 / 0.156-0.157 with every CU, 0.646-0.654 / 0.347-0.354 / 0.200-0.205 /
-    // 0.137-0.140 with half; 3/8, 5/8 and 3/4 of the CUs in between (profiles/r03/ab_grid/).
-    // A frame issued alone (no other frame running) keeps every CU.  Requiring two or three
-    // running frames instead of one measured the same (profiles/r03/ab_grid/grid2.log).  A
-    // pipeline that copies every frame to the host measured 12% slower this way, with the copy
-    // anywhere (render stream, copy stream, high priority, fewer blit workgroups) and with the
-    // optional second half of the grid gated on later frames being queued
-    // (profiles/r03/ab_grid/readback.log): such callers set RT_OVERLAP_FULL.
-    int cap = s->n_cu * per_cu;
-    // another frame of the scene still in flight (any slot count, any overlap policy): the heavy
-    // list's static dealing below is for frames whose blocks all start at once
-    bool other_running = false;
-    for (int i = 1; i < s->n_slots && !other_running; i++) {
-        const int sl = (s->cur_slot + s->n_slots - i) % s->n_slots;
-        other_running = s->slot_pending[sl] && hipEventQuery(s->slot_done[sl]) == hipErrorNotReady;
-    }
-    if (s->n_slots >= 4 && s->overlap != RT_OVERLAP_FULL) {
-        const bool running = s->overlap == RT_OVERLAP_STREAM || other_running;   // or a stream
-        // Small frames (row slices of N >= 4 ranks: under ~48 groups per wave on half the CUs)
-        // take a quarter: four frames' blocks share the GPU, each block runs twice the groups,
-        // so its LDS staging and its slowest wave's tail weigh half as much.  Measured per-rank
-        // ms per frame, 60-frame streams, same box (profiles/r04/grid_div.log): N = 8 0.112 ->
-        // 0.101, N = 4 0.175 -> 0.171; whole frames unchanged by it (0.597 / 0.599), kept at half.
-        const long long half_waves = (long long)(cap / 2) * (TRACE_BLOCK_P / 64);
-        // (Not with virtual ranks, several slices of one frame per device from one scene: those
-        // slices share frame slots, and a quarter measured slower there: --gpus 1 --ranks 8 per
-        // slice 0.153 -> 0.173 ms, profiles/r04/grid_div.log.)
-        const int div = ((long long)P.n_groups < RT_SMALL_FRAME_GPW * half_waves && s->ranks_per_device == 1) ? 4 : 2;
-        if (running) cap = std::max(1, cap / div);
-    }
-    int blocks = std::min(cap, (waves_needed + TRACE_BLOCK_P / 64 - 1) / (TRACE_BLOCK_P / 64));
-    blocks = std::max(blocks, 1);
-    P.grid_waves = blocks * (TRACE_BLOCK_P / 64);              // the launch below: dim3(blocks)
-    // every block starts at once: a full grid and no other frame of the scene running (RT_OVERLAP_FULL
-    // and 2-3 frame slots keep the full grid for overlapping frames; those frames keep the counter)
-    P.heavy_static = (blocks == s->n_cu * per_cu && !other_running) ? 1 : 0;
-    P.heavy_cap = std::max(2 * blocks * (TRACE_BLOCK_P / 64), P.n_groups / 4);   // a bound, not a target
-    // longest-first history (fast frames): valid while the launch layout is unchanged
-    // Only where a wave runs few groups (1080p 8-way row slices: ~8 per wave): with more (63
-    // for a whole 1080p frame, 16 for a 4-way slice) the dynamic queues already balance the
-    // frame and the two clock reads per group cost as much as the shorter tail saves or more
-    // (measured, four frames in flight, ms per frame with / without: whole frame 0.919 / 0.914,
-    // 4-way 0.360 / 0.360, 8-way 0.179-0.186 / 0.200-0.204; profiles/r02/hist_policy.log).
-    P.hist = 0;
-    const long long waves = (long long)blocks * (TRACE_BLOCK_P / 64);
     // sky pre-pass: the fast (ordered-LBVH) kernels, one round of samples, a tree to test
     // (brute-force frames: the instances' grown boxes instead, when the pruning claim holds)
-    const bool sky_brute = brute_k && !prof && !want_stats && o.spp <= 64 && S.prune_abs >= 0.0f && S.n_inst >= 1 &&
+    const bool sky_brute = brute_k && !prof && !want_stats && spp <= 64 && S.prune_abs >= 0.0f && S.n_inst >= 1 &&
                            S.n_inst <= 64 && !getenv("RT_NO_BRUTE_SKY");
-    const bool sky = (ft && !prof && o.spp <= 64 && S.use_bvh && S.n_leaf > 0) || sky_brute;
-    // Heavy-first by work (hist = 2) where groups per wave are many: a group whose samples took
-    // >= heavy_q wave queries (mirror pixels: primary, shadow and reflection chains) is flagged,
-    // and the next frame of the slot runs the flagged groups first off a heavy live list the sky
-    // pre-pass builds.  No clock reads (the timed history's cost, item 17), one byte store per
-    // heavy group.  RT_HEAVY_Q (environment) sets heavy_q; 0 turns it off.
-    // The mode must not depend on the grid (half or whole, frames in flight or alone): the two
-    // modes' flags mean different things (hist = 1 flags only the groups on its heavy list and
-    // skips them in the normal queues; hist = 2 flags by work and lists nothing), so the history
-    // key includes the mode and a change of mode resets the flags.
-    static const int heavy_q = [] { const char* e = getenv("RT_HEAVY_Q"); return e ? atoi(e) : RT_HEAVY_Q_DEFAULT; }();
-    const long long full_waves = (long long)s->n_cu * per_cu * (TRACE_BLOCK_P / 64);
-    const bool hist2 = !want_stats && !dbg && sky && heavy_q > 0;
-    const bool hist1 = !hist2 && !want_stats && !dbg && (prof || (long long)P.n_groups <= RT_HIST_GROUPS_PER_WAVE * full_waves);
-    (void)waves;
-    if (hist1 || hist2) {
-        const long long key[8] = {P.W, P.H, P.row0, P.row_step, P.n_rows, P.spp, P.n_groups,
-                                  (long long)o.textures | (hist2 ? 2 : 1) << 8};
-        int r;
-        const int cap0 = s->hist_cap;
-        if ((r = ensure_history(s, P.n_groups, key, st)) != RT_OK) return r;
-        if (s->n_slots > 1 && s->hist_cap > cap0 && (r = mirror_slot_caps(s)) != RT_OK) return r;
-        const int prev = s->hist_parity, next = 1 - prev;
-        P.hist = hist1 ? 1 : 2;
-        P.heavy_q = heavy_q;
-        P.hl_prev = s->d_hlist[prev]; P.hl_next = s->d_hlist[next];
-        P.hf_prev = s->d_hflag[prev]; P.hf_next = s->d_hflag[next];
-        P.hctl_prev = s->d_hctl + 2 * prev; P.hctl_next = s->d_hctl + 2 * next;
-        if (hist1 && s->hctl_zeroed != next) HIPCHK(hipMemsetAsync(s->d_hctl + 2 * next, 0, 2 * sizeof(unsigned long long), st));
-        s->hist_parity = next;
-    }
-    s->work_zeroed = false;                                   // this launch consumes the counters
-    s->hctl_zeroed = -1;
-    if (sky) {
-        bool grew = false;
-        if (P.n_groups > s->gsky_cap) {
-            grew = true;
-            dfree(s->d_gsky);
-            const int cap = (std::max(P.n_groups, 1024) + 3) & ~3;   // whole dwords (scalar loads)
-            HIPCHK(hipMalloc((void**)&s->d_gsky, cap));
-            s->gsky_cap = cap;
-        }
-        const int sblocks = (P.n_groups + 63) / 64;
-        const int lcap = (sblocks + NQ - 1) / NQ * 64;          // most groups of the blocks b = q mod NQ
-        const int need = lcap * NQ + P.n_groups;                // + the heavy live list (hist = 2)
-        if (need > s->live_cap) {
-            grew = true;
-            dfree(s->d_live);
-            HIPCHK(hipMalloc((void**)&s->d_live, (size_t)need * sizeof(int)));
-            s->live_cap = need;
-        }
-        P.gsky = s->d_gsky;
-        P.live = s->d_live; P.live_cap = lcap;
-        if (s->n_slots > 1 && grew) { int r; if ((r = mirror_slot_caps(s)) != RT_OK) return r; }
-        P.tpc = (part_k && P.lanes_per_px == 64) ? RT_TPC_WIDE : RT_TPC_LIVE;
-        const Box* mbox = s->d_mesh_box;
-        float sky_A = S.prune_abs, sky_B = 0x1p-12f;          // brute-force frames: the grown boxes' slack
-        void* sargs[] = {&P, &S, &s->d_gsky, &s->d_live, &mbox, &sky_A, &sky_B};
-        HIPCHK(hipExtLaunchKernel(sky_brute ? (const void*)sky_kernel<true> : (const void*)sky_kernel<false>, dim3(sblocks), dim3(SKY_THREADS), sargs, 0, st, e0, nullptr, 0));
-    }
+    const bool sky = (ft && !prof && spp <= 64 && S.use_bvh && S.n_leaf > 0) || sky_brute;
+    return TraceVariant{fn, shm, per_cu, part_k, sky, sky_brute};
+}
+
+hipError_t launch_sky(bool brute, int blocks, TraceParams& P, SceneView& S, unsigned char* gsky, int* live,
+                      const Box* mesh_box, float slack_a, float slack_b, hipStream_t st, hipEvent_t e0) {
+    void* sargs[] = {&P, &S, &gsky, &live, &mesh_box, &slack_a, &slack_b};
+    return hipExtLaunchKernel(brute ? (const void*)sky_kernel<true> : (const void*)sky_kernel<false>, dim3(blocks), dim3(SKY_THREADS), sargs, 0, st, e0, nullptr, 0);
+}
+
+hipError_t launch_trace_kernel(const TraceVariant& v, int blocks, TraceParams& P, SceneView& S, hipStream_t st,
+                               hipEvent_t e0, hipEvent_t e1) {
     void* args[] = {&P, &S};
-    HIPCHK(hipExtLaunchKernel(fn, dim3(blocks), dim3(TRACE_BLOCK_P), args, shm, st, sky ? nullptr : e0, e1, 0));
-    HIPCHK(hipGetLastError());
-    return RT_OK;
+    return hipExtLaunchKernel(v.fn, dim3(blocks), dim3(TRACE_BLOCK_P), args, v.shm, st, e0, e1, 0);
 }
 
-#define CHECK_SCENE(s) do { if (!(s)) return fail(RT_ERR_ARG, "null scene"); } while (0)
-#define CHECK_BUILDING(s) do { CHECK_SCENE(s); if ((s)->finished) return fail(RT_ERR_STATE, "scene already finished"); } while (0)
-#define CHECK_FINISHED(s) do { CHECK_SCENE(s); if (!(s)->finished) return fail(RT_ERR_STATE, "scene not finished (call rt_builder_finish)"); } while (0)
-
-rt::Material mat_from(const float* m) {
-    rt::Material r;
-    r.Ke = v4(m[0], m[1], m[2], m[3]); r.Ka = v4(m[4], m[5], m[6], m[7]); r.Kd = v4(m[8], m[9], m[10], m[11]);
-    r.Ks = v4(m[12], m[13], m[14], m[15]); r.Kt = v4(m[16], m[17], m[18], m[19]); r.Kr = v4(m[20], m[21], m[22], m[23]);
-    r.alpha = m[24]; r.eta = m[25];
-    return r;
+hipError_t launch_bvh_build(BvhArgs& A, bool lds_tree, size_t lds, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
+    const void* fn = lds_tree ? (const void*)bvh_build_kernel<true> : (const void*)bvh_build_kernel<false>;
+    if (lds > 64 * 1024) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    void* args[] = {&A};
+    return hipExtLaunchKernel(fn, dim3(1), dim3(1024), args, lds, st, e0, e1, 0);
 }
 
-void invalidate(rt_scene* s) {
-    s->bvh_valid = false;
-    for (auto& o : s->store) o.bvh_valid = false;
-}
-
-}  // namespace
-
-void free_multi(rt_scene* s);
-rt_scene::~rt_scene() {
-    free_multi(this);
-    if (uploaded) (void)hipSetDevice(device);
-    free_atlas(this);
-    dfree(d_fnode);
-    if (d_bscratch) (void)hipFree(d_bscratch);
-    for (int p = 0; p < 2; p++) { dfree(d_hlist[p]); dfree(d_hflag[p]); }
-    dfree(d_hctl);
-    dfree(d_gsky); dfree(d_live);
-    dfree(d_tris); dfree(d_meshes); dfree(d_insts); dfree(d_mats); dfree(d_lights); dfree(d_tri_ax);
-    dfree(d_node_pair); dfree(d_leaf); dfree(d_inst4); dfree(d_work);
-    dfree(d_mesh_box); dfree(d_tree); dfree(d_spp); dfree(d_stats); dfree(d_canvas); dfree(d_dbg);
-    for (auto& p : d_out) dfree(p);
-    for (auto& e : ev) if (e) (void)hipEventDestroy(e);
-    for (auto& e : tev) (void)hipEventDestroy(e);
-    auto hfree = [](auto*& p) { if (p) { (void)hipHostFree(p); p = nullptr; } };
-    hfree(h_insts_pin); hfree(h_inst4_pin);
-    for (int i = 0; i < MAX_SLOTS; i++) {                      // store[cur_slot] is the (freed) current state
-        if (i == cur_slot) continue;
-        Slot& o = store[i];
-        dfree(o.d_tree); dfree(o.d_node_pair); dfree(o.d_leaf); dfree(o.d_fnode); dfree(o.d_work);
-        if (o.d_bscratch) (void)hipFree(o.d_bscratch);
-        for (int p = 0; p < 2; p++) { dfree(o.d_hlist[p]); dfree(o.d_hflag[p]); }
-        dfree(o.d_hctl); dfree(o.d_gsky); dfree(o.d_live);
-        dfree(o.d_insts); dfree(o.d_inst4);
-        hfree(o.h_insts_pin); hfree(o.h_inst4_pin);
-    }
-    for (auto& e : slot_done) if (e) (void)hipEventDestroy(e);
-    if (stream) (void)hipStreamDestroy(stream);
-}
-
-// ---------------------------------------------------------------------------
-// Multi-GPU frames from one host process (rt_scene_set_devices).  The frame is
-// split row-cyclically into n_ranks slices (slice r = rows r, r + N, ...), the BVH and scene
-// replicated on every device (each replica rebuilds the same tree from the same instance
-// array, raytracer.cu:103-119), so the one exchange is the gather of the RGBA8 slices:
-//   1. device i renders ranks [i k, (i+1) k) (k = n_ranks / n_devices) into its slice buffer
-//      sbuf[i] = k slices of rows_max x W (compact rows; rows_max = ceil(H / N)), on its stream;
-//   2. ncclGroupStart; per device ncclGather(sbuf[i], gbuf on device 0, k rows_max W uint32,
-//      root 0, comm[i], stream[i]); ncclGroupEnd -- one communicator per device from
-//      ncclCommInitAll, so rank order = device order = slice order;
-//   3. device 0 un-permutes gbuf into the frame (unpermute_kernel).
-// Several ranks per device ("virtual" ranks: n_ranks > n_devices) keep the same sequence, so a
-// one-GPU box runs the whole call sequence with a one-rank communicator.  RCCL is opened
-// with dlopen at the first multi-device frame (the copy torch loaded, if any): the library
-// has no link-time RCCL dependency.
-// ---------------------------------------------------------------------------
-namespace {
-__global__ __launch_bounds__(256) void unpermute_kernel(const uint32_t* __restrict__ g, uint32_t* __restrict__ out, int W,
-                                                        int H, int N, int rows_max) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (long long)W * H) return;
-    const int y = (int)(i / W), x = (int)(i - (long long)y * W);
-    out[i] = g[((size_t)(y % N) * rows_max + y / N) * W + x];         // frame row y = slice y % N, row y / N
-}
-
-struct Rccl {
-    void* lib = nullptr;
-    ncclResult_t (*comm_init_all)(ncclComm_t*, int, const int*) = nullptr;
-    ncclResult_t (*comm_destroy)(ncclComm_t) = nullptr;
-    ncclResult_t (*gather)(const void*, void*, size_t, ncclDataType_t, int, ncclComm_t, hipStream_t) = nullptr;
-    ncclResult_t (*group_start)() = nullptr;
-    ncclResult_t (*group_end)() = nullptr;
-    const char* (*err)(ncclResult_t) = nullptr;
-};
-Rccl* rccl(std::string* why) {
-    static Rccl R;
-    static std::string reason;
-    static bool tried = false;
-    static std::mutex mu;
-    std::lock_guard<std::mutex> lk(mu);
-    if (!tried) {
-        tried = true;
-        for (const char* n : {"librccl.so", "librccl.so.1"})                 // the copy already loaded (torch's)
-            if (!R.lib) R.lib = dlopen(n, RTLD_NOW | RTLD_NOLOAD);
-        for (const char* n : {"librccl.so.1", "/opt/rocm/lib/librccl.so.1"})
-            if (!R.lib) R.lib = dlopen(n, RTLD_NOW | RTLD_GLOBAL);
-        if (!R.lib) { reason = std::string("cannot load RCCL: ") + dlerror(); }
-        else {
-            auto sym = [&](const char* n) { void* f = dlsym(R.lib, n); if (!f && reason.empty()) reason = std::string("RCCL lacks ") + n; return f; };
-            R.comm_init_all = (decltype(R.comm_init_all))sym("ncclCommInitAll");
-            R.comm_destroy = (decltype(R.comm_destroy))sym("ncclCommDestroy");
-            R.gather = (decltype(R.gather))sym("ncclGather");
-            R.group_start = (decltype(R.group_start))sym("ncclGroupStart");
-            R.group_end = (decltype(R.group_end))sym("ncclGroupEnd");
-            R.err = (decltype(R.err))sym("ncclGetErrorString");
-        }
-    }
-    if (!reason.empty()) { if (why) *why = reason; return nullptr; }
-    return &R;
-}
-}  // namespace
-
-struct MultiDev {
-    std::vector<int> devices;
-    int n_ranks = 1, per_dev = 1, rows_max = 0, W = 0, H = 0;
-    std::vector<rt_scene*> reps;                 // reps[0] = the scene itself; reps[i > 0] owned replicas
-    std::vector<unsigned> inst_gen;              // host instance generation each replica holds
-    std::vector<ncclComm_t> comms;               // one per device (ncclCommInitAll: rank = device order)
-    // Frames in flight: the scene's frame slots (rt_scene_set_frame_slots) give `depth`; frame f
-    // uses slot k = f % depth -- its own stream per device, slice buffers and gather buffer -- so
-    // frame f + 1 renders while frame f gathers and un-permutes.  A slot's stream orders frame f
-    // after frame f - depth, the last user of the slot's buffers.
-    int depth = 0;
-    long long frame = 0;
-    std::vector<std::vector<hipStream_t>> streams;   // [device][slot]
-    std::vector<std::vector<uint32_t*>> sbuf;        // [device][slot]: per_dev slices of rows_max x W
-    std::vector<uint32_t*> gbuf;                     // [slot], device 0: n_ranks slices
-    hipEvent_t ev_in = nullptr, ev_out = nullptr;    // device 0: caller's stream -> frame -> caller's stream
-    // per device: the last frame's gather; the next frame's gather (another slot's stream) waits
-    // for it, so operations on a communicator run in issue order whatever RCCL does across streams
-    std::vector<hipEvent_t> gdone;
-    bool gdone_pending = false;
-};
-
-namespace {
-// The per-slot streams and buffers (and their device work) released; the replicas and the
-// communicators stay.
-void free_multi_slots(MultiDev* m) {
-    for (size_t i = 0; i < m->streams.size(); i++) {
-        (void)hipSetDevice(m->devices[i]);
-        for (hipStream_t st : m->streams[i]) if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
-        if (i < m->sbuf.size()) for (uint32_t* b : m->sbuf[i]) if (b) (void)hipFree(b);
-    }
-    (void)hipSetDevice(m->devices[0]);
-    for (uint32_t* b : m->gbuf) if (b) (void)hipFree(b);
-    m->streams.clear(); m->sbuf.clear(); m->gbuf.clear();
-    m->depth = 0;
-}
-}  // namespace
-
-void free_multi(rt_scene* s) {
-    MultiDev* m = s->multi;
-    if (!m) return;
-    s->multi = nullptr;
-    s->ranks_per_device = 1;
-    free_multi_slots(m);
-    Rccl* R = rccl(nullptr);
-    for (size_t i = 0; i < m->comms.size(); i++) {
-        (void)hipSetDevice(m->devices[i]);
-        if (R && m->comms[i]) (void)R->comm_destroy(m->comms[i]);
-    }
-    for (size_t i = 0; i < m->gdone.size(); i++) {
-        (void)hipSetDevice(m->devices[i]);
-        if (m->gdone[i]) (void)hipEventDestroy(m->gdone[i]);
-    }
-    (void)hipSetDevice(m->devices[0]);
-    if (m->ev_in) (void)hipEventDestroy(m->ev_in);
-    if (m->ev_out) (void)hipEventDestroy(m->ev_out);
-    for (size_t i = 1; i < m->reps.size(); i++) delete m->reps[i];
-    if (s->uploaded) (void)hipSetDevice(s->device);
-    delete m;
-}
-
-namespace {
-// Replica i's host scene brought up to the primary's: camera, environment, instance poses,
-// atlas (the device copies follow at its next frame, as for any scene).
-void sync_replica(rt_scene* s, MultiDev* m, size_t i) {
-    rt_scene* r = m->reps[i];
-    r->h.cam = s->h.cam; r->h.d_cam = s->h.d_cam;
-    r->h.dist_atten = s->h.dist_atten; r->h.ambience = s->h.ambience; r->h.depth = s->h.depth;
-    r->overlap = s->overlap;
-    if (m->inst_gen[i] != s->inst_gen) {
-        r->h.insts = s->h.insts; r->h.d_insts = s->h.d_insts;
-        r->inst_gen++;
-        invalidate(r);
-        m->inst_gen[i] = s->inst_gen;
-    }
-    if (r->h.atlas_rgba.size() != s->h.atlas_rgba.size() || (s->atlas_dirty && !s->h.atlas_rgba.empty())) {
-        r->h.atlas_rgba = s->h.atlas_rgba; r->h.atlas_w = s->h.atlas_w; r->h.atlas_h = s->h.atlas_h;
-        r->atlas_dirty = true;
-    }
-}
-
-// Replicas and communicators on first use; per-slot streams and buffers whenever the frame
-// slots changed (the work in flight is waited for first).
-int setup_multi(rt_scene* s, MultiDev* m, Rccl* R) {
-    const int nd = (int)m->devices.size(), W = m->W;
-    int r;
-    for (int i = (int)m->reps.size(); i < nd; i++) {
-        HIPCHK(hipSetDevice(m->devices[i]));
-        rt_scene* rp = new rt_scene;
-        rp->h = s->h; rp->finished = true;
-        rp->h.atlas_rgba.clear();
-        rp->overlap = s->overlap;
-        rp->ranks_per_device = m->per_dev;
-        m->reps.push_back(rp);
-        m->inst_gen.push_back(0);
-        const int saved = g_device;
-        g_device = m->devices[i];
-        r = upload(rp);
-        g_device = saved;
-        if (r != RT_OK) return r;
-    }
-    if (m->gdone.empty()) {
-        m->gdone.assign(nd, nullptr);
-        for (int i = 0; i < nd; i++) {
-            HIPCHK(hipSetDevice(m->devices[i]));
-            HIPCHK(hipEventCreateWithFlags(&m->gdone[i], hipEventDisableTiming));
-        }
-    }
-    if (m->comms.empty()) {
-        m->comms.assign(nd, nullptr);
-        ncclResult_t e = R->comm_init_all(m->comms.data(), nd, m->devices.data());
-        if (e != ncclSuccess) { m->comms.clear(); return fail(RT_ERR_HIP, std::string("ncclCommInitAll: ") + R->err(e)); }
-    }
-    HIPCHK(hipSetDevice(m->devices[0]));
-    if (!m->ev_in) HIPCHK(hipEventCreateWithFlags(&m->ev_in, hipEventDisableTiming));
-    if (!m->ev_out) HIPCHK(hipEventCreateWithFlags(&m->ev_out, hipEventDisableTiming));
-    const int D = s->n_slots;
-    if (m->depth == D) return RT_OK;
-    free_multi_slots(m);
-    for (int i = 1; i < nd; i++) {                             // replicas rotate as many frame slots
-        m->reps[i]->overlap = s->overlap;
-        if ((r = rt_scene_set_frame_slots(m->reps[i], D)) != RT_OK) return r;
-    }
-    m->streams.assign(nd, std::vector<hipStream_t>(D, nullptr));
-    m->sbuf.assign(nd, std::vector<uint32_t*>(D, nullptr));
-    m->gbuf.assign(D, nullptr);
-    for (int i = 0; i < nd; i++) {
-        HIPCHK(hipSetDevice(m->devices[i]));
-        for (int k = 0; k < D; k++) {
-            HIPCHK(hipStreamCreateWithFlags(&m->streams[i][k], hipStreamNonBlocking));
-            HIPCHK(hipMalloc((void**)&m->sbuf[i][k], (size_t)m->per_dev * m->rows_max * W * 4));
-        }
-    }
-    HIPCHK(hipSetDevice(m->devices[0]));
-    for (int k = 0; k < D; k++) HIPCHK(hipMalloc((void**)&m->gbuf[k], (size_t)m->n_ranks * m->rows_max * W * 4));
-    m->depth = D;
-    m->frame = 0;
-    m->gdone_pending = false;
-    return RT_OK;
-}
-
-int render_multi(rt_scene* s, const rt_render_opts* o, rt_stats* stats) {
-    MultiDev* m = s->multi;
-    if (o->radiance || o->hit_inst || o->hit_tri) return fail(RT_ERR_ARG, "multi-device frames write RGBA8 only");
-    std::string why;
-    Rccl* R = rccl(&why);
-    if (!R) return fail(RT_ERR_STATE, why);
-    const int nd = (int)m->devices.size(), N = m->n_ranks, W = s->h.cam.W, H = s->h.cam.H;
-    int r;
-    if (m->W != W || m->H != H) return fail(RT_ERR_STATE, "canvas size changed after rt_scene_set_devices");
-    if ((r = setup_multi(s, m, R)) != RT_OK) return r;
-    for (int i = 1; i < nd; i++) sync_replica(s, m, i);
-    const int k = (int)(m->frame % m->depth);
-    hipStream_t caller = o->stream ? (hipStream_t)o->stream : nullptr;
-    if (caller) {                                          // the caller's work before this frame (its output buffer)
-        HIPCHK(hipSetDevice(m->devices[0]));
-        HIPCHK(hipEventRecord(m->ev_in, caller));
-    }
-    unsigned long long tot[4] = {0, 0, 0, 0};
-    double bvh_ms = 0, trace_ms = 0;
-    // 1. every rank's slice, on its device's stream of this slot.  Event timing (o->timing)
-    // covers the first device's ranks (the scene's own rt_timing_collect); replicas untimed.
-    for (int i = 0; i < nd; i++) {
-        double dev_bvh = 0, dev_trace = 0;
-        for (int j = 0; j < m->per_dev; j++) {
-            rt_render_opts so = *o;
-            so.row0 = i * m->per_dev + j; so.row_step = N; so.compact = 1;
-            so.rgba = m->sbuf[i][k] + (size_t)j * m->rows_max * W;
-            so.stream = m->streams[i][k]; so.host_outputs = 0; so.sync = 0;
-            if (i > 0) so.timing = 0;
-            rt_stats st{};
-            if ((r = rt_render(m->reps[i], &so, stats ? &st : nullptr)) != RT_OK) return r;
-            if (stats) {
-                tot[0] += st.rays; tot[1] += st.nodes; tot[2] += st.leaves; tot[3] += st.tri_tests;
-                dev_bvh += st.bvh_ms; dev_trace += st.trace_ms;
-            }
-        }
-        bvh_ms = std::max(bvh_ms, dev_bvh); trace_ms = std::max(trace_ms, dev_trace);
-    }
-    // 2. the gather to device 0 (one communicator per device, grouped)
-    const size_t cnt = (size_t)m->per_dev * m->rows_max * W;
-    if (m->gdone_pending)                                  // after the previous frame's gather (issue order)
-        for (int i = 0; i < nd; i++) {
-            HIPCHK(hipSetDevice(m->devices[i]));
-            HIPCHK(hipStreamWaitEvent(m->streams[i][k], m->gdone[i], 0));
-        }
-    ncclResult_t e = R->group_start();
-    for (int i = 0; i < nd && e == ncclSuccess; i++) {
-        HIPCHK(hipSetDevice(m->devices[i]));
-        e = R->gather(m->sbuf[i][k], i == 0 ? m->gbuf[k] : nullptr, cnt, ncclUint32, 0, m->comms[i], m->streams[i][k]);
-    }
-    ncclResult_t e2 = R->group_end();
-    if (e == ncclSuccess) e = e2;
-    if (e != ncclSuccess) return fail(RT_ERR_HIP, std::string("ncclGather: ") + R->err(e));
-    for (int i = 0; i < nd; i++) {
-        HIPCHK(hipSetDevice(m->devices[i]));
-        HIPCHK(hipEventRecord(m->gdone[i], m->streams[i][k]));
-    }
-    m->gdone_pending = true;
-    // 3. un-permute on device 0 into the caller's buffer (after the caller's earlier work on it)
-    // or the canvas
-    HIPCHK(hipSetDevice(m->devices[0]));
-    hipStream_t s0 = m->streams[0][k];
-    if (caller) HIPCHK(hipStreamWaitEvent(s0, m->ev_in, 0));
-    uint32_t* out = (o->rgba && !o->host_outputs) ? o->rgba : s->d_canvas;
+void launch_unpermute(const uint32_t* g, uint32_t* out, int W, int H, int N, int rows_max, hipStream_t st) {
     const long long px = (long long)W * H;
-    hipLaunchKernelGGL(unpermute_kernel, dim3((unsigned)((px + 255) / 256)), dim3(256), 0, s0, m->gbuf[k], out, W, H, N,
-                       m->rows_max);
-    HIPCHK(hipGetLastError());
-    if (caller) {                                          // the caller's stream continues after the frame
-        HIPCHK(hipEventRecord(m->ev_out, s0));
-        HIPCHK(hipStreamWaitEvent(caller, m->ev_out, 0));
-    }
-    m->frame++;
-    if (o->sync || o->host_outputs || stats)               // this frame only: the other slots keep running
-        for (int i = 0; i < nd; i++) { HIPCHK(hipSetDevice(m->devices[i])); HIPCHK(hipStreamSynchronize(m->streams[i][k])); }
-    HIPCHK(hipSetDevice(m->devices[0]));
-    if (o->host_outputs && o->rgba) HIPCHK(hipMemcpy(o->rgba, out, (size_t)px * 4, hipMemcpyDeviceToHost));
-    if (stats) {
-        // counters summed over ranks; bvh_ms / trace_ms: the slowest device's summed kernel times
-        // (its ranks run one after another on its stream), the frame's parallel kernel time
-        stats->rays = tot[0]; stats->nodes = tot[1]; stats->leaves = tot[2]; stats->tri_tests = tot[3];
-        stats->bvh_ms = bvh_ms; stats->trace_ms = trace_ms;
-    }
-    return RT_OK;
+    hipLaunchKernelGGL(unpermute_kernel, dim3((unsigned)((px + 255) / 256)), dim3(256), 0, st, g, out, W, H, N, rows_max);
 }
-}  // namespace
-
-extern "C" {
-
-int rt_abi_version(void) { return RT_ABI_VERSION; }
-const char* rt_last_error(void) { return g_err.c_str(); }
-
-int rt_device_count(int* count) {
-    if (!count) return fail(RT_ERR_ARG, "null count");
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) n = 0;
-    *count = n;
-    return RT_OK;
+void launch_profile_marker(int tag, hipStream_t st) {
+    hipLaunchKernelGGL(profile_marker_kernel, dim3(tag), dim3(64), 0, st, tag);
+}
+void launch_copy_gate(const unsigned* flag, unsigned long long max_ticks, hipStream_t st) {
+    hipLaunchKernelGGL(copy_gate_kernel, dim3(1), dim3(64), 0, st, flag, max_ticks);
+}
+void launch_kat(int op, int n, const float* a, const float* b, const float* c, float* of, int* oi, unsigned long long* ou) {
+    hipLaunchKernelGGL(kat_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, op, n, a, b, c, of, oi, ou);
 }
 
-int rt_set_device(int device) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return fail(RT_ERR_NODEV, "no HIP device available");
-    if (device < 0 || device >= n) return fail(RT_ERR_ARG, "device index out of range");
-    g_device = device;
-    HIPCHK(hipSetDevice(device));
-    return RT_OK;
-}
-
-// Profile marker (rt_profile_marker): an empty kernel whose grid (64 x tag threads) tells a
-// rocprofv3 trace where a caller's timed region begins and ends (tools/pmc_step.py).
-namespace {
-__global__ __launch_bounds__(64) void profile_marker_kernel(int tag) { (void)tag; }
-
-// rt_copy_engines_warm's gate: one wave that holds the copies queued behind it pending until the
-// host opens the gate (a flag in coherent host memory) or `max_ticks` of the wall clock pass, so
-// that every queued copy finds the engines of the copies before it busy.  Vector loads only.
-__global__ __launch_bounds__(64) void copy_gate_kernel(const unsigned* flag, unsigned long long max_ticks) {
-    const unsigned long long t0 = wall_clock64();
-    while (__hip_atomic_load(flag, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM) == 0u && wall_clock64() - t0 < max_ticks)
-        __builtin_amdgcn_s_sleep(32);
-}
-}  // namespace
-
-int rt_profile_marker(int tag, void* stream) {
-    if (tag < 1 || tag > 64) return fail(RT_ERR_ARG, "marker tag must be 1..64");
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return fail(RT_ERR_NODEV, "no HIP device available");
-    hipLaunchKernelGGL(profile_marker_kernel, dim3(tag), dim3(64), 0, (hipStream_t)stream, tag);
-    HIPCHK(hipGetLastError());
-    return RT_OK;
-}
-
-int rt_spp_offset(int k, float* dx, float* dy) {
-    if (k < 0 || !dx || !dy) return fail(RT_ERR_ARG, "bad arguments");
-    rt::spp_offset(k, dx, dy);
-    return RT_OK;
-}
-
-int rt_host_alloc(int64_t bytes, void** out) {
-    if (!out || bytes <= 0) return fail(RT_ERR_ARG, "bytes > 0 and an output pointer required");
-    *out = nullptr;
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return fail(RT_ERR_NODEV, "no HIP device available");
-    HIPCHK(hipHostMalloc(out, (size_t)bytes, hipHostMallocDefault));
-    return RT_OK;
-}
-int rt_host_free(void* p) {
-    if (p) HIPCHK(hipHostFree(p));
-    return RT_OK;
-}
-// A device -> pinned-host copy on a DMA copy engine.  hipMemcpyDeviceToDeviceNoCU asks the
-// runtime for the SDMA path explicitly (the copy still goes where the pointers live: with a
-// hipHostMalloc destination it writes host memory over PCIe).  Measured on this image
-// (tools/copy_probe.hip, profiles/r06/copy/): 8.29 MB in 0.157 ms (53 GB/s), finished 0.66 ms
-// into a grid that held every CU for 3 ms, and no dispatch in the kernel trace; the torch
-// pinned-tensor copy the round-5 bench used ran as 320-us `__amd_rocclr_copyBuffer` blit kernels
-// that competed with the persistent trace blocks for CUs.
-int rt_copy_to_host_async(void* host_dst, const void* dev_src, int64_t bytes, void* stream) {
-    if (!host_dst || !dev_src || bytes < 0) return fail(RT_ERR_ARG, "null pointer or negative size");
-    if (bytes == 0) return RT_OK;
-    HIPCHK(hipMemcpyAsync(host_dst, dev_src, (size_t)bytes, hipMemcpyDeviceToDeviceNoCU, (hipStream_t)stream));
-    return RT_OK;
-}
-
-// The runtime gives a stream's first copy (and a copy after the stream's last one has drained)
-// an idle SDMA engine, and keeps the stream on that engine otherwise; a pipeline's copies queue
-// behind frames still rendering, so as they pile up they land on engines 1, 2, 4, ... and the
-// first copy on an engine in a direction creates that engine's queue: ~7 ms of host time inside
-// hipMemcpyAsync (profiles/r06/rblog/).  Here each of the n streams queues one copy behind a
-// gate kernel (on a stream of its own), so every copy finds the engines before it busy and the
-// n copies start n engines; then the gate opens.  The streams should be the ones the pipeline
-// will use.  Once per process and device for up to the largest n asked for.
-int rt_copy_engines_warm(void* const* streams, int n) {
-    if (!streams || n < 1 || n > 64) return fail(RT_ERR_ARG, "1 to 64 streams");
-    int ndev = 0, dev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(RT_ERR_NODEV, "no HIP device available");
-    HIPCHK(hipGetDevice(&dev));
-    static std::mutex mu;
-    static int warmed[64] = {};
-    std::lock_guard<std::mutex> lock(mu);
-    if (dev < 0 || dev >= 64 || warmed[dev] >= n) return RT_OK;
-    unsigned* flag = nullptr; uint8_t* h = nullptr; uint8_t* d = nullptr;
-    hipStream_t gate = nullptr;
-    hipEvent_t ev = nullptr;
-    int clk_khz = 0;
-    // (copies below the runtime's SDMA threshold run elsewhere: 1 MB each, all into one buffer)
-    constexpr size_t B = 1 << 20;
-    HIPCHK(hipDeviceGetAttribute(&clk_khz, hipDeviceAttributeWallClockRate, dev));
-    HIPCHK(hipHostMalloc((void**)&flag, 4, hipHostMallocCoherent));
-    HIPCHK(hipHostMalloc((void**)&h, B, hipHostMallocDefault));
-    HIPCHK(hipMalloc((void**)&d, B));
-    HIPCHK(hipMemset(d, 0, B));
-    HIPCHK(hipStreamCreateWithFlags(&gate, hipStreamNonBlocking));
-    HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    __atomic_store_n(flag, 0u, __ATOMIC_RELEASE);
-    hipLaunchKernelGGL(copy_gate_kernel, dim3(1), dim3(64), 0, gate, (const unsigned*)flag,
-                       (unsigned long long)clk_khz * 2000ull);                     // at most 2 s
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ev, gate));
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < n && e == hipSuccess; i++) {
-        e = hipStreamWaitEvent((hipStream_t)streams[i], ev, 0);
-        if (e == hipSuccess) e = hipMemcpyAsync(h, d, B, hipMemcpyDeviceToDeviceNoCU, (hipStream_t)streams[i]);
-    }
-    __atomic_store_n(flag, 1u, __ATOMIC_RELEASE);                              // open the gate
-    HIPCHK(hipStreamSynchronize(gate));
-    for (int i = 0; i < n; i++) HIPCHK(hipStreamSynchronize((hipStream_t)streams[i]));
-    HIPCHK(e);
-    (void)hipEventDestroy(ev);
-    (void)hipStreamDestroy(gate);
-    (void)hipFree(d); (void)hipHostFree(h); (void)hipHostFree(flag);
-    warmed[dev] = n;
-    return RT_OK;
-}
-
-// procedural::gpu::generate / SceneBuilder::build_gpu_scene put the scene on the device when it
-// is made (cube_world.cc:195-207, scene_builder.cu:29-81); the first update_scene then only
-// renders.  Here the upload is lazy (host-only scenes must load without a GPU), so a finished
-// scene on a machine with a gfx950 device is uploaded at once and one untimed 1-spp frame is
-// rendered into the device canvas: the code object, the scene's stream and the frame layout's
-// buffers (sky flags, live lists, scheduling history) are then in place before the caller's
-// first frame.  Without a usable device nothing happens (render calls report RT_ERR_NODEV as
-// before); a failure here is left for the first render to report.  RT_NO_WARM=1 turns it off.
-static int warm_scene(rt_scene* s);
-
-int rt_scene_load_json(const char* path, int width, int height, rt_scene** out) {
-    if (!path || !out) return fail(RT_ERR_ARG, "null argument");
-    std::unique_ptr<rt_scene> s(new rt_scene);
-    std::string err;
-    int r = rt::load_cube_world(path, width, height, &s->h, &err);
-    if (r == -2) return fail(RT_ERR_IO, err);
-    if (r != 0) return fail(RT_ERR_PARSE, err);
-    s->finished = true;
-    s->canvas.assign((size_t)s->h.cam.W * s->h.cam.H, 0u);
-    (void)warm_scene(s.get());
-    *out = s.release();
-    return RT_OK;
-}
-
-int rt_scene_create(const char* atlas, rt_scene** out) {
-    if (!out) return fail(RT_ERR_ARG, "null argument");
-    rt_scene* s = new rt_scene;
-    s->h.atlas = atlas ? atlas : "";
-    *out = s;
-    return RT_OK;
-}
-
-int rt_scene_free(rt_scene* s) { delete s; return RT_OK; }
-
-int rt_builder_add_vertex(rt_scene* s, float x, float y, float z, int* idx) {
-    CHECK_BUILDING(s);
-    int i = s->h.add_vertex(v3(x, y, z));
-    if (idx) *idx = i;
-    return RT_OK;
-}
-int rt_builder_create_mesh(rt_scene* s, const float* pos, const float* q, int* mesh) {
-    CHECK_BUILDING(s);
-    int m = s->h.create_mesh(pos ? v3(pos[0], pos[1], pos[2]) : v3(0, 0, 0), q ? Q{q[0], q[1], q[2], q[3]} : Q{0, 0, 0, 1});
-    if (mesh) *mesh = m;
-    return RT_OK;
-}
-int rt_builder_add_triangle(rt_scene* s, int mesh, int i0, int i1, int i2, const float* mat) {
-    CHECK_BUILDING(s);
-    if (!mat) return fail(RT_ERR_ARG, "null material");
-    if (mesh < 0 || mesh >= (int)s->h.meshes.size()) return fail(RT_ERR_ARG, "mesh index out of range");
-    int nv = (int)s->h.verts.size();
-    if (i0 < 0 || i1 < 0 || i2 < 0 || i0 >= nv || i1 >= nv || i2 >= nv) return fail(RT_ERR_ARG, "vertex index out of range");
-    s->h.add_triangle(mesh, i0, i1, i2, s->h.add_material(mat_from(mat)));
-    return RT_OK;
-}
-int rt_builder_add_triangle_tex(rt_scene* s, int mesh, int i0, int i1, int i2, const float* mat, const float* tex) {
-    CHECK_BUILDING(s);
-    if (!mat || !tex) return fail(RT_ERR_ARG, "null argument");
-    if (mesh < 0 || mesh >= (int)s->h.meshes.size()) return fail(RT_ERR_ARG, "mesh index out of range");
-    int nv = (int)s->h.verts.size();
-    if (i0 < 0 || i1 < 0 || i2 < 0 || i0 >= nv || i1 >= nv || i2 >= nv) return fail(RT_ERR_ARG, "vertex index out of range");
-    rt::TexDesc t;
-    t.has = 1; t.tx = tex[0]; t.ty = tex[1]; t.ux = tex[2]; t.uy = tex[3]; t.vx = tex[4]; t.vy = tex[5];
-    s->h.add_triangle(mesh, i0, i1, i2, s->h.add_material(mat_from(mat)), t);
-    return RT_OK;
-}
-int rt_builder_add_trans(rt_scene* s, int mesh, int* trans) {
-    CHECK_BUILDING(s);
-    if (mesh < 0 || mesh >= (int)s->h.meshes.size()) return fail(RT_ERR_ARG, "mesh index out of range");
-    int t = s->h.add_trans(mesh);
-    if (trans) *trans = t;
-    return RT_OK;
-}
-int rt_builder_set_trans(rt_scene* s, int t, const float* pos, const float* q) {
-    CHECK_SCENE(s);
-    if (t < 0 || t >= (int)s->h.insts.size()) return fail(RT_ERR_ARG, "transformation index out of range");
-    if (pos) s->h.insts[t].pos = v3(pos[0], pos[1], pos[2]);
-    if (q) s->h.insts[t].rot = Q{q[0], q[1], q[2], q[3]};
-    if (s->finished) {   // instances moved after finishing: refresh the flat copy
-        // Device copies are per frame slot and are refreshed, stream-ordered, by the next frame
-        // of each slot (sync_slot_insts): frames in flight keep the poses they were built from.
-        s->h.d_insts[t].pose = make_pose(s->h.insts[t].rot, s->h.insts[t].pos);
-        s->inst_gen++;
-        invalidate(s);
-    }
-    return RT_OK;
-}
-int rt_builder_build_cube(rt_scene* s, float scale, const float* mat, int* mesh) {
-    CHECK_BUILDING(s);
-    if (!mat) return fail(RT_ERR_ARG, "null material");
-    int m = s->h.build_cube(scale, mat_from(mat));
-    if (mesh) *mesh = m;
-    return RT_OK;
-}
-int rt_builder_build_cube_tex(rt_scene* s, float scale, const float* mat, const float* tile, int* mesh) {
-    CHECK_BUILDING(s);
-    if (!mat || !tile) return fail(RT_ERR_ARG, "null argument");
-    int m = s->h.build_cube(scale, mat_from(mat), tile);
-    if (mesh) *mesh = m;
-    return RT_OK;
-}
-int rt_builder_add_point_light(rt_scene* s, const float* pos, const float* col) {
-    CHECK_BUILDING(s);
-    if (!pos || !col) return fail(RT_ERR_ARG, "null argument");
-    s->h.add_point_light(v3(pos[0], pos[1], pos[2]), v4(col[0], col[1], col[2], col[3]));
-    return RT_OK;
-}
-int rt_builder_add_directional_light(rt_scene* s, const float* dir, const float* col) {
-    CHECK_BUILDING(s);
-    if (!dir || !col) return fail(RT_ERR_ARG, "null argument");
-    s->h.add_directional_light(v3(dir[0], dir[1], dir[2]), v4(col[0], col[1], col[2], col[3]));
-    return RT_OK;
-}
-int rt_builder_finish(rt_scene* s, int W, int H, float fov, float unit, const float* cpos, const float* cq,
-                      const float* da, const float* amb, int depth) {
-    CHECK_BUILDING(s);
-    if (W <= 0 || H <= 0 || !(unit > 0)) return fail(RT_ERR_ARG, "bad canvas/camera parameters");
-    s->h.set_camera(W, H, fov, unit);
-    if (cpos) s->h.cam.pos = v3(cpos[0], cpos[1], cpos[2]);
-    if (cq) s->h.cam.rot = Q{cq[0], cq[1], cq[2], cq[3]};
-    if (da) s->h.dist_atten = v3(da[0], da[1], da[2]);
-    if (amb) s->h.ambience = v4(amb[0], amb[1], amb[2], amb[3]);
-    s->h.depth = depth;
-    std::string err;
-    if (s->h.flatten(&err) != 0) return fail(RT_ERR_PARSE, err);
-    s->finished = true;
-    s->canvas.assign((size_t)W * H, 0u);
-    (void)warm_scene(s);
-    return RT_OK;
-}
-
-int rt_scene_info(const rt_scene* s, int32_t* c) {
-    CHECK_FINISHED(s);
-    if (!c) return fail(RT_ERR_ARG, "null argument");
-    const rt::Scene& h = s->h;
-    c[0] = h.cam.W; c[1] = h.cam.H; c[2] = (int)h.verts.size(); c[3] = (int)h.tris.size(); c[4] = (int)h.meshes.size();
-    c[5] = (int)h.insts.size(); c[6] = (int)h.d_lights.size(); c[7] = (int)h.points.size(); c[8] = h.depth;
-    c[9] = (int)h.mats.size();
-    return RT_OK;
-}
-
-// (ABI 3) hit_tri indexes the triangles in flattened mesh order, so the meshes must list every
-// triangle exactly once: a bitmap of the triangles seen, failing on a repeat or on one left out
-// (a count alone would pass a list that repeats one triangle and omits another).
-static bool meshes_cover_tris_once(const rt::Scene& h) {
-    std::vector<unsigned char> seen(h.tris.size(), 0);
-    size_t n = 0;
-    for (auto& m : h.meshes)
-        for (int i : m.tris) {
-            if (i < 0 || (size_t)i >= seen.size() || seen[i]) return false;
-            seen[i] = 1;
-            n++;
-        }
-    return n == h.tris.size();
-}
-
-int rt_scene_export(const rt_scene* s, int what, void* dst, int64_t cap) {
-    CHECK_FINISHED(s);
-    const rt::Scene& h = s->h;
-    if ((what == RT_EXPORT_TRIS || what == RT_EXPORT_TEXCOORDS) && !meshes_cover_tris_once(h))
-        return fail(RT_ERR_STATE, "meshes do not cover every triangle once");
-    std::vector<float> f;
-    std::vector<int32_t> iv;
-    switch (what) {
-        case RT_EXPORT_VERTICES: for (auto& v : h.verts) { f.push_back(v.x); f.push_back(v.y); f.push_back(v.z); } break;
-        case RT_EXPORT_NORMALS: f = h.verts_norm; break;
-        case RT_EXPORT_TRIS:                                   // flattened (mesh) order: hit_tri indexes it
-            for (auto& m : h.meshes)
-                for (int i : m.tris) { const auto& t = h.tris[i]; iv.insert(iv.end(), {t.i0, t.i1, t.i2, t.mat}); }
-            break;
-        case RT_EXPORT_MATERIALS:
-            for (auto& m : h.mats) {
-                for (const V4* v : {&m.Ke, &m.Ka, &m.Kd, &m.Ks, &m.Kt, &m.Kr}) { f.push_back(v->x); f.push_back(v->y); f.push_back(v->z); f.push_back(v->w); }
-                f.push_back(m.alpha); f.push_back(m.eta);
-            }
-            break;
-        case RT_EXPORT_INSTANCES:
-            for (auto& t : h.insts) { f.insert(f.end(), {t.rot.i, t.rot.j, t.rot.k, t.rot.r, t.pos.x, t.pos.y, t.pos.z}); }
-            break;
-        case RT_EXPORT_INST_MESH: for (auto& t : h.insts) iv.push_back(t.mesh); break;
-        case RT_EXPORT_LIGHTS:
-            for (auto& l : h.d_lights) f.insert(f.end(), {l.v.x, l.v.y, l.v.z, (float)l.type, l.col.x, l.col.y, l.col.z, l.col.w});
-            break;
-        case RT_EXPORT_CAMERA: {
-            const DCamera& c = h.d_cam;
-            f = {c.pos.x, c.pos.y, c.pos.z, h.cam.rot.i, h.cam.rot.j, h.cam.rot.k, h.cam.rot.r, c.near_, c.unit, c.W, c.H,
-                 c.r.x, c.r.y, c.r.z, c.u.x, c.u.y, c.u.z, c.f.x, c.f.y, c.f.z, 0.0f};
-            break;
-        }
-        case RT_EXPORT_ENV:
-            f = {h.dist_atten.x, h.dist_atten.y, h.dist_atten.z, h.ambience.x, h.ambience.y, h.ambience.z, h.ambience.w};
-            break;
-        case RT_EXPORT_TEXCOORDS:
-            for (auto& m : h.meshes)
-                for (int i : m.tris) {
-                    const auto& t = h.tris[i];
-                    f.insert(f.end(), {(float)t.tex.has, t.tex.tx, t.tex.ty, t.tex.ux, t.tex.uy, t.tex.vx, t.tex.vy});
-                }
-            break;
-        case RT_EXPORT_ATLAS: {
-            const size_t n = h.atlas_rgba.size();
-            if (!dst || cap < (int64_t)n) return fail(RT_ERR_ARG, "destination too small");
-            if (n) memcpy(dst, h.atlas_rgba.data(), n);
-            return RT_OK;
-        }
-        default: return fail(RT_ERR_ARG, "unknown export");
-    }
-    size_t bytes = f.size() * 4 + iv.size() * 4;
-    if (!dst || cap < (int64_t)bytes) return fail(RT_ERR_ARG, "destination too small");
-    if (!f.empty()) memcpy(dst, f.data(), f.size() * 4);
-    if (!iv.empty()) memcpy(dst, iv.data(), iv.size() * 4);
-    return RT_OK;
-}
-
-int rt_camera_get(const rt_scene* s, float* pos, float* q) {
-    CHECK_SCENE(s);
-    if (pos) { pos[0] = s->h.cam.pos.x; pos[1] = s->h.cam.pos.y; pos[2] = s->h.cam.pos.z; }
-    if (q) { q[0] = s->h.cam.rot.i; q[1] = s->h.cam.rot.j; q[2] = s->h.cam.rot.k; q[3] = s->h.cam.rot.r; }
-    return RT_OK;
-}
-int rt_camera_set(rt_scene* s, const float* pos, const float* q) {
-    CHECK_FINISHED(s);
-    if (pos) s->h.cam.pos = v3(pos[0], pos[1], pos[2]);
-    if (q) s->h.cam.rot = Q{q[0], q[1], q[2], q[3]};
-    s->h.update_camera_basis();
-    return RT_OK;
-}
-int rt_camera_translate(rt_scene* s, const float* d) {           // entity.h:53-56: translate_global(vec_to_local(dp))
-    CHECK_FINISHED(s);
-    if (!d) return fail(RT_ERR_ARG, "null argument");
-    s->h.cam.pos = s->h.cam.pos + qrot(s->h.cam.rot, v3(d[0], d[1], d[2]));
-    s->h.update_camera_basis();
-    return RT_OK;
-}
-int rt_camera_rotate(rt_scene* s, const float* dq) {             // entity.h:63-65: o = dr * o
-    CHECK_FINISHED(s);
-    if (!dq) return fail(RT_ERR_ARG, "null argument");
-    s->h.cam.rot = qmul(Q{dq[0], dq[1], dq[2], dq[3]}, s->h.cam.rot);
-    s->h.update_camera_basis();
-    return RT_OK;
-}
-int rt_camera_axes(const rt_scene* s, float* r, float* u, float* f) {
-    CHECK_FINISHED(s);
-    const DCamera& c = s->h.d_cam;
-    if (r) { r[0] = c.r.x; r[1] = c.r.y; r[2] = c.r.z; }
-    if (u) { u[0] = c.u.x; u[1] = c.u.y; u[2] = c.u.z; }
-    if (f) { f[0] = c.f.x; f[1] = c.f.y; f[2] = c.f.z; }
-    return RT_OK;
-}
-int rt_env_set(rt_scene* s, const float* amb, const float* da, int depth) {
-    CHECK_FINISHED(s);
-    if (depth < 0 || depth >= MAX_FRAMES) return fail(RT_ERR_ARG, "depth must be in [0, 9]");
-    if (amb) s->h.ambience = v4(amb[0], amb[1], amb[2], amb[3]);
-    if (da) s->h.dist_atten = v3(da[0], da[1], da[2]);
-    s->h.depth = depth;
-    return RT_OK;
-}
-
-int rt_scene_set_atlas(rt_scene* s, const uint8_t* rgba8, int w, int h) {
-    if (!s) return fail(RT_ERR_ARG, "null scene");
-    if (!rgba8 || w <= 0 || h <= 0 || w > 16384 || h > 16384) return fail(RT_ERR_ARG, "bad atlas image");
-    s->h.atlas_rgba.assign(rgba8, rgba8 + (size_t)w * h * 4);
-    s->h.atlas_w = w; s->h.atlas_h = h;
-    s->atlas_dirty = true;
-    return RT_OK;
-}
-int rt_scene_load_atlas(rt_scene* s, const char* path) {
-    if (!s) return fail(RT_ERR_ARG, "null scene");
-    std::vector<std::string> tries;
-    if (path) tries.push_back(path);
-    else {
-        if (s->h.atlas.empty()) return fail(RT_ERR_STATE, "the scene names no atlas");
-        if (s->h.atlas[0] != '/' && !s->h.base_dir.empty()) tries.push_back(s->h.base_dir + "/" + s->h.atlas);
-        tries.push_back(s->h.atlas);
-    }
-    std::string err;
-    for (const std::string& p : tries) {
-        std::ifstream probe(p, std::ios::binary);
-        if (!probe) { err = p + ": cannot open"; continue; }
-        std::vector<uint8_t> px;
-        int w = 0, h = 0;
-        if (rt::load_png_rgba8(p, &px, &w, &h, &err) != 0) return fail(RT_ERR_PARSE, err);
-        return rt_scene_set_atlas(s, px.data(), w, h);
-    }
-    return fail(RT_ERR_IO, err);
-}
-int rt_scene_atlas_info(const rt_scene* s, int32_t* a) {
-    if (!s || !a) return fail(RT_ERR_ARG, "null argument");
-    a[0] = s->h.atlas_w; a[1] = s->h.atlas_h; a[2] = s->h.atlas_rgba.empty() ? 0 : 1;
-    return RT_OK;
-}
-
-void rt_render_opts_default(rt_render_opts* o) {
-    if (!o) return;
-    memset(o, 0, sizeof *o);
-    o->spp = 1; o->use_bvh = 1; o->rebuild_bvh = 1; o->row0 = 0; o->row_step = 1; o->kernel_dim = 16; o->sync = 1;
-}
-
-int rt_render(rt_scene* s, const rt_render_opts* o, rt_stats* stats) {
-    CHECK_FINISHED(s);
-    if (!o) return fail(RT_ERR_ARG, "null options");
-    if (o->spp < 1 || o->row_step < 1 || o->row0 < 0) return fail(RT_ERR_ARG, "spp >= 1, row_step >= 1, row0 >= 0 required");
-    int r;
-    if ((r = upload(s)) != RT_OK) return r;
-    HIPCHK(hipSetDevice(s->device));
-    if ((size_t)s->h.cam.W * s->h.cam.H > (size_t)INT32_MAX) return fail(RT_ERR_LIMIT, "frame larger than 2^31 pixels");
-    if (s->multi && o->row0 == 0 && o->row_step == 1) return render_multi(s, o, stats);   // whole frames: split
-    if ((r = ensure_spp(s, o->spp)) != RT_OK) return r;
-    hipStream_t st = o->stream ? (hipStream_t)o->stream : sstream(s);
-    const bool timed = stats != nullptr;
-    hipEvent_t* te = nullptr;
-    if (o->timing) {
-        if (s->tev_used + 4 > s->tev.size()) {
-            if (s->tev.size() >= 4 * 4096) return fail(RT_ERR_STATE, "too many timed frames pending: call rt_timing_collect");
-            for (int i = 0; i < 4 * 64; i++) { hipEvent_t e; HIPCHK(hipEventCreate(&e)); s->tev.push_back(e); }
-        }
-        te = &s->tev[s->tev_used];
-        s->tev_used += 4;
-    }
-    if (s->n_slots > 1) {                                    // rotate frame slots (rt_scene_set_frame_slots)
-        if ((r = ensure_other_slot(s)) != RT_OK) return r;
-        select_slot(s, (s->cur_slot + 1) % s->n_slots);
-    }
-    if ((r = begin_frame(s, st, false)) != RT_OK) return r;  // after the slot's previous frame, current poses
-    if (timed) { HIPCHK(hipMemsetAsync(s->d_stats, 0, STATS_N * sizeof(unsigned long long), st)); HIPCHK(hipEventRecord(s->ev[0], st)); }
-    if (o->use_bvh && (o->rebuild_bvh || !s->bvh_valid)) {
-        if ((r = build_bvh(s, st, te ? te[0] : nullptr, te ? te[1] : nullptr)) != RT_OK) {
-            if (te) s->tev_used -= 4;                            // the frame's events stay unrecorded
-            return r;
-        }
-    } else if (te) {
-        HIPCHK(hipEventRecord(te[0], st)); HIPCHK(hipEventRecord(te[1], st));
-    }
-    if (timed) HIPCHK(hipEventRecord(s->ev[1], st));
-    rt_render_opts oo = *o;
-    const size_t W = s->h.cam.W, H = s->h.cam.H;
-    const size_t n_rows = (H > (size_t)o->row0) ? (H - o->row0 + o->row_step - 1) / o->row_step : 0;
-    const size_t out_px = o->compact ? n_rows * W : W * H;
-    if (o->host_outputs) {                                   // stage through device buffers
-        if (s->d_out_px < W * H) {
-            for (auto& p : s->d_out) dfree(p);
-            HIPCHK(hipMalloc(&s->d_out[0], W * H * 4)); HIPCHK(hipMalloc(&s->d_out[1], W * H * 16));
-            HIPCHK(hipMalloc(&s->d_out[2], W * H * 4)); HIPCHK(hipMalloc(&s->d_out[3], W * H * 4));
-            s->d_out_px = W * H;
-        }
-        oo.rgba = o->rgba ? (uint32_t*)s->d_out[0] : nullptr;
-        oo.radiance = o->radiance ? (float*)s->d_out[1] : nullptr;
-        oo.hit_inst = o->hit_inst ? (int32_t*)s->d_out[2] : nullptr;
-        oo.hit_tri = o->hit_tri ? (int32_t*)s->d_out[3] : nullptr;
-    }
-    uint32_t* rgba = oo.rgba ? oo.rgba : s->d_canvas;
-    if ((r = launch_trace(s, oo, st, rgba, nullptr, -1, -1, timed, -1, te ? te[2] : nullptr, te ? te[3] : nullptr)) != RT_OK) {
-        if (te) s->tev_used -= 4;
-        return r;
-    }
-    if (timed) HIPCHK(hipEventRecord(s->ev[2], st));
-    if ((r = end_frame(s, st)) != RT_OK) return r;           // the slot is free again once this frame is done
-    if (o->sync || timed || o->host_outputs) HIPCHK(hipStreamSynchronize(st));
-    if (o->host_outputs) {
-        if (o->rgba) HIPCHK(hipMemcpy(o->rgba, oo.rgba, out_px * 4, hipMemcpyDeviceToHost));
-        if (o->radiance) HIPCHK(hipMemcpy(o->radiance, oo.radiance, out_px * 16, hipMemcpyDeviceToHost));
-        if (o->hit_inst) HIPCHK(hipMemcpy(o->hit_inst, oo.hit_inst, out_px * 4, hipMemcpyDeviceToHost));
-        if (o->hit_tri) HIPCHK(hipMemcpy(o->hit_tri, oo.hit_tri, out_px * 4, hipMemcpyDeviceToHost));
-    }
-    if (timed) {
-        unsigned long long v[4];
-        HIPCHK(hipMemcpy(v, s->d_stats, sizeof v, hipMemcpyDeviceToHost));
-        stats->rays = v[0]; stats->nodes = v[1]; stats->leaves = v[2]; stats->tri_tests = v[3];
-        float a = 0, b = 0;
-        HIPCHK(hipEventElapsedTime(&a, s->ev[0], s->ev[1]));
-        HIPCHK(hipEventElapsedTime(&b, s->ev[1], s->ev[2]));
-        stats->bvh_ms = a; stats->trace_ms = b;
-    }
-    return RT_OK;
-}
-
-
-int rt_scene_set_frame_slots(rt_scene* s, int n) {
-    CHECK_FINISHED(s);
-    if (n < 1 || n > rt_scene::MAX_SLOTS) return fail(RT_ERR_ARG, "frame slots: 1 to " + std::to_string(rt_scene::MAX_SLOTS));
-    if (n == s->n_slots) return RT_OK;
-    if (s->uploaded) { HIPCHK(hipSetDevice(s->device)); HIPCHK(hipDeviceSynchronize()); }   // nothing in flight
-    select_slot(s, 0);
-    for (auto& p : s->slot_pending) p = false;
-    s->n_slots = n;
-    return (n > 1 && s->uploaded) ? ensure_other_slot(s) : RT_OK;
-}
-
-int rt_scene_set_overlap(rt_scene* s, int policy) {
-    CHECK_SCENE(s);
-    if (policy != RT_OVERLAP_HALF && policy != RT_OVERLAP_FULL && policy != RT_OVERLAP_STREAM)
-        return fail(RT_ERR_ARG, "overlap policy: RT_OVERLAP_HALF, RT_OVERLAP_FULL or RT_OVERLAP_STREAM");
-    s->overlap = policy;
-    if (s->multi)                                              // the replicas of rt_scene_set_devices too
-        for (rt_scene* rp : s->multi->reps) rp->overlap = policy;
-    return RT_OK;
-}
-
-int rt_scene_set_devices(rt_scene* s, const int* devices, int n_devices, int n_ranks) {
-    CHECK_FINISHED(s);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(RT_ERR_NODEV, "no HIP device available");
-    if (!devices || n_devices < 1 || n_ranks < n_devices || n_ranks % n_devices != 0)
-        return fail(RT_ERR_ARG, "n_devices >= 1 device indices, n_ranks a multiple of n_devices");
-    for (int i = 0; i < n_devices; i++) {
-        if (devices[i] < 0 || devices[i] >= ndev) return fail(RT_ERR_ARG, "device index out of range");
-        for (int j = 0; j < i; j++) if (devices[j] == devices[i]) return fail(RT_ERR_ARG, "a device listed twice");
-    }
-    if (n_ranks > s->h.cam.H) return fail(RT_ERR_ARG, "more ranks than canvas rows");
-    int r;
-    if (s->uploaded && s->device != devices[0]) return fail(RT_ERR_STATE, "devices[0] must be the scene's device");
-    if (!s->uploaded) {
-        const int saved = g_device;
-        g_device = devices[0];
-        r = upload(s);
-        g_device = saved;
-        if (r != RT_OK) return r;
-    }
-    HIPCHK(hipSetDevice(s->device));
-    HIPCHK(hipDeviceSynchronize());
-    free_multi(s);
-    if (n_devices == 1 && n_ranks == 1) return RT_OK;       // back to single-device frames
-    MultiDev* m = new MultiDev;
-    m->devices.assign(devices, devices + n_devices);
-    m->n_ranks = n_ranks; m->per_dev = n_ranks / n_devices;
-    m->W = s->h.cam.W; m->H = s->h.cam.H;
-    m->rows_max = (m->H + n_ranks - 1) / n_ranks;
-    m->reps.push_back(s);
-    m->inst_gen.push_back(s->inst_gen);
-    s->multi = m;
-    s->ranks_per_device = m->per_dev;
-    return RT_OK;
-}
-
-int rt_timing_collect(rt_scene* s, double* bvh_ms, double* trace_ms, int* n) {
-    CHECK_FINISHED(s);
-    double a = 0, b = 0;
-    for (size_t i = 0; i + 4 <= s->tev_used; i += 4) {
-        HIPCHK(hipEventSynchronize(s->tev[i + 3]));
-        float x = 0, y = 0;
-        HIPCHK(hipEventElapsedTime(&x, s->tev[i], s->tev[i + 1]));
-        HIPCHK(hipEventElapsedTime(&y, s->tev[i + 2], s->tev[i + 3]));
-        a += x; b += y;
-    }
-    if (bvh_ms) *bvh_ms = a;
-    if (trace_ms) *trace_ms = b;
-    if (n) *n = (int)(s->tev_used / 4);
-    s->tev_used = 0;
-    return RT_OK;
-}
-
-int rt_update_scene(rt_scene* s, int kernel_dim, int optimize) {    // raytracer.cu:102-120
-    CHECK_FINISHED(s);
-    if (kernel_dim <= 0) return fail(RT_ERR_ARG, "kernel_dim must be positive");
-    rt_render_opts o;
-    rt_render_opts_default(&o);
-    o.use_bvh = optimize ? 1 : 0; o.rebuild_bvh = 1; o.kernel_dim = kernel_dim;
-    o.sync = s->multi ? 1 : 0;                                // split frames end on the slot's streams
-    int r = rt_render(s, &o, nullptr);
-    if (r != RT_OK) return r;
-    // the canvas is host-readable on return (canvas.cu:23-29): one copy-engine transfer into the
-    // pinned host canvas on the frame's stream, then wait for that stream only
-    hipStream_t st = sstream(s);
-    if (s->canvas.pinned)
-        HIPCHK(hipMemcpyAsync(s->canvas.data(), s->d_canvas, s->canvas.size() * sizeof(uint32_t), hipMemcpyDeviceToDeviceNoCU, st));
-    else
-        HIPCHK(hipMemcpyAsync(s->canvas.data(), s->d_canvas, s->canvas.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return RT_OK;
-}
-
-static int warm_scene(rt_scene* s) {
-    static const bool off = [] { const char* e = getenv("RT_NO_WARM"); return e && atoi(e) != 0; }();
-    int n = 0;
-    if (off || hipGetDeviceCount(&n) != hipSuccess || n <= 0) { (void)hipGetLastError(); return RT_OK; }
-    const std::string saved = g_err;
-    // update_scene's own path: a 1-spp frame and its copy into the pinned canvas (the copy starts
-    // the copy engine's queue for device-to-host transfers, ~7 ms the first time)
-    if (s->h.cam.W > 0 && s->h.cam.H > 0 && rt_update_scene(s, 16, 1) != RT_OK) {
-        g_err = saved;                                    // left for the caller's first render to report
-        (void)hipGetLastError();
-        return RT_OK;
-    }
-    // capacity for the whole frame at 8 pixels per wave (4 x 2 groups: 8-32 spp, the bench's layout)
-    const long long groups = (long long)((s->h.cam.W + 3) / 4) * ((s->h.cam.H + 1) / 2);
-    if (groups < (1ll << 26) && reserve_layout(s, (int)groups) != RT_OK) { g_err = saved; (void)hipGetLastError(); }
-    return RT_OK;
-}
-
-int rt_canvas_read(const rt_scene* s, uint32_t* dst, int64_t n) {
-    CHECK_FINISHED(s);
-    if (!dst || n < (int64_t)s->canvas.size()) return fail(RT_ERR_ARG, "destination too small");
-    memcpy(dst, s->canvas.data(), s->canvas.size() * sizeof(uint32_t));
-    return RT_OK;
-}
-const uint32_t* rt_canvas_host_ptr(const rt_scene* s) { return s ? s->canvas.data() : nullptr; }
-int rt_canvas_get_color(const rt_scene* s, int x, int y, uint8_t* c) {
-    CHECK_FINISHED(s);
-    if (!c || x < 0 || y < 0 || x >= s->h.cam.W || y >= s->h.cam.H) return fail(RT_ERR_ARG, "pixel out of range");
-    uint32_t e = s->canvas[(size_t)y * s->h.cam.W + x];                  // Color::from_encoding (color.cu:28-34)
-    c[0] = (uint8_t)(e >> 24); c[1] = (uint8_t)(e >> 16); c[2] = (uint8_t)(e >> 8); c[3] = (uint8_t)e;
-    return RT_OK;
-}
-
-int rt_debug_cast(rt_scene* s, int x, int y, char* buf, int64_t cap) {   // raytracer.cu:91-100
-    CHECK_FINISHED(s);
-    if (x < 0 || y < 0 || x >= s->h.cam.W || y >= s->h.cam.H) return fail(RT_ERR_ARG, "pixel out of range");
-    int r;
-    if ((r = upload(s)) != RT_OK) return r;
-    HIPCHK(hipSetDevice(s->device));
-    if ((r = ensure_spp(s, 1)) != RT_OK) return r;
-    // rebuilds the current slot's BVH: first wait for every frame in flight (any slot)
-    if ((r = begin_frame(s, sstream(s), true)) != RT_OK) return r;
-    if ((r = build_bvh(s, sstream(s))) != RT_OK) return r;
-    HIPCHK(hipMemsetAsync(s->d_dbg, 0, 4096 * sizeof(int), sstream(s)));
-    rt_render_opts o;
-    rt_render_opts_default(&o);
-    o.row0 = y; o.row_step = s->h.cam.H;                                  // just the row of (x, y)
-    if ((r = launch_trace(s, o, sstream(s), s->d_canvas, s->d_dbg, x, y, true)) != RT_OK) return r;
-    if ((r = end_frame(s, sstream(s))) != RT_OK) return r;
-    std::vector<int> log(4096);
-    HIPCHK(hipStreamSynchronize(sstream(s)));
-    HIPCHK(hipMemcpy(log.data(), s->d_dbg, log.size() * sizeof(int), hipMemcpyDeviceToHost));
-    static const char* names[] = {"", "shooting a ray", "preparing to shoot a reflection ray",
-                                  "preparing to shoot a refraction ray", "shooting shadow ray"};
-    std::string out;
-    int n = std::min(log[0], 4094);
-    for (int i = 0; i < n; i++) { int e = log[2 + i]; if (e >= 1 && e <= 4) { out += names[e]; out += '\n'; } }
-    if (buf && cap > 0) { size_t m = std::min<size_t>(out.size(), (size_t)cap - 1); memcpy(buf, out.data(), m); buf[m] = 0; }
-    return RT_OK;
-}
-
-// Profiling aid (not part of rt_amd.h's stable surface): run experiment `which` `reps`
-// times -- 4: the counted kernel with the occlusion early exit, 5: the counted kernel,
-// 6: the fast kernel's PROF variant (wave step counts, cycle split, and the queries the
-// fast kernel issues) -- and return the mean kernel ms and the counters.
-int rt_experiment(rt_scene* s, int which, int spp, int reps, double* ms, uint64_t* counters) {
-    CHECK_FINISHED(s);
-    int r;
-    if (which == 4 || which == 5 || which == 6) {             // full frame: counted kernel (4: occlusion exit on),
-                                                              // 6: the fast kernel's profiling variant (M_PROF)
-        if ((r = upload(s)) != RT_OK) return r;
-        HIPCHK(hipSetDevice(s->device));
-        if ((r = ensure_spp(s, spp)) != RT_OK) return r;
-        rt_render_opts o; rt_render_opts_default(&o); o.spp = spp;
-        if ((r = begin_frame(s, sstream(s), true)) != RT_OK) return r;   // nothing else in flight on this slot
-        if ((r = build_bvh(s, sstream(s))) != RT_OK) return r;
-        float total = 0;
-        for (int i = 0; i < reps; i++) {
-            HIPCHK(hipMemsetAsync(s->d_stats, 0, STATS_N * sizeof(unsigned long long), sstream(s)));
-            HIPCHK(hipMemsetAsync(s->d_stats + 15, 0xff, sizeof(unsigned long long), sstream(s)));
-            HIPCHK(hipMemsetAsync(s->d_stats + 19, 0xff, sizeof(unsigned long long), sstream(s)));
-            HIPCHK(hipEventRecord(s->ev[0], sstream(s)));
-            if ((r = (which == 6 ? launch_trace(s, o, sstream(s), s->d_canvas, nullptr, -1, -1, false, -1, nullptr, nullptr, true)
-                                 : launch_trace(s, o, sstream(s), s->d_canvas, nullptr, -1, -1, true, which == 4 ? 1 : 0))) != RT_OK)
-                return r;
-            HIPCHK(hipEventRecord(s->ev[1], sstream(s)));
-            HIPCHK(hipEventSynchronize(s->ev[1]));
-            float t = 0; HIPCHK(hipEventElapsedTime(&t, s->ev[0], s->ev[1]));
-            if (i > 0 || reps == 1) total += t;
-        }
-        if ((r = end_frame(s, sstream(s))) != RT_OK) return r;
-        unsigned long long v[22];
-        HIPCHK(hipMemcpy(v, s->d_stats, sizeof v, hipMemcpyDeviceToHost));
-        if (counters) for (int i = 0; i < 22; i++) counters[i] = v[i];
-        if (ms) *ms = total / (reps > 1 ? reps - 1 : 1);
-        return RT_OK;
-    }
-    return fail(RT_ERR_ARG, "experiment: 4 (counted, occlusion exit), 5 (counted), 6 (fast kernel, PROF counters)");
-}
-
-int rt_frame_work(rt_scene* s, const rt_render_opts* o, rt_work* w) {
-    CHECK_FINISHED(s);
-    if (!o || !w) return fail(RT_ERR_ARG, "null argument");
-    if (o->spp < 1 || o->spp > 64 || o->row_step < 1 || o->row0 < 0 || !o->use_bvh || o->textures)
-        return fail(RT_ERR_ARG, "rt_frame_work: BVH frames, 1 <= spp <= 64, untextured");
-    int r;
-    if ((r = upload(s)) != RT_OK) return r;
-    HIPCHK(hipSetDevice(s->device));
-    if ((r = ensure_spp(s, o->spp)) != RT_OK) return r;
-    const size_t rows = (s->h.cam.H > o->row0) ? (size_t)(s->h.cam.H - o->row0 + o->row_step - 1) / o->row_step : 0;
-    uint32_t* d_rgba = nullptr;
-    HIPCHK(hipMalloc((void**)&d_rgba, std::max<size_t>(1, (o->compact ? rows : (size_t)s->h.cam.H) * s->h.cam.W) * 4));
-    hipStream_t st = sstream(s);
-    r = begin_frame(s, st, true);                             // nothing else in flight on this slot
-    if (r == RT_OK) r = build_bvh(s, st);
-    if (r == RT_OK) {
-        HIPCHK(hipMemsetAsync(s->d_stats, 0, STATS_N * sizeof(unsigned long long), st));
-        HIPCHK(hipMemsetAsync(s->d_stats + 15, 0xff, sizeof(unsigned long long), st));
-        HIPCHK(hipMemsetAsync(s->d_stats + 19, 0xff, sizeof(unsigned long long), st));
-        rt_render_opts oo = *o;
-        oo.radiance = nullptr; oo.hit_inst = oo.hit_tri = nullptr;
-        r = launch_trace(s, oo, st, d_rgba, nullptr, -1, -1, false, -1, nullptr, nullptr, true);
-    }
-    if (r == RT_OK) r = end_frame(s, st);
-    unsigned long long v[STATS_N] = {};
-    if (r == RT_OK) {
-        HIPCHK(hipStreamSynchronize(st));
-        HIPCHK(hipMemcpy(v, s->d_stats, sizeof v, hipMemcpyDeviceToHost));
-        if (v[4] == 0 && rows > 0) r = fail(RT_ERR_STATE, "no profiling variant of the fast kernel for this scene");
-    }
-    (void)hipFree(d_rgba);
-    if (r != RT_OK) return r;
-    w->queries = v[0]; w->wave_queries = v[4]; w->pair_steps = v[5]; w->leaf_visits = v[6]; w->tri_iters = v[7];
-    w->leaf_lanes = v[2];
-    w->scene_bytes = lds_bytes(view_of(s, true), true, true);   // the scene image a block stages
-    w->lanes_primary = v[PROF_LANES_PRIMARY]; w->lanes_secondary = v[PROF_LANES_SECONDARY];
-    w->lanes_shadow = v[PROF_LANES_SHADOW]; w->lanes_unlit = v[PROF_LANES_UNLIT];
-    w->live_wave_queries = v[PROF_LIVE_WQ]; w->live_lanes = v[PROF_LIVE_LANES];
-    for (int i = 0; i < 8; i++) {
-        w->hist_wave_queries[i] = v[PROF_HIST_WQ + i];
-        w->hist_pair_steps[i] = v[PROF_HIST_PAIR + i];
-        w->hist_leaf_visits[i] = v[PROF_HIST_LEAF + i];
-    }
-    return RT_OK;
-}
-
-// Profiling aid (tools/group_profile.py, not on the product path): per-group durations
-// (100 MHz ticks) of the fast frame kernel over rows row0, row0 + row_step, ... (compact),
-// as bench.py's rank row0 of row_step renders them.  `reps` frames, each with the per-frame
-// BVH rebuild; the last one (scheduled from the previous frame's history) is recorded.
-// geo = {n_groups, gw, gh, n_gx}; *ms = the last frame's kernel time.  prof = 1: the recorded
-// frame runs the PROF variant (when the scene has one) and out[n_groups + 12 g ..] holds group
-// g's wave queries, child-pair steps, leaf visits, triangle iterations, then shader cycles in
-// queries, in leaf visits, in trace_sample, after queries (state machine), and in the group; then
-// (slots 9-11) cycles in the light step (ST_LIGHT), in the hit normal of a query's step, and in
-// parking (writes before the query, reads after it; the reads also count in the query's cycles).
-int rt_profile_groups(rt_scene* s, int spp, int row0, int row_step, int reps, int prof, uint32_t* out, int64_t cap,
-                      int* geo, double* ms) {
-    CHECK_FINISHED(s);
-    if (!out || !geo || cap <= 0 || reps < 1 || row_step < 1 || row0 < 0) return fail(RT_ERR_ARG, "bad arguments");
-    int r;
-    if ((r = upload(s)) != RT_OK) return r;
-    HIPCHK(hipSetDevice(s->device));
-    if ((r = ensure_spp(s, spp)) != RT_OK) return r;
-    const int rows = (s->h.cam.H - row0 + row_step - 1) / row_step;
-    if (rows <= 0) return fail(RT_ERR_ARG, "no rows in the slice");
-    rt_render_opts o; rt_render_opts_default(&o);
-    o.spp = spp; o.row0 = row0; o.row_step = row_step; o.compact = 1;
-    uint32_t* d_rgba = nullptr;
-    unsigned* d_g = nullptr;
-    HIPCHK(hipMalloc((void**)&d_rgba, (size_t)s->h.cam.W * rows * sizeof(uint32_t)));
-    geo[0] = geo[1] = geo[2] = geo[3] = 0;
-    reps = std::max(reps, 2);                                 // frame 0 sizes the buffer and seeds the history
-    const int nw = prof ? 13 : 1;                             // prof: + 12 counters per group (PROF kernel)
-    if ((r = begin_frame(s, sstream(s), true)) != RT_OK) { (void)hipFree(d_rgba); return r; }
-    for (int i = 0; i < reps && r == RT_OK; i++) {
-        const bool rec = i == reps - 1;
-        if (rec) {
-            if (geo[0] <= 0 || (int64_t)geo[0] * nw > cap) { r = fail(RT_ERR_LIMIT, "group buffer too small"); break; }
-            HIPCHK(hipMalloc((void**)&d_g, (size_t)geo[0] * nw * sizeof(unsigned)));
-            HIPCHK(hipMemsetAsync(d_g, 0, (size_t)geo[0] * nw * sizeof(unsigned), sstream(s)));
-        }
-        if ((r = build_bvh(s, sstream(s))) != RT_OK) break;
-        r = launch_trace(s, o, sstream(s), d_rgba, nullptr, -1, -1, false, -1, s->ev[0], s->ev[1], rec && prof,
-                         rec ? d_g : nullptr, geo);
-    }
-    if (r == RT_OK) r = end_frame(s, sstream(s));
-    if (r == RT_OK) {
-        HIPCHK(hipEventSynchronize(s->ev[1]));
-        float t = 0;
-        HIPCHK(hipEventElapsedTime(&t, s->ev[0], s->ev[1]));
-        if (ms) *ms = t;
-        HIPCHK(hipMemcpy(out, d_g, (size_t)geo[0] * nw * sizeof(unsigned), hipMemcpyDeviceToHost));
-    }
-    (void)hipFree(d_rgba);
-    (void)hipFree(d_g);
-    return r;
-}
-
-int rt_kat_device(const char* op, int n, const float* in0, const float* in1, const float* in2, float* of, int32_t* oi,
-                  uint64_t* ou) {
-    static const char* ops[] = {"normalize3", "cross", "reflect", "refract", "quat_rotate", "quat_inverse", "quat_mul",
-                                "tri_hit", "ray_ctor", "zorder", "to_mat3", "box_hit", "pow", "tri_hit_f", "box_hit_f",
-                                "box_pair", "rcp_cr", "sqrt_cr", "box_from_local", "box_merge", "entity"};
-    // per-op sizes (floats): in0, in1, in2, out_f, out_i, out_u per element
-    static const int sz[][6] = {{3, 0, 0, 3, 0, 0}, {3, 3, 0, 3, 0, 0}, {3, 3, 0, 3, 0, 0}, {3, 3, 2, 3, 1, 0},
-                                {4, 3, 0, 3, 0, 0}, {4, 0, 0, 4, 0, 0}, {4, 4, 0, 4, 0, 0}, {9, 6, 0, 3, 1, 0},
-                                {6, 0, 0, 6, 0, 0}, {3, 0, 0, 0, 0, 1}, {4, 0, 0, 9, 0, 0}, {7, 6, 0, 0, 1, 0},
-                                {1, 1, 0, 1, 0, 0}, {9, 6, 0, 3, 1, 0}, {7, 6, 0, 0, 1, 0}, {14, 6, 0, 0, 2, 0},
-                                {1, 0, 0, 1, 0, 0}, {1, 0, 0, 1, 0, 0}, {7, 7, 0, 6, 1, 0}, {7, 7, 0, 6, 1, 0},
-                                {7, 3, 0, 12, 0, 0}};
-    if (!op || n <= 0) return fail(RT_ERR_ARG, "bad arguments");
-    int k = -1;
-    for (int i = 0; i < (int)(sizeof ops / sizeof *ops); i++) if (!strcmp(op, ops[i])) k = i;
-    if (k < 0) return fail(RT_ERR_ARG, std::string("unknown op ") + op);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(RT_ERR_NODEV, "no HIP device available");
-    HIPCHK(hipSetDevice(g_device));
-    const float* hin[3] = {in0, in1, in2};
-    float* din[3] = {nullptr, nullptr, nullptr};
-    float* dof = nullptr; int* doi = nullptr; unsigned long long* dou = nullptr;
-    for (int i = 0; i < 3; i++)
-        if (sz[k][i]) {
-            if (!hin[i]) return fail(RT_ERR_ARG, "missing input");
-            HIPCHK(hipMalloc((void**)&din[i], (size_t)n * sz[k][i] * 4));
-            HIPCHK(hipMemcpy(din[i], hin[i], (size_t)n * sz[k][i] * 4, hipMemcpyHostToDevice));
-        }
-    if (sz[k][3]) HIPCHK(hipMalloc((void**)&dof, (size_t)n * sz[k][3] * 4));
-    if (sz[k][4]) HIPCHK(hipMalloc((void**)&doi, (size_t)n * sz[k][4] * 4));
-    if (sz[k][5]) HIPCHK(hipMalloc((void**)&dou, (size_t)n * 8));
-    hipLaunchKernelGGL(kat_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, k, n, din[0], din[1], din[2], dof, doi, dou);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipDeviceSynchronize());
-    if (sz[k][3] && of) HIPCHK(hipMemcpy(of, dof, (size_t)n * sz[k][3] * 4, hipMemcpyDeviceToHost));
-    if (sz[k][4] && oi) HIPCHK(hipMemcpy(oi, doi, (size_t)n * sz[k][4] * 4, hipMemcpyDeviceToHost));
-    if (sz[k][5] && ou) HIPCHK(hipMemcpy(ou, dou, (size_t)n * 8, hipMemcpyDeviceToHost));
-    for (auto p : din) if (p) (void)hipFree(p);
-    if (dof) (void)hipFree(dof);
-    if (doi) (void)hipFree(doi);
-    if (dou) (void)hipFree(dou);
-    return RT_OK;
-}
-
-}  // extern "C"
+}  // namespace rtd

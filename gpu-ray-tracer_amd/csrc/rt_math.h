@@ -401,7 +401,8 @@ RT_HD bool pow_pos(float xf, float yf, float& out) {
     return true;
 }
 
-// Host-built record of a triangle for the axis-plane path (rt_kernels.hip, cast_local).
+// Host-built record (rt_runtime.cpp, tri_axis_records) of a triangle for the axis-plane path
+// (rt_kernels.hip, cast_local).
 // code: bits 0-1 axis (3 = general triangle), bit 2 = the next triangle of the mesh has the
 // same axis and plane coordinate (identical t: when no lane accepts this plane crossing, the
 // next one is rejected too), bit 3 = the in-plane reject below is valid for this triangle.

@@ -1,0 +1,1457 @@
+// rt_runtime.cpp — the host runtime of the ray-tracing core: the scene object (rt_internal.h),
+// its upload, the frame slots, the per-frame BVH build and trace launch set-up, and the C ABI
+// (rt_amd.h) except the multi-device entries (rt_multi.cpp) and the copy-engine entries
+// (rt_copy.cpp).  Host code only: kernels are reached through the launch layer of rt_device.h
+// (rt_kernels.hip).  The host float code here (ordered_tree_shape, tri_axis_records, view_of's
+// pruning slack) decides kernel variants and bounds: it is built with the kernels' float rules.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <fstream>
+#include <memory>
+#include <numeric>
+#include <string>
+#include <vector>
+
+#include "rt_internal.h"
+
+using namespace rtm;
+using namespace rtb;
+using namespace rtd;
+using namespace rti;
+using rt::DCamera;
+using rt::DInst;
+using rt::DLight;
+using rt::DMat;
+using rt::DMesh;
+using rt::DTri;
+
+namespace rti {
+thread_local int g_device = 0;
+namespace {
+thread_local std::string g_err;
+}
+int fail(int code, const std::string& msg) { g_err = msg; return code; }
+}  // namespace rti
+
+namespace {
+constexpr int BVH_MAX_LEAVES = 1 << 24;  // padded leaves (int indexing of the 12n-float pair records)
+
+int padded(int n_t) {   // raytracer.cu:79: 1 << ceil(log2(n))
+    if (n_t <= 0) return 0;
+    int n = 1;
+    while (n < n_t) n <<= 1;
+    return n;
+}
+
+int upload_inst4(rt_scene* s);
+int ensure_other_slot(rt_scene* s);
+int mirror_slot_caps(rt_scene* s);
+
+// TriAx records (rt_math.h) of the axis-plane triangle path: axis, plane coordinate,
+// shared-plane flag and the in-plane reject box with its host-checked error bound.
+std::vector<TriAx> tri_axis_records(const rt::Scene& h) {
+    const double u = 0x1p-24;
+    std::vector<TriAx> out(h.d_tris.size());
+    auto c3 = [](V3 v, int a) { return a == 0 ? v.x : a == 1 ? v.y : v.z; };
+    for (size_t i = 0; i < h.d_tris.size(); i++) {
+        const DTri& T = h.d_tris[i];
+        TriAx x{};
+        x.code = 3;
+        int ax = -1, zeros = 0;
+        for (int a = 0; a < 3; a++) {
+            const float c = c3(T.pn, a);
+            if (c == 0.0f) zeros++;                          // +0 or -0
+            else if (c == 1.0f || c == -1.0f) ax = a;
+        }
+        if (zeros == 2 && ax >= 0 && c3(T.b, ax) == c3(T.a, ax) && c3(T.c, ax) == c3(T.a, ax)) {
+            x.code = ax;
+            x.a_ax = c3(T.a, ax);
+            const int au = (ax + 1) % 3, av = (ax + 2) % 3;
+            const V3 P[3] = {T.a, T.b, T.c};
+            double D = 0, lo[2] = {INFINITY, INFINITY}, hi[2] = {-INFINITY, -INFINITY};
+            for (int k = 0; k < 3; k++) {
+                const V3 p = P[k], q = P[(k + 1) % 3];
+                const double dx = (double)p.x - q.x, dy = (double)p.y - q.y, dz = (double)p.z - q.z;
+                D = std::max(D, std::sqrt(dx * dx + dy * dy + dz * dz));
+                const double pc[2] = {c3(p, au), c3(p, av)};
+                for (int j = 0; j < 2; j++) { lo[j] = std::min(lo[j], pc[j]); hi[j] = std::max(hi[j], pc[j]); }
+            }
+            // exact (double) doubled area vs the stored float area
+            const double e1[3] = {(double)T.b.x - T.a.x, (double)T.b.y - T.a.y, (double)T.b.z - T.a.z};
+            const double e2[3] = {(double)T.c.x - T.a.x, (double)T.c.y - T.a.y, (double)T.c.z - T.a.z};
+            const double cx = e1[1] * e2[2] - e1[2] * e2[1], cy = e1[2] * e2[0] - e1[0] * e2[2], cz = e1[0] * e2[1] - e1[1] * e2[0];
+            const double A = std::sqrt(cx * cx + cy * cy + cz * cz);
+            const double m = 1e-4 * D, win = 1e3 * D, off = m;
+            bool ok = A > 0 && D > 0 && std::isfinite(A) && std::isfinite(D) && std::isfinite(win);
+            if (ok) {
+                const double eta = std::fabs((double)T.area - A) / A + 1e-12;
+                auto margin = [&](double e) {
+                    return (e / D) * (1 - 5.6 * u - eta) - (5.6 * u + eta) - 41.8 * u * (D + e + off) * (D + e + off) / A - 1.01e-5;
+                };
+                ok = margin(m) > 0 && margin(win) > 0;
+            }
+            if (ok) {
+                // bounds rounded outwards to float
+                x.ulo = std::nextafter((float)(lo[0] - m), -INFINITY); x.uhi = std::nextafter((float)(hi[0] + m), INFINITY);
+                x.vlo = std::nextafter((float)(lo[1] - m), -INFINITY); x.vhi = std::nextafter((float)(hi[1] + m), INFINITY);
+                x.win = std::nextafter((float)win, 0.0f);
+                x.off = std::nextafter((float)off, 0.0f);
+                x.code |= 8;
+            }
+        }
+        out[i] = x;
+    }
+    // shared plane with the next triangle of the same mesh
+    for (const DMesh& M : h.d_meshes)
+        for (int t = M.tri_begin; t + 1 < M.tri_begin + M.tri_count; t++) {
+            const TriAx &x = out[t], &y = out[t + 1];
+            if ((x.code & 3) != 3 && (x.code & 3) == (y.code & 3)) {
+                uint32_t bx, by;
+                memcpy(&bx, &x.a_ax, 4); memcpy(&by, &y.a_ax, 4);
+                if (bx == by) out[t].code |= 4;
+            }
+        }
+    return out;
+}
+
+// Leaf count and depth (internal nodes on the longest root-leaf path) of the ordered
+// LBVH bvh_build_kernel will build: the same box, Morton and sort arithmetic on the
+// host (RT_HD functions).  The fast traversal's stack holds <= FT_MAX_DEPTH entries.
+constexpr int FT_MAX_DEPTH = 31;
+// Mesh boxes: Trimesh::compute_bounding_box (trimesh.cu:21-32, sequential fit order) and
+// the mesh pose.  They depend only on the immutable mesh data, so they are computed once
+// here; the per-frame build (bvh_build_kernel) redoes everything per instance.
+std::vector<Box> mesh_boxes(const rt::Scene& h) {
+    std::vector<Box> mbox(h.d_meshes.size());
+    for (size_t m = 0; m < h.d_meshes.size(); m++) {
+        Box b; b.nd = 0; b.mn = b.mx = v3(0, 0, 0);
+        const DMesh& mesh = h.d_meshes[m];
+        for (int t = mesh.tri_begin; t < mesh.tri_begin + mesh.tri_count; t++) {
+            fit_vertex(b, h.d_tris[t].a); fit_vertex(b, h.d_tris[t].b); fit_vertex(b, h.d_tris[t].c);
+        }
+        mbox[m] = from_local(b, mesh.pose);
+    }
+    return mbox;
+}
+// n_real and the deepest internal node's depth (root = 1).
+void ordered_tree_shape(const rt::Scene& h, int* n_real, int* depth) {
+    const std::vector<Box> mbox = mesh_boxes(h);
+    std::vector<std::pair<unsigned long long, int>> kv;
+    bool ordered = true;                                      // every real box finite with mn <= mx
+    for (size_t i = 0; i < h.d_insts.size(); i++) {
+        const Box b = from_local(mbox[h.d_insts[i].mesh], h.d_insts[i].pose);
+        if (b.nd) {
+            kv.push_back({z_order(neg(box_center(b))), (int)i});
+            const float c[6] = {b.mn.x, b.mn.y, b.mn.z, b.mx.x, b.mx.y, b.mx.z};
+            for (float x : c) ordered = ordered && std::isfinite(x);
+            ordered = ordered && b.mn.x <= b.mx.x && b.mn.y <= b.mx.y && b.mn.z <= b.mx.z;
+        }
+    }
+    std::stable_sort(kv.begin(), kv.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
+    const int nr = (int)kv.size();
+    *n_real = nr;
+    *depth = 0;
+    // The fast traversal takes every record of the ordered tree as a proper box (no
+    // degenerate / NaN test per child, pair_hit_tt): a pose that makes a box non-finite
+    // leaves the frame to the heap kernels.
+    if (!ordered) { *depth = 1 << 20; return; }
+    if (nr < 2) return;
+    std::vector<unsigned long long> keys(nr);
+    for (int i = 0; i < nr; i++) keys[i] = kv[i].first;
+    std::vector<int> child(2 * (nr - 1));                   // internal children (-1: leaf)
+    for (int i = 0; i < nr - 1; i++) {
+        int first, last, gamma;
+        fnode_split(keys.data(), nr, i, first, last, gamma);
+        child[2 * i] = gamma + 1 == last ? -1 : gamma + 1;
+        child[2 * i + 1] = gamma == first ? -1 : gamma;
+    }
+    std::vector<std::pair<int, int>> todo{{0, 1}};
+    while (!todo.empty()) {
+        const auto [node, d] = todo.back();
+        todo.pop_back();
+        *depth = std::max(*depth, d);
+        if (d > nr) { *depth = 1 << 20; return; }          // malformed: disable the fast tree
+        for (int c = 0; c < 2; c++) if (child[2 * node + c] >= 0) todo.push_back({child[2 * node + c], d + 1});
+    }
+}
+void free_atlas(rt_scene* s);
+int ensure_atlas(rt_scene* s);
+
+// The scene's own stream, created on first use: a caller passing its own streams (frame
+// pipelining) keeps every HIP stream of the process on a hardware queue of its own
+// (GPU_MAX_HW_QUEUES = 4; streams beyond that share queues and serialise).
+hipStream_t sstream(rt_scene* s) {
+    if (!s->stream) (void)hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking);
+    return s->stream;
+}
+
+}  // namespace
+
+int rti::upload(rt_scene* s) {
+    if (s->uploaded) return RT_OK;
+    FrameSlot& f = s->cur();
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(RT_ERR_NODEV, "no HIP device available");
+    s->device = g_device;
+    HIPCHK(hipSetDevice(s->device));
+    hipDeviceProp_t prop;
+    HIPCHK(hipGetDeviceProperties(&prop, s->device));
+    if (std::string(prop.gcnArchName).find("gfx950") == std::string::npos)
+        return fail(RT_ERR_NODEV, std::string("device is ") + prop.gcnArchName + ", this build targets gfx950");
+    for (auto& e : s->ev) HIPCHK(hipEventCreate(&e));
+    const rt::Scene& h = s->h;
+    auto up = [&](auto*& dst, const auto& vec) -> int {
+        using T = typename std::remove_reference<decltype(vec)>::type::value_type;
+        size_t bytes = std::max<size_t>(1, vec.size()) * sizeof(T);
+        HIPCHK(hipMalloc((void**)&dst, bytes));
+        if (!vec.empty()) HIPCHK(hipMemcpy(dst, vec.data(), vec.size() * sizeof(T), hipMemcpyHostToDevice));
+        return RT_OK;
+    };
+    int r;
+    if ((r = up(s->d_tris, h.d_tris)) || (r = up(s->d_meshes, h.d_meshes)) || (r = up(f.d_insts, h.d_insts)) ||
+        (r = up(s->d_mats, h.d_mats)) || (r = up(s->d_lights, h.d_lights)))
+        return r;
+    s->n_leaf = padded((int)h.d_insts.size());
+    if (s->n_leaf > BVH_MAX_LEAVES) return fail(RT_ERR_LIMIT, "more than 2^24 padded instances");
+    s->n_cu = prop.multiProcessorCount;
+    size_t nl = std::max(1, s->n_leaf);
+    HIPCHK(hipMalloc((void**)&f.d_node_pair, 3 * nl * sizeof(float4)));
+    ordered_tree_shape(h, &s->n_real, &s->fdepth);
+    s->shape_gen = s->inst_gen;
+    HIPCHK(hipMalloc((void**)&f.d_fnode, 4 * (size_t)std::max(1, s->n_real - 1) * sizeof(float4)));
+    HIPCHK(hipMalloc((void**)&f.d_leaf, nl * sizeof(int)));
+    HIPCHK(hipMalloc((void**)&f.d_inst4, std::max<size_t>(1, h.d_insts.size()) * sizeof(float4)));
+    HIPCHK(hipMalloc((void**)&f.d_work, WORK_INTS * sizeof(int)));
+    if ((r = upload_inst4(s)) != RT_OK) return r;
+    if ((r = up(s->d_tri_ax, tri_axis_records(h))) != RT_OK) return r;
+    if ((r = up(s->d_mesh_box, mesh_boxes(h))) != RT_OK) return r;
+    HIPCHK(hipMalloc((void**)&f.d_tree, 2 * nl * sizeof(Box)));
+    if (s->n_leaf > BVH_WG_LEAVES) HIPCHK(hipMalloc(&f.d_bscratch, bvh_large_scratch_bytes(s->n_leaf)));
+    HIPCHK(hipMalloc((void**)&s->d_stats, STATS_N * sizeof(unsigned long long)));
+    HIPCHK(hipMalloc((void**)&s->d_canvas, (size_t)h.cam.W * h.cam.H * sizeof(uint32_t)));
+    HIPCHK(hipMalloc((void**)&s->d_dbg, 4096 * sizeof(int)));
+    for (auto& o : s->slots) if (!o.done) HIPCHK(hipEventCreateWithFlags(&o.done, hipEventDisableTiming));
+    f.inst_gen = s->inst_gen;
+    s->uploaded = true;
+    if (s->n_slots > 1) return ensure_other_slot(s);
+    return RT_OK;
+}
+
+namespace {
+
+// compact instance records for the trace kernel: (p, mesh | 0x80000000 when the pose is not identity)
+void fill_inst4(const rt::Scene& h, float4* v) {
+    for (size_t i = 0; i < h.d_insts.size(); i++) {
+        const DInst& d = h.d_insts[i];
+        uint32_t w = (uint32_t)d.mesh | (d.pose.identity ? 0u : 0x80000000u);
+        float fw; memcpy(&fw, &w, 4);
+        v[i] = make_float4(d.pose.p.x, d.pose.p.y, d.pose.p.z, fw);
+    }
+}
+int upload_inst4(rt_scene* s) {
+    std::vector<float4> v(s->h.d_insts.size());
+    fill_inst4(s->h, v.data());
+    if (!v.empty()) HIPCHK(hipMemcpy(s->cur().d_inst4, v.data(), v.size() * sizeof(float4), hipMemcpyHostToDevice));
+    return RT_OK;
+}
+
+// Bring the current slot's instance arrays to the host's generation, stream-ordered on `st`
+// (after the slot's previous frame, which the caller has made `st` wait for).  The pinned
+// staging is rewritten only once the copy that last read it has run (the slot's last frame,
+// recorded after that copy).
+int sync_slot_insts(rt_scene* s, hipStream_t st) {
+    FrameSlot& f = s->cur();
+    if (f.inst_gen == s->inst_gen) return RT_OK;
+    const size_t n = s->h.d_insts.size();
+    if (n) {
+        if (!f.h_insts_pin) {
+            HIPCHK(hipHostMalloc((void**)&f.h_insts_pin, n * sizeof(DInst), hipHostMallocDefault));
+            HIPCHK(hipHostMalloc((void**)&f.h_inst4_pin, n * sizeof(float4), hipHostMallocDefault));
+            int r;
+            if (s->n_slots > 1 && (r = mirror_slot_caps(s)) != RT_OK) return r;
+        } else if (f.pending) {
+            HIPCHK(hipEventSynchronize(f.done));
+        }
+        memcpy(f.h_insts_pin, s->h.d_insts.data(), n * sizeof(DInst));
+        fill_inst4(s->h, f.h_inst4_pin);
+        HIPCHK(hipMemcpyAsync(f.d_insts, f.h_insts_pin, n * sizeof(DInst), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(f.d_inst4, f.h_inst4_pin, n * sizeof(float4), hipMemcpyHostToDevice, st));
+        HIPCHK(hipEventRecord(f.done, st));   // covers the staging until the frame records it again
+        f.pending = true;
+    }
+    f.inst_gen = s->inst_gen;
+    return RT_OK;
+}
+
+// Ordered-LBVH shape (leaf count, depth) for the current host poses: instances that moved
+// change the Morton order and with it the tree depth the fast traversal's stack must hold.
+void refresh_shape(rt_scene* s) {
+    if (s->shape_gen == s->inst_gen) return;
+    int nr = 0;
+    ordered_tree_shape(s->h, &nr, &s->fdepth);
+    s->shape_gen = s->inst_gen;
+}
+
+// Begin a frame on the current slot: `st` waits for the slot's previous frame (all slots'
+// last frames for side entries that do not rotate slots), then the slot's instances are
+// brought up to date.  end_frame records the slot's completion.
+int begin_frame(rt_scene* s, hipStream_t st, bool all_slots) {
+    for (int i = 0; i < rt_scene::MAX_SLOTS; i++)
+        if (s->slots[i].pending && (all_slots || i == s->cur_slot)) HIPCHK(hipStreamWaitEvent(st, s->slots[i].done, 0));
+    refresh_shape(s);
+    return sync_slot_insts(s, st);
+}
+int end_frame(rt_scene* s, hipStream_t st) {
+    HIPCHK(hipEventRecord(s->cur().done, st));
+    s->cur().pending = true;
+    return RT_OK;
+}
+
+// Buffers of the frame slots other than the current one (sizes as in upload), slot events.
+int ensure_other_slot(rt_scene* s) {
+    const size_t nl = std::max(1, s->n_leaf);
+    for (int i = 0; i < s->n_slots; i++) {
+        FrameSlot& o = s->slots[i];
+        if (i == s->cur_slot || o.d_work) continue;
+        HIPCHK(hipMalloc((void**)&o.d_node_pair, 3 * nl * sizeof(float4)));
+        HIPCHK(hipMalloc((void**)&o.d_fnode, 4 * (size_t)std::max(1, s->n_real - 1) * sizeof(float4)));
+        HIPCHK(hipMalloc((void**)&o.d_leaf, nl * sizeof(int)));
+        HIPCHK(hipMalloc((void**)&o.d_tree, 2 * nl * sizeof(Box)));
+        HIPCHK(hipMalloc((void**)&o.d_work, WORK_INTS * sizeof(int)));
+        HIPCHK(hipMalloc((void**)&o.d_insts, std::max<size_t>(1, s->h.d_insts.size()) * sizeof(DInst)));
+        HIPCHK(hipMalloc((void**)&o.d_inst4, std::max<size_t>(1, s->h.d_insts.size()) * sizeof(float4)));
+        // the grid-wide build's sort buffers now, not at the slot's first frame inside a pipeline
+        if (s->n_leaf > BVH_WG_LEAVES && !o.d_bscratch) HIPCHK(hipMalloc(&o.d_bscratch, bvh_large_scratch_bytes(s->n_leaf)));
+        // the current poses now (blocking copies, here rather than at the slot's first frame: an
+        // asynchronous copy on a frame's stream may start a new SDMA engine, ~7 ms of host time
+        // the first time, profiles/r06/rblog/); later pose changes reach the slot through
+        // sync_slot_insts, stream-ordered
+        const size_t n = s->h.d_insts.size();
+        if (n) {
+            std::vector<float4> v4(n);
+            fill_inst4(s->h, v4.data());
+            HIPCHK(hipMemcpy(o.d_insts, s->h.d_insts.data(), n * sizeof(DInst), hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(o.d_inst4, v4.data(), n * sizeof(float4), hipMemcpyHostToDevice));
+        }
+        o.inst_gen = s->inst_gen;
+        o.work_zeroed = false; o.bvh_valid = false;
+    }
+    return mirror_slot_caps(s);                              // the current slot's grown buffers too
+}
+
+// Capacities of the per-frame layout buffers for n_groups pixel groups.
+struct Layout { int flags, sky_blocks, live_q, live; };
+Layout layout_of(int n_groups) {
+    Layout l;
+    l.sky_blocks = (n_groups + 63) / 64;                       // sky_kernel's blocks, 64 groups each
+    l.flags = (std::max(n_groups, 1024) + 3) & ~3;             // sky and history flags: whole dwords (scalar loads)
+    l.live_q = (l.sky_blocks + NQ - 1) / NQ * 64;                  // most groups of the blocks b = q mod NQ
+    l.live = l.live_q * NQ + n_groups;                         // + the heavy live list (hist = 2)
+    return l;
+}
+
+// Slot f's sky flags, live lists and scheduling history brought to at least the given
+// capacities (0: that buffer is not wanted).  `synced` (another slot's buffers, which a frame in
+// flight may be using): the device is waited for once per call, *synced, before a smaller
+// buffer is freed.  A regrown history is reset at the slot's next use (the key).  *grew
+// (optional) is set when a buffer grew.
+int grow_slot(FrameSlot& f, int gsky_cap, int live_cap, int hist_cap, bool* synced, bool* grew) {
+    auto quiesce = [&](const void* old) -> hipError_t {
+        if (!old || !synced || *synced) return hipSuccess;
+        *synced = true;
+        return hipDeviceSynchronize();
+    };
+    if (gsky_cap > f.gsky_cap) {
+        HIPCHK(quiesce(f.d_gsky));
+        dfree(f.d_gsky);
+        HIPCHK(hipMalloc((void**)&f.d_gsky, gsky_cap));
+        f.gsky_cap = gsky_cap; if (grew) *grew = true;
+    }
+    if (live_cap > f.live_cap) {
+        HIPCHK(quiesce(f.d_live));
+        dfree(f.d_live);
+        HIPCHK(hipMalloc((void**)&f.d_live, (size_t)live_cap * sizeof(int)));
+        f.live_cap = live_cap; if (grew) *grew = true;
+    }
+    if (hist_cap > f.hist_cap) {
+        HIPCHK(quiesce(f.d_hctl));
+        for (int p = 0; p < 2; p++) { dfree(f.d_hlist[p]); dfree(f.d_hflag[p]); }
+        dfree(f.d_hctl);
+        for (int p = 0; p < 2; p++) {
+            HIPCHK(hipMalloc((void**)&f.d_hlist[p], (size_t)hist_cap * sizeof(int)));
+            HIPCHK(hipMalloc((void**)&f.d_hflag[p], hist_cap));
+        }
+        HIPCHK(hipMalloc((void**)&f.d_hctl, 4 * sizeof(unsigned long long)));
+        f.hist_cap = hist_cap;
+        f.hist_key[0] = -1;
+        if (grew) *grew = true;
+    }
+    return RT_OK;
+}
+
+// The current slot grew a per-frame buffer (sky flags, live lists, history, pinned instance
+// staging) at its first frame of a new layout: give every other allocated slot the same
+// capacity now, so that their first frames -- possibly inside a steady pipeline -- allocate
+// nothing (an allocation there cost the first 8 frames of a run up to ~1 ms: hipFree waits for
+// the device, pinned allocations take milliseconds).  The slots' contents are reset on first
+// use as before (history key, instance generation).  Only growth reaches here: waiting for the
+// device before freeing a smaller buffer is a one-time cost per layout.
+int mirror_slot_caps(rt_scene* s) {
+    const FrameSlot& c = s->cur();
+    const size_t n = s->h.d_insts.size();
+    bool synced = false;
+    for (int i = 0; i < s->n_slots; i++) {
+        FrameSlot& o = s->slots[i];
+        if (i == s->cur_slot || !o.d_work) continue;          // itself; not allocated (ensure_other_slot)
+        int r;
+        if ((r = grow_slot(o, c.gsky_cap, c.live_cap, c.hist_cap, &synced, nullptr)) != RT_OK) return r;
+        if (c.h_insts_pin && !o.h_insts_pin && n) {
+            HIPCHK(hipHostMalloc((void**)&o.h_insts_pin, n * sizeof(DInst), hipHostMallocDefault));
+            HIPCHK(hipHostMalloc((void**)&o.h_inst4_pin, n * sizeof(float4), hipHostMallocDefault));
+        }
+    }
+    return RT_OK;
+}
+
+// The current slot's layout buffers for n_groups pixel groups (sky: flags and live lists; hist:
+// the scheduling history), and on growth every other allocated slot's (mirror_slot_caps).
+int ensure_layout(rt_scene* s, int n_groups, bool sky, bool hist) {
+    const Layout l = layout_of(n_groups);
+    bool grew = false;
+    int r = grow_slot(s->cur(), sky ? l.flags : 0, sky ? l.live : 0, hist ? l.flags : 0, nullptr, &grew);
+    if (r != RT_OK) return r;
+    return (grew && s->n_slots > 1) ? mirror_slot_caps(s) : RT_OK;
+}
+
+// Atlas -> float4 texels (byte / 255, as assets.cc:61-81) in HBM; the reference's CUDA
+// texture (gputils TextureBuffer4D, alloc.h:24-80: point sampling, clamp) is sampled
+// explicitly by hit_kd, since gfx950 has no texture units.
+void free_atlas(rt_scene* s) {
+    if (s->d_atlas) (void)hipFree(s->d_atlas);
+    s->d_atlas = nullptr;
+}
+int ensure_atlas(rt_scene* s) {
+    const rt::Scene& h = s->h;
+    if (h.atlas_rgba.empty()) return fail(RT_ERR_STATE, "textured rendering needs an atlas: rt_scene_load_atlas / rt_scene_set_atlas");
+    if (!s->atlas_dirty && s->d_atlas) return RT_OK;
+    free_atlas(s);
+    const size_t n = (size_t)h.atlas_w * h.atlas_h;
+    std::vector<float4> texels(n);
+    for (size_t i = 0; i < n; i++)
+        texels[i] = make_float4((float)h.atlas_rgba[4 * i] / 255, (float)h.atlas_rgba[4 * i + 1] / 255,
+                                (float)h.atlas_rgba[4 * i + 2] / 255, (float)h.atlas_rgba[4 * i + 3] / 255);
+    HIPCHK(hipMalloc((void**)&s->d_atlas, n * sizeof(float4)));
+    HIPCHK(hipMemcpy(s->d_atlas, texels.data(), n * sizeof(float4), hipMemcpyHostToDevice));
+    s->atlas_dirty = false;
+    return RT_OK;
+}
+
+// A factor coprime with the queue length, so t -> t * f mod len is a permutation
+// (checked with gcd; f near len * 0.618 spreads consecutive tickets across the image).
+int ticket_scramble(int len) {
+    if (len <= 2) return 1;
+    int f = (int)(len * 0.6180339887) | 1;
+    while (std::gcd(f % len, len) != 1) f++;
+    return f % len;
+}
+
+// (Re)allocate / reset the current slot's scheduling history when the launch layout changes.
+int ensure_history(rt_scene* s, int n_groups, const long long* key, hipStream_t st) {
+    int r;
+    if ((r = ensure_layout(s, n_groups, false, true)) != RT_OK) return r;
+    FrameSlot& f = s->cur();
+    if (memcmp(key, f.hist_key, sizeof f.hist_key) != 0) {
+        for (int p = 0; p < 2; p++) HIPCHK(hipMemsetAsync(f.d_hflag[p], 0, f.hist_cap, st));
+        HIPCHK(hipMemsetAsync(f.d_hctl, 0, 4 * sizeof(unsigned long long), st));
+        memcpy(f.hist_key, key, sizeof f.hist_key);
+        f.hist_parity = 0;
+    }
+    return RT_OK;
+}
+
+// Per-frame buffers (sky flags, live lists, scheduling history) sized for a layout of n_groups
+// pixel groups in the current slot and every allocated one, ahead of the first frame that needs
+// them (warm_scene: the whole frame at 2-8 pixels per wave, the layouts of spp 8-32).  Contents
+// are reset at first use as before (the history key); only capacity is reserved here.
+int reserve_layout(rt_scene* s, int n_groups) { return ensure_layout(s, n_groups, true, true); }
+
+int ensure_spp(rt_scene* s, int spp) {
+    if (spp <= s->spp_cap) return RT_OK;
+    int cap = std::max(spp, 64);
+    std::vector<float2> tab(cap);
+    for (int k = 0; k < cap; k++) rt::spp_offset(k, &tab[k].x, &tab[k].y);
+    dfree(s->d_spp);
+    HIPCHK(hipMalloc((void**)&s->d_spp, cap * sizeof(float2)));
+    HIPCHK(hipMemcpy(s->d_spp, tab.data(), cap * sizeof(float2), hipMemcpyHostToDevice));
+    s->spp_cap = cap;
+    return RT_OK;
+}
+
+int build_bvh(rt_scene* s, hipStream_t st, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr) {
+    FrameSlot& f = s->cur();
+    if (s->n_leaf == 0) {
+        if (e0) { HIPCHK(hipEventRecord(e0, st)); HIPCHK(hipEventRecord(e1, st)); }
+        f.bvh_valid = true;
+        return RT_OK;
+    }
+    BvhArgs A;
+    A.insts = f.d_insts; A.n_inst = (int)s->h.d_insts.size();
+    A.mesh_box = s->d_mesh_box; A.n = s->n_leaf;
+    A.tree = f.d_tree;
+    A.node_pair = reinterpret_cast<float*>(f.d_node_pair); A.leaf_inst = f.d_leaf;
+    A.fnode = f.d_fnode; A.n_real = s->n_real;
+    A.work = f.d_work; A.n_work = WORK_INTS;
+    // the slot the next fast frame records its heavy list into (launch_trace skips its memset)
+    A.hctl = f.d_hctl ? f.d_hctl + 2 * (1 - f.hist_parity) : nullptr;
+    f.hctl_zeroed = f.d_hctl ? 1 - f.hist_parity : -1;
+    if (A.n > BVH_WG_LEAVES) {                                // above one workgroup's LDS: the grid-wide build
+        if (!f.d_bscratch) HIPCHK(hipMalloc(&f.d_bscratch, bvh_large_scratch_bytes(A.n)));
+        HIPCHK(bvh_build_large(A, f.d_bscratch, st, e0, e1));
+    } else {
+        const bool lds_tree = bvh_lds_bytes(A.n, true) <= 160 * 1024;       // n <= 2048
+        const size_t lds = bvh_lds_bytes(A.n, lds_tree);
+        if (lds > 160 * 1024) return fail(RT_ERR_LIMIT, "BVH build needs more LDS than one CU has");
+        HIPCHK(launch_bvh_build(A, lds_tree, lds, st, e0, e1));
+        HIPCHK(hipGetLastError());
+    }
+    f.bvh_valid = true;
+    f.work_zeroed = true;
+    return RT_OK;
+}
+
+SceneView view_of(const rt_scene* s, bool use_bvh) {
+    const FrameSlot& f = s->cur();
+    SceneView v;
+    v.tris = s->d_tris; v.meshes = s->d_meshes; v.insts = f.d_insts; v.mats = s->d_mats; v.lights = s->d_lights;
+    v.node_pair = f.d_node_pair; v.leaf_inst = f.d_leaf;
+    v.fnode = f.d_fnode; v.n_real = s->n_real;
+    v.ftree = (s->n_real >= 2 && s->fdepth <= FT_MAX_DEPTH) ? 1 : 0; v.inst4 = f.d_inst4;
+    v.n_leaf = s->n_leaf; v.n_inst = (int)s->h.d_insts.size();
+    v.n_lights = (int)s->h.d_lights.size(); v.use_bvh = use_bvh ? 1 : 0;
+    v.n_mats = (int)s->h.d_mats.size(); v.n_tris = (int)s->h.d_tris.size(); v.n_meshes = (int)s->h.d_meshes.size();
+    v.ident_all = 1;
+    for (const auto& i : s->h.d_insts) v.ident_all &= i.pose.identity ? 1 : 0;
+    for (const auto& m : s->h.d_meshes) v.ident_all &= m.pose.identity ? 1 : 0;
+    // Distance pruning (closest_hit): boxes provably contain their triangles only for
+    // pure translations with zero mesh offsets (the BVH boxes ignore the mesh pose,
+    // raytracer.cu:54-89).  Slack: 1e-4 x mesh size + 2^-14 x scene radius.
+    bool prune_ok = v.ident_all != 0;
+    float vmax = 0.0f, pmax = 0.0f;
+    for (const auto& m : s->h.d_meshes) prune_ok = prune_ok && m.pose.p.x == 0 && m.pose.p.y == 0 && m.pose.p.z == 0;
+    auto amax = [](rtm::V3 a) { return std::max(std::fabs(a.x), std::max(std::fabs(a.y), std::fabs(a.z))); };
+    for (const auto& t : s->h.d_tris) vmax = std::max(vmax, std::max(amax(t.a), std::max(amax(t.b), amax(t.c))));
+    for (const auto& i : s->h.d_insts) pmax = std::max(pmax, amax(i.pose.p));
+    const float radius = pmax + vmax + amax(s->h.d_cam.pos) + 1.0f;
+    prune_ok = prune_ok && std::isfinite(radius);
+    v.prune_abs = prune_ok ? 4e-4f * vmax + 0x1p-14f * radius : -1.0f;
+    v.tri_ax = (v.ident_all && !s->h.d_tris.empty()) ? s->d_tri_ax : nullptr;
+    return v;
+}
+
+bool opaque_scene(const rt_scene* s) {
+    for (const DMat& m : s->h.d_mats) if (m.refractive) return false;
+    return true;
+}
+
+int launch_trace(rt_scene* s, const rt_render_opts& o, hipStream_t st, uint32_t* rgba, int* dbg, int dbg_x, int dbg_y,
+                 bool want_stats, int occl_force = -1, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr,
+                 bool prof = false, unsigned* gdur = nullptr, int* geo = nullptr) {
+    TraceParams P{};
+    P.gdur = gdur;
+    FrameSlot& f = s->cur();
+    const rt::Scene& h = s->h;
+    P.cam = h.d_cam; P.dist_atten = h.dist_atten; P.ambience = h.ambience;
+    P.W = h.cam.W; P.H = h.cam.H; P.row0 = o.row0; P.row_step = o.row_step;
+    P.n_rows = (P.H - o.row0 + o.row_step - 1) / o.row_step;
+    if (P.n_rows <= 0) {
+        if (e0) { HIPCHK(hipEventRecord(e0, st)); HIPCHK(hipEventRecord(e1, st)); }
+        return RT_OK;
+    }
+    P.compact = o.compact; P.spp = o.spp; P.depth = h.depth;
+    P.spp_recip = (o.spp & (o.spp - 1)) == 0 ? 1.0f / (float)o.spp : 0.0f;
+    P.spp_off = s->d_spp;
+    P.rgba = rgba; P.radiance = reinterpret_cast<float4*>(o.radiance); P.hit_inst = o.hit_inst; P.hit_tri = o.hit_tri;
+    P.stats = (want_stats || prof) ? s->d_stats : nullptr; P.dbg_log = dbg; P.dbg_x = dbg_x; P.dbg_y = dbg_y;
+    if (o.textures) {
+        int r;
+        if ((r = ensure_atlas(s)) != RT_OK) return r;
+        P.atlas = s->d_atlas; P.atlas_w = s->h.atlas_w; P.atlas_h = s->h.atlas_h;
+    }
+    SceneView S = view_of(s, o.use_bvh != 0);
+    // sample-parallel mapping: L lanes per pixel (one sample each per round), 64/L pixels per wave
+    P.lanes_per_px = std::min(o.spp, 64);
+    P.px_per_wave = 64 / P.lanes_per_px;
+    int gw = 1;
+    if ((P.px_per_wave & (P.px_per_wave - 1)) == 0) { while (gw * gw < P.px_per_wave) gw <<= 1; }
+    else gw = P.px_per_wave;
+    // Row slices with rows >= 8 frame rows apart (N >= 8 ranks): a 2-row group would pair
+    // rows that far apart, so groups are one row (8 x 1 at 8 spp).  Measured with four frames
+    // in flight: 8-way slice 0.234 -> 0.229 ms; whole frames and 2-way slices keep 4 x 2
+    // (8 x 1 there: +3.4% / +2%; profiles/r01/ab_group_shape_v31.log).
+    if (o.row_step >= 8) gw = P.px_per_wave;
+    P.gw = gw; P.gh = P.px_per_wave / gw;
+    auto log2_exact = [](int v) { int k = 0; while ((1 << k) < v) k++; return (1 << k) == v ? k : -1; };
+    P.l_shift = log2_exact(P.lanes_per_px); P.gw_shift = log2_exact(P.gw);
+    P.n_gx = (P.W + P.gw - 1) / P.gw;
+    P.n_groups = P.n_gx * ((P.n_rows + P.gh - 1) / P.gh);
+    if (geo) { geo[0] = P.n_groups; geo[1] = P.gw; geo[2] = P.gh; geo[3] = P.n_gx; }
+    P.scramble = ticket_scramble((P.n_groups + NQ - 1) / NQ);
+    P.scramble_small = (unsigned long long)((P.n_groups + NQ - 1) / NQ + TPC) * (unsigned long long)P.scramble < (1ull << 32);
+    P.div_ngx = udiv_make((unsigned)P.n_gx);
+    P.div_perq = udiv_make((unsigned)((P.n_groups + NQ - 1) / NQ));
+    P.work = f.d_work; P.tpc = TPC;
+    {   // unlit skip (trace_sample, ST_LIGHT): every incoming light must be >= +0 and finite
+        bool ok = !want_stats && !dbg;                        // (the PROF variant profiles the fast frame: on)
+        auto pos0 = [](float v) { return std::isfinite(v) && !std::signbit(v); };
+        for (const DLight& l : h.d_lights) ok = ok && pos0(l.col.x) && pos0(l.col.y) && pos0(l.col.z) && pos0(l.col.w);
+        for (const DMat& m : h.d_mats)
+            ok = ok && pos0(m.Kt.x) && pos0(m.Kt.y) && pos0(m.Kt.z) && pos0(m.Kt.w) && m.Kt.x <= 1.0f && m.Kt.y <= 1.0f &&
+                 m.Kt.z <= 1.0f && m.Kt.w <= 1.0f;
+        bool start_ok = true;                                  // no -0 channel in Ke + Ka * ambience (org_light)
+        for (const DMat& m : h.d_mats) {
+            const V4 o = m.Ke + m.Ka * h.ambience;
+            for (float v : {o.x, o.y, o.z, o.w}) start_ok = start_ok && !(v == 0.0f && std::signbit(v));
+        }
+        P.unlit_skip = ok ? (start_ok ? 2 : 1) : 0;
+    }
+    P.occl_exit = (opaque_scene(s) && (occl_force == 1 || (occl_force < 0 && !want_stats))) ? 1 : 0;
+    if (!f.work_zeroed) HIPCHK(hipMemsetAsync(f.d_work, 0, WORK_INTS * sizeof(int), st));
+    // suspended frames needed (<= MAX_FRAMES - 1); none without a refractive material, where a
+    // reflection child replaces its parent (trace_sample, F_REFLECT)
+    // (NS = 0 kernels assume that: a depth-0 scene with refraction takes the NS = 2 bucket)
+    const int ns = opaque_scene(s) ? 0 : std::max(h.depth, 1);
+    const TraceVariant V = choose_trace_variant(S, o.spp, o.textures != 0, want_stats, prof, ns);
+    const int per_cu = V.per_cu;
+    const int waves_needed = P.n_groups;
+    // Frames in flight: a launch issued while the scene's previous frame is still running takes
+    // half the CUs.  A persistent block holds its CU (the LDS image) until its slowest wave
+    // ends; fewer blocks, each running twice the groups, leave fewer CUs held by one wave's last
+    // group, and two frames' blocks still cover the GPU.  Measured with four in flight
+    // (tools/pipe_slices.py, per-rank ms per frame at N = 1/2/4/8, same box): 0.655-0.665 /
+    // 0.374 / 0.226 / 0.156-0.157 with every CU, 0.646-0.654 / 0.347-0.354 / 0.200-0.205 /
+    // 0.137-0.140 with half; 3/8, 5/8 and 3/4 of the CUs in between (profiles/r03/ab_grid/).
+    // A frame issued alone (no other frame running) keeps every CU.  Requiring two or three
+    // running frames instead of one measured the same (profiles/r03/ab_grid/grid2.log).  A
+    // pipeline that copies every frame to the host measured 12% slower this way, with the copy
+    // anywhere (render stream, copy stream, high priority, fewer blit workgroups) and with the
+    // optional second half of the grid gated on later frames being queued
+    // (profiles/r03/ab_grid/readback.log): such callers set RT_OVERLAP_FULL.
+    int cap = s->n_cu * per_cu;
+    // another frame of the scene still in flight (any slot count, any overlap policy): the heavy
+    // list's static dealing below is for frames whose blocks all start at once
+    bool other_running = false;
+    for (int i = 1; i < s->n_slots && !other_running; i++) {
+        const int sl = (s->cur_slot + s->n_slots - i) % s->n_slots;
+        other_running = s->slots[sl].pending && hipEventQuery(s->slots[sl].done) == hipErrorNotReady;
+    }
+    if (s->n_slots >= 4 && s->overlap != RT_OVERLAP_FULL) {
+        const bool running = s->overlap == RT_OVERLAP_STREAM || other_running;   // or a stream
+        // Small frames (row slices of N >= 4 ranks: under ~48 groups per wave on half the CUs)
+        // take a quarter: four frames' blocks share the GPU, each block runs twice the groups,
+        // so its LDS staging and its slowest wave's tail weigh half as much.  Measured per-rank
+        // ms per frame, 60-frame streams, same box (profiles/r04/grid_div.log): N = 8 0.112 ->
+        // 0.101, N = 4 0.175 -> 0.171; whole frames unchanged by it (0.597 / 0.599), kept at half.
+        const long long half_waves = (long long)(cap / 2) * (TRACE_BLOCK_P / 64);
+        // (Not with virtual ranks, several slices of one frame per device from one scene: those
+        // slices share frame slots, and a quarter measured slower there: --gpus 1 --ranks 8 per
+        // slice 0.153 -> 0.173 ms, profiles/r04/grid_div.log.)
+        const int div = ((long long)P.n_groups < RT_SMALL_FRAME_GPW * half_waves && s->ranks_per_device == 1) ? 4 : 2;
+        if (running) cap = std::max(1, cap / div);
+    }
+    int blocks = std::min(cap, (waves_needed + TRACE_BLOCK_P / 64 - 1) / (TRACE_BLOCK_P / 64));
+    blocks = std::max(blocks, 1);
+    P.grid_waves = blocks * (TRACE_BLOCK_P / 64);              // the launch below: dim3(blocks)
+    // every block starts at once: a full grid and no other frame of the scene running (RT_OVERLAP_FULL
+    // and 2-3 frame slots keep the full grid for overlapping frames; those frames keep the counter)
+    P.heavy_static = (blocks == s->n_cu * per_cu && !other_running) ? 1 : 0;
+    P.heavy_cap = std::max(2 * blocks * (TRACE_BLOCK_P / 64), P.n_groups / 4);   // a bound, not a target
+    // longest-first history (fast frames): valid while the launch layout is unchanged
+    // Only where a wave runs few groups (1080p 8-way row slices: ~8 per wave): with more (63
+    // for a whole 1080p frame, 16 for a 4-way slice) the dynamic queues already balance the
+    // frame and the two clock reads per group cost as much as the shorter tail saves or more
+    // (measured, four frames in flight, ms per frame with / without: whole frame 0.919 / 0.914,
+    // 4-way 0.360 / 0.360, 8-way 0.179-0.186 / 0.200-0.204; profiles/r02/hist_policy.log).
+    P.hist = 0;
+    const long long waves = (long long)blocks * (TRACE_BLOCK_P / 64);
+    const bool sky = V.sky;                                    // sky pre-pass (choose_trace_variant)
+    // Heavy-first by work (hist = 2) where groups per wave are many: a group whose samples took
+    // >= heavy_q wave queries (mirror pixels: primary, shadow and reflection chains) is flagged,
+    // and the next frame of the slot runs the flagged groups first off a heavy live list the sky
+    // pre-pass builds.  No clock reads (the timed history's cost, item 17), one byte store per
+    // heavy group.  RT_HEAVY_Q (environment) sets heavy_q; 0 turns it off.
+    // The mode must not depend on the grid (half or whole, frames in flight or alone): the two
+    // modes' flags mean different things (hist = 1 flags only the groups on its heavy list and
+    // skips them in the normal queues; hist = 2 flags by work and lists nothing), so the history
+    // key includes the mode and a change of mode resets the flags.
+    static const int heavy_q = [] { const char* e = getenv("RT_HEAVY_Q"); return e ? atoi(e) : RT_HEAVY_Q_DEFAULT; }();
+    const long long full_waves = (long long)s->n_cu * per_cu * (TRACE_BLOCK_P / 64);
+    const bool hist2 = !want_stats && !dbg && sky && heavy_q > 0;
+    const bool hist1 = !hist2 && !want_stats && !dbg && (prof || (long long)P.n_groups <= RT_HIST_GROUPS_PER_WAVE * full_waves);
+    (void)waves;
+    if (hist1 || hist2) {
+        const long long key[8] = {P.W, P.H, P.row0, P.row_step, P.n_rows, P.spp, P.n_groups,
+                                  (long long)o.textures | (hist2 ? 2 : 1) << 8};
+        int r;
+        if ((r = ensure_history(s, P.n_groups, key, st)) != RT_OK) return r;
+        const int prev = f.hist_parity, next = 1 - prev;
+        P.hist = hist1 ? 1 : 2;
+        P.heavy_q = heavy_q;
+        P.hl_prev = f.d_hlist[prev]; P.hl_next = f.d_hlist[next];
+        P.hf_prev = f.d_hflag[prev]; P.hf_next = f.d_hflag[next];
+        P.hctl_prev = f.d_hctl + 2 * prev; P.hctl_next = f.d_hctl + 2 * next;
+        if (hist1 && f.hctl_zeroed != next) HIPCHK(hipMemsetAsync(f.d_hctl + 2 * next, 0, 2 * sizeof(unsigned long long), st));
+        f.hist_parity = next;
+    }
+    f.work_zeroed = false;                                    // this launch consumes the counters
+    f.hctl_zeroed = -1;
+    if (sky) {
+        int r;
+        if ((r = ensure_layout(s, P.n_groups, true, false)) != RT_OK) return r;
+        const Layout l = layout_of(P.n_groups);
+        P.gsky = f.d_gsky;
+        P.live = f.d_live; P.live_cap = l.live_q;
+        P.tpc = (V.part_k && P.lanes_per_px == 64) ? RT_TPC_WIDE : RT_TPC_LIVE;
+        // (brute-force frames: the grown boxes' slack)
+        HIPCHK(launch_sky(V.sky_brute, l.sky_blocks, P, S, f.d_gsky, f.d_live, s->d_mesh_box, S.prune_abs, 0x1p-12f, st, e0));
+    }
+    HIPCHK(launch_trace_kernel(V, blocks, P, S, st, sky ? nullptr : e0, e1));
+    HIPCHK(hipGetLastError());
+    return RT_OK;
+}
+
+rt::Material mat_from(const float* m) {
+    rt::Material r;
+    r.Ke = v4(m[0], m[1], m[2], m[3]); r.Ka = v4(m[4], m[5], m[6], m[7]); r.Kd = v4(m[8], m[9], m[10], m[11]);
+    r.Ks = v4(m[12], m[13], m[14], m[15]); r.Kt = v4(m[16], m[17], m[18], m[19]); r.Kr = v4(m[20], m[21], m[22], m[23]);
+    r.alpha = m[24]; r.eta = m[25];
+    return r;
+}
+
+// procedural::gpu::generate / SceneBuilder::build_gpu_scene put the scene on the device when it
+// is made (cube_world.cc:195-207, scene_builder.cu:29-81); the first update_scene then only
+// renders.  Here the upload is lazy (host-only scenes must load without a GPU), so a finished
+// scene on a machine with a gfx950 device is uploaded at once and one untimed 1-spp frame is
+// rendered into the device canvas: the code object, the scene's stream and the frame layout's
+// buffers (sky flags, live lists, scheduling history) are then in place before the caller's
+// first frame.  Without a usable device nothing happens (render calls report RT_ERR_NODEV as
+// before); a failure here is left for the first render to report.  RT_NO_WARM=1 turns it off.
+int warm_scene(rt_scene* s) {
+    static const bool off = [] { const char* e = getenv("RT_NO_WARM"); return e && atoi(e) != 0; }();
+    int n = 0;
+    if (off || hipGetDeviceCount(&n) != hipSuccess || n <= 0) { (void)hipGetLastError(); return RT_OK; }
+    const std::string saved = g_err;
+    // update_scene's own path: a 1-spp frame and its copy into the pinned canvas (the copy starts
+    // the copy engine's queue for device-to-host transfers, ~7 ms the first time)
+    if (s->h.cam.W > 0 && s->h.cam.H > 0 && rt_update_scene(s, 16, 1) != RT_OK) {
+        g_err = saved;                                    // left for the caller's first render to report
+        (void)hipGetLastError();
+        return RT_OK;
+    }
+    // capacity for the whole frame at 8 pixels per wave (4 x 2 groups: 8-32 spp, the bench's layout)
+    const long long groups = (long long)((s->h.cam.W + 3) / 4) * ((s->h.cam.H + 1) / 2);
+    if (groups < (1ll << 26) && reserve_layout(s, (int)groups) != RT_OK) { g_err = saved; (void)hipGetLastError(); }
+    return RT_OK;
+}
+
+}  // namespace
+
+void rti::invalidate(rt_scene* s) {
+    for (auto& f : s->slots) f.bvh_valid = false;
+}
+
+rt_scene::~rt_scene() {
+    free_multi(this);
+    if (uploaded) (void)hipSetDevice(device);
+    free_atlas(this);
+    dfree(d_tris); dfree(d_meshes); dfree(d_mats); dfree(d_lights); dfree(d_tri_ax);
+    dfree(d_mesh_box); dfree(d_spp); dfree(d_stats); dfree(d_canvas); dfree(d_dbg);
+    for (auto& p : d_out) dfree(p);
+    for (auto& e : ev) if (e) (void)hipEventDestroy(e);
+    for (auto& e : tev) (void)hipEventDestroy(e);
+    for (auto& f : slots) f.release();
+    if (stream) (void)hipStreamDestroy(stream);
+}
+
+extern "C" {
+
+int rt_abi_version(void) { return RT_ABI_VERSION; }
+const char* rt_last_error(void) { return g_err.c_str(); }
+
+int rt_device_count(int* count) {
+    if (!count) return fail(RT_ERR_ARG, "null count");
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess) n = 0;
+    *count = n;
+    return RT_OK;
+}
+
+int rt_set_device(int device) {
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return fail(RT_ERR_NODEV, "no HIP device available");
+    if (device < 0 || device >= n) return fail(RT_ERR_ARG, "device index out of range");
+    g_device = device;
+    HIPCHK(hipSetDevice(device));
+    return RT_OK;
+}
+
+int rt_spp_offset(int k, float* dx, float* dy) {
+    if (k < 0 || !dx || !dy) return fail(RT_ERR_ARG, "bad arguments");
+    rt::spp_offset(k, dx, dy);
+    return RT_OK;
+}
+
+int rt_scene_load_json(const char* path, int width, int height, rt_scene** out) {
+    if (!path || !out) return fail(RT_ERR_ARG, "null argument");
+    std::unique_ptr<rt_scene> s(new rt_scene);
+    std::string err;
+    int r = rt::load_cube_world(path, width, height, &s->h, &err);
+    if (r == -2) return fail(RT_ERR_IO, err);
+    if (r != 0) return fail(RT_ERR_PARSE, err);
+    s->finished = true;
+    s->canvas.assign((size_t)s->h.cam.W * s->h.cam.H, 0u);
+    (void)warm_scene(s.get());
+    *out = s.release();
+    return RT_OK;
+}
+
+int rt_scene_create(const char* atlas, rt_scene** out) {
+    if (!out) return fail(RT_ERR_ARG, "null argument");
+    rt_scene* s = new rt_scene;
+    s->h.atlas = atlas ? atlas : "";
+    *out = s;
+    return RT_OK;
+}
+
+int rt_scene_free(rt_scene* s) { delete s; return RT_OK; }
+
+int rt_builder_add_vertex(rt_scene* s, float x, float y, float z, int* idx) {
+    CHECK_BUILDING(s);
+    int i = s->h.add_vertex(v3(x, y, z));
+    if (idx) *idx = i;
+    return RT_OK;
+}
+int rt_builder_create_mesh(rt_scene* s, const float* pos, const float* q, int* mesh) {
+    CHECK_BUILDING(s);
+    int m = s->h.create_mesh(pos ? v3(pos[0], pos[1], pos[2]) : v3(0, 0, 0), q ? Q{q[0], q[1], q[2], q[3]} : Q{0, 0, 0, 1});
+    if (mesh) *mesh = m;
+    return RT_OK;
+}
+int rt_builder_add_triangle(rt_scene* s, int mesh, int i0, int i1, int i2, const float* mat) {
+    CHECK_BUILDING(s);
+    if (!mat) return fail(RT_ERR_ARG, "null material");
+    if (mesh < 0 || mesh >= (int)s->h.meshes.size()) return fail(RT_ERR_ARG, "mesh index out of range");
+    int nv = (int)s->h.verts.size();
+    if (i0 < 0 || i1 < 0 || i2 < 0 || i0 >= nv || i1 >= nv || i2 >= nv) return fail(RT_ERR_ARG, "vertex index out of range");
+    s->h.add_triangle(mesh, i0, i1, i2, s->h.add_material(mat_from(mat)));
+    return RT_OK;
+}
+int rt_builder_add_triangle_tex(rt_scene* s, int mesh, int i0, int i1, int i2, const float* mat, const float* tex) {
+    CHECK_BUILDING(s);
+    if (!mat || !tex) return fail(RT_ERR_ARG, "null argument");
+    if (mesh < 0 || mesh >= (int)s->h.meshes.size()) return fail(RT_ERR_ARG, "mesh index out of range");
+    int nv = (int)s->h.verts.size();
+    if (i0 < 0 || i1 < 0 || i2 < 0 || i0 >= nv || i1 >= nv || i2 >= nv) return fail(RT_ERR_ARG, "vertex index out of range");
+    rt::TexDesc t;
+    t.has = 1; t.tx = tex[0]; t.ty = tex[1]; t.ux = tex[2]; t.uy = tex[3]; t.vx = tex[4]; t.vy = tex[5];
+    s->h.add_triangle(mesh, i0, i1, i2, s->h.add_material(mat_from(mat)), t);
+    return RT_OK;
+}
+int rt_builder_add_trans(rt_scene* s, int mesh, int* trans) {
+    CHECK_BUILDING(s);
+    if (mesh < 0 || mesh >= (int)s->h.meshes.size()) return fail(RT_ERR_ARG, "mesh index out of range");
+    int t = s->h.add_trans(mesh);
+    if (trans) *trans = t;
+    return RT_OK;
+}
+int rt_builder_set_trans(rt_scene* s, int t, const float* pos, const float* q) {
+    CHECK_SCENE(s);
+    if (t < 0 || t >= (int)s->h.insts.size()) return fail(RT_ERR_ARG, "transformation index out of range");
+    if (pos) s->h.insts[t].pos = v3(pos[0], pos[1], pos[2]);
+    if (q) s->h.insts[t].rot = Q{q[0], q[1], q[2], q[3]};
+    if (s->finished) {   // instances moved after finishing: refresh the flat copy
+        // Device copies are per frame slot and are refreshed, stream-ordered, by the next frame
+        // of each slot (sync_slot_insts): frames in flight keep the poses they were built from.
+        s->h.d_insts[t].pose = make_pose(s->h.insts[t].rot, s->h.insts[t].pos);
+        s->inst_gen++;
+        invalidate(s);
+    }
+    return RT_OK;
+}
+int rt_builder_build_cube(rt_scene* s, float scale, const float* mat, int* mesh) {
+    CHECK_BUILDING(s);
+    if (!mat) return fail(RT_ERR_ARG, "null material");
+    int m = s->h.build_cube(scale, mat_from(mat));
+    if (mesh) *mesh = m;
+    return RT_OK;
+}
+int rt_builder_build_cube_tex(rt_scene* s, float scale, const float* mat, const float* tile, int* mesh) {
+    CHECK_BUILDING(s);
+    if (!mat || !tile) return fail(RT_ERR_ARG, "null argument");
+    int m = s->h.build_cube(scale, mat_from(mat), tile);
+    if (mesh) *mesh = m;
+    return RT_OK;
+}
+int rt_builder_add_point_light(rt_scene* s, const float* pos, const float* col) {
+    CHECK_BUILDING(s);
+    if (!pos || !col) return fail(RT_ERR_ARG, "null argument");
+    s->h.add_point_light(v3(pos[0], pos[1], pos[2]), v4(col[0], col[1], col[2], col[3]));
+    return RT_OK;
+}
+int rt_builder_add_directional_light(rt_scene* s, const float* dir, const float* col) {
+    CHECK_BUILDING(s);
+    if (!dir || !col) return fail(RT_ERR_ARG, "null argument");
+    s->h.add_directional_light(v3(dir[0], dir[1], dir[2]), v4(col[0], col[1], col[2], col[3]));
+    return RT_OK;
+}
+int rt_builder_finish(rt_scene* s, int W, int H, float fov, float unit, const float* cpos, const float* cq,
+                      const float* da, const float* amb, int depth) {
+    CHECK_BUILDING(s);
+    if (W <= 0 || H <= 0 || !(unit > 0)) return fail(RT_ERR_ARG, "bad canvas/camera parameters");
+    s->h.set_camera(W, H, fov, unit);
+    if (cpos) s->h.cam.pos = v3(cpos[0], cpos[1], cpos[2]);
+    if (cq) s->h.cam.rot = Q{cq[0], cq[1], cq[2], cq[3]};
+    if (da) s->h.dist_atten = v3(da[0], da[1], da[2]);
+    if (amb) s->h.ambience = v4(amb[0], amb[1], amb[2], amb[3]);
+    s->h.depth = depth;
+    std::string err;
+    if (s->h.flatten(&err) != 0) return fail(RT_ERR_PARSE, err);
+    s->finished = true;
+    s->canvas.assign((size_t)W * H, 0u);
+    (void)warm_scene(s);
+    return RT_OK;
+}
+
+int rt_scene_info(const rt_scene* s, int32_t* c) {
+    CHECK_FINISHED(s);
+    if (!c) return fail(RT_ERR_ARG, "null argument");
+    const rt::Scene& h = s->h;
+    c[0] = h.cam.W; c[1] = h.cam.H; c[2] = (int)h.verts.size(); c[3] = (int)h.tris.size(); c[4] = (int)h.meshes.size();
+    c[5] = (int)h.insts.size(); c[6] = (int)h.d_lights.size(); c[7] = (int)h.points.size(); c[8] = h.depth;
+    c[9] = (int)h.mats.size();
+    return RT_OK;
+}
+
+// (ABI 3) hit_tri indexes the triangles in flattened mesh order, so the meshes must list every
+// triangle exactly once: a bitmap of the triangles seen, failing on a repeat or on one left out
+// (a count alone would pass a list that repeats one triangle and omits another).
+static bool meshes_cover_tris_once(const rt::Scene& h) {
+    std::vector<unsigned char> seen(h.tris.size(), 0);
+    size_t n = 0;
+    for (auto& m : h.meshes)
+        for (int i : m.tris) {
+            if (i < 0 || (size_t)i >= seen.size() || seen[i]) return false;
+            seen[i] = 1;
+            n++;
+        }
+    return n == h.tris.size();
+}
+
+int rt_scene_export(const rt_scene* s, int what, void* dst, int64_t cap) {
+    CHECK_FINISHED(s);
+    const rt::Scene& h = s->h;
+    if ((what == RT_EXPORT_TRIS || what == RT_EXPORT_TEXCOORDS) && !meshes_cover_tris_once(h))
+        return fail(RT_ERR_STATE, "meshes do not cover every triangle once");
+    std::vector<float> f;
+    std::vector<int32_t> iv;
+    switch (what) {
+        case RT_EXPORT_VERTICES: for (auto& v : h.verts) { f.push_back(v.x); f.push_back(v.y); f.push_back(v.z); } break;
+        case RT_EXPORT_NORMALS: f = h.verts_norm; break;
+        case RT_EXPORT_TRIS:                                   // flattened (mesh) order: hit_tri indexes it
+            for (auto& m : h.meshes)
+                for (int i : m.tris) { const auto& t = h.tris[i]; iv.insert(iv.end(), {t.i0, t.i1, t.i2, t.mat}); }
+            break;
+        case RT_EXPORT_MATERIALS:
+            for (auto& m : h.mats) {
+                for (const V4* v : {&m.Ke, &m.Ka, &m.Kd, &m.Ks, &m.Kt, &m.Kr}) { f.push_back(v->x); f.push_back(v->y); f.push_back(v->z); f.push_back(v->w); }
+                f.push_back(m.alpha); f.push_back(m.eta);
+            }
+            break;
+        case RT_EXPORT_INSTANCES:
+            for (auto& t : h.insts) { f.insert(f.end(), {t.rot.i, t.rot.j, t.rot.k, t.rot.r, t.pos.x, t.pos.y, t.pos.z}); }
+            break;
+        case RT_EXPORT_INST_MESH: for (auto& t : h.insts) iv.push_back(t.mesh); break;
+        case RT_EXPORT_LIGHTS:
+            for (auto& l : h.d_lights) f.insert(f.end(), {l.v.x, l.v.y, l.v.z, (float)l.type, l.col.x, l.col.y, l.col.z, l.col.w});
+            break;
+        case RT_EXPORT_CAMERA: {
+            const DCamera& c = h.d_cam;
+            f = {c.pos.x, c.pos.y, c.pos.z, h.cam.rot.i, h.cam.rot.j, h.cam.rot.k, h.cam.rot.r, c.near_, c.unit, c.W, c.H,
+                 c.r.x, c.r.y, c.r.z, c.u.x, c.u.y, c.u.z, c.f.x, c.f.y, c.f.z, 0.0f};
+            break;
+        }
+        case RT_EXPORT_ENV:
+            f = {h.dist_atten.x, h.dist_atten.y, h.dist_atten.z, h.ambience.x, h.ambience.y, h.ambience.z, h.ambience.w};
+            break;
+        case RT_EXPORT_TEXCOORDS:
+            for (auto& m : h.meshes)
+                for (int i : m.tris) {
+                    const auto& t = h.tris[i];
+                    f.insert(f.end(), {(float)t.tex.has, t.tex.tx, t.tex.ty, t.tex.ux, t.tex.uy, t.tex.vx, t.tex.vy});
+                }
+            break;
+        case RT_EXPORT_ATLAS: {
+            const size_t n = h.atlas_rgba.size();
+            if (!dst || cap < (int64_t)n) return fail(RT_ERR_ARG, "destination too small");
+            if (n) memcpy(dst, h.atlas_rgba.data(), n);
+            return RT_OK;
+        }
+        default: return fail(RT_ERR_ARG, "unknown export");
+    }
+    size_t bytes = f.size() * 4 + iv.size() * 4;
+    if (!dst || cap < (int64_t)bytes) return fail(RT_ERR_ARG, "destination too small");
+    if (!f.empty()) memcpy(dst, f.data(), f.size() * 4);
+    if (!iv.empty()) memcpy(dst, iv.data(), iv.size() * 4);
+    return RT_OK;
+}
+
+int rt_camera_get(const rt_scene* s, float* pos, float* q) {
+    CHECK_SCENE(s);
+    if (pos) { pos[0] = s->h.cam.pos.x; pos[1] = s->h.cam.pos.y; pos[2] = s->h.cam.pos.z; }
+    if (q) { q[0] = s->h.cam.rot.i; q[1] = s->h.cam.rot.j; q[2] = s->h.cam.rot.k; q[3] = s->h.cam.rot.r; }
+    return RT_OK;
+}
+int rt_camera_set(rt_scene* s, const float* pos, const float* q) {
+    CHECK_FINISHED(s);
+    if (pos) s->h.cam.pos = v3(pos[0], pos[1], pos[2]);
+    if (q) s->h.cam.rot = Q{q[0], q[1], q[2], q[3]};
+    s->h.update_camera_basis();
+    return RT_OK;
+}
+int rt_camera_translate(rt_scene* s, const float* d) {           // entity.h:53-56: translate_global(vec_to_local(dp))
+    CHECK_FINISHED(s);
+    if (!d) return fail(RT_ERR_ARG, "null argument");
+    s->h.cam.pos = s->h.cam.pos + qrot(s->h.cam.rot, v3(d[0], d[1], d[2]));
+    s->h.update_camera_basis();
+    return RT_OK;
+}
+int rt_camera_rotate(rt_scene* s, const float* dq) {             // entity.h:63-65: o = dr * o
+    CHECK_FINISHED(s);
+    if (!dq) return fail(RT_ERR_ARG, "null argument");
+    s->h.cam.rot = qmul(Q{dq[0], dq[1], dq[2], dq[3]}, s->h.cam.rot);
+    s->h.update_camera_basis();
+    return RT_OK;
+}
+int rt_camera_axes(const rt_scene* s, float* r, float* u, float* f) {
+    CHECK_FINISHED(s);
+    const DCamera& c = s->h.d_cam;
+    if (r) { r[0] = c.r.x; r[1] = c.r.y; r[2] = c.r.z; }
+    if (u) { u[0] = c.u.x; u[1] = c.u.y; u[2] = c.u.z; }
+    if (f) { f[0] = c.f.x; f[1] = c.f.y; f[2] = c.f.z; }
+    return RT_OK;
+}
+int rt_env_set(rt_scene* s, const float* amb, const float* da, int depth) {
+    CHECK_FINISHED(s);
+    if (depth < 0 || depth >= MAX_FRAMES) return fail(RT_ERR_ARG, "depth must be in [0, 9]");
+    if (amb) s->h.ambience = v4(amb[0], amb[1], amb[2], amb[3]);
+    if (da) s->h.dist_atten = v3(da[0], da[1], da[2]);
+    s->h.depth = depth;
+    return RT_OK;
+}
+
+int rt_scene_set_atlas(rt_scene* s, const uint8_t* rgba8, int w, int h) {
+    if (!s) return fail(RT_ERR_ARG, "null scene");
+    if (!rgba8 || w <= 0 || h <= 0 || w > 16384 || h > 16384) return fail(RT_ERR_ARG, "bad atlas image");
+    s->h.atlas_rgba.assign(rgba8, rgba8 + (size_t)w * h * 4);
+    s->h.atlas_w = w; s->h.atlas_h = h;
+    s->atlas_dirty = true;
+    return RT_OK;
+}
+int rt_scene_load_atlas(rt_scene* s, const char* path) {
+    if (!s) return fail(RT_ERR_ARG, "null scene");
+    std::vector<std::string> tries;
+    if (path) tries.push_back(path);
+    else {
+        if (s->h.atlas.empty()) return fail(RT_ERR_STATE, "the scene names no atlas");
+        if (s->h.atlas[0] != '/' && !s->h.base_dir.empty()) tries.push_back(s->h.base_dir + "/" + s->h.atlas);
+        tries.push_back(s->h.atlas);
+    }
+    std::string err;
+    for (const std::string& p : tries) {
+        std::ifstream probe(p, std::ios::binary);
+        if (!probe) { err = p + ": cannot open"; continue; }
+        std::vector<uint8_t> px;
+        int w = 0, h = 0;
+        if (rt::load_png_rgba8(p, &px, &w, &h, &err) != 0) return fail(RT_ERR_PARSE, err);
+        return rt_scene_set_atlas(s, px.data(), w, h);
+    }
+    return fail(RT_ERR_IO, err);
+}
+int rt_scene_atlas_info(const rt_scene* s, int32_t* a) {
+    if (!s || !a) return fail(RT_ERR_ARG, "null argument");
+    a[0] = s->h.atlas_w; a[1] = s->h.atlas_h; a[2] = s->h.atlas_rgba.empty() ? 0 : 1;
+    return RT_OK;
+}
+
+void rt_render_opts_default(rt_render_opts* o) {
+    if (!o) return;
+    memset(o, 0, sizeof *o);
+    o->spp = 1; o->use_bvh = 1; o->rebuild_bvh = 1; o->row0 = 0; o->row_step = 1; o->kernel_dim = 16; o->sync = 1;
+}
+
+int rt_render(rt_scene* s, const rt_render_opts* o, rt_stats* stats) {
+    CHECK_FINISHED(s);
+    if (!o) return fail(RT_ERR_ARG, "null options");
+    if (o->spp < 1 || o->row_step < 1 || o->row0 < 0) return fail(RT_ERR_ARG, "spp >= 1, row_step >= 1, row0 >= 0 required");
+    int r;
+    if ((r = upload(s)) != RT_OK) return r;
+    HIPCHK(hipSetDevice(s->device));
+    if ((size_t)s->h.cam.W * s->h.cam.H > (size_t)INT32_MAX) return fail(RT_ERR_LIMIT, "frame larger than 2^31 pixels");
+    if (s->multi && o->row0 == 0 && o->row_step == 1) return render_multi(s, o, stats);   // whole frames: split
+    if ((r = ensure_spp(s, o->spp)) != RT_OK) return r;
+    hipStream_t st = o->stream ? (hipStream_t)o->stream : sstream(s);
+    const bool timed = stats != nullptr;
+    hipEvent_t* te = nullptr;
+    if (o->timing) {
+        if (s->tev_used + 4 > s->tev.size()) {
+            if (s->tev.size() >= 4 * 4096) return fail(RT_ERR_STATE, "too many timed frames pending: call rt_timing_collect");
+            for (int i = 0; i < 4 * 64; i++) { hipEvent_t e; HIPCHK(hipEventCreate(&e)); s->tev.push_back(e); }
+        }
+        te = &s->tev[s->tev_used];
+        s->tev_used += 4;
+    }
+    if (s->n_slots > 1) {                                    // rotate frame slots (rt_scene_set_frame_slots)
+        if ((r = ensure_other_slot(s)) != RT_OK) return r;
+        s->cur_slot = (s->cur_slot + 1) % s->n_slots;
+    }
+    if ((r = begin_frame(s, st, false)) != RT_OK) return r;  // after the slot's previous frame, current poses
+    if (timed) { HIPCHK(hipMemsetAsync(s->d_stats, 0, STATS_N * sizeof(unsigned long long), st)); HIPCHK(hipEventRecord(s->ev[0], st)); }
+    if (o->use_bvh && (o->rebuild_bvh || !s->cur().bvh_valid)) {
+        if ((r = build_bvh(s, st, te ? te[0] : nullptr, te ? te[1] : nullptr)) != RT_OK) {
+            if (te) s->tev_used -= 4;                            // the frame's events stay unrecorded
+            return r;
+        }
+    } else if (te) {
+        HIPCHK(hipEventRecord(te[0], st)); HIPCHK(hipEventRecord(te[1], st));
+    }
+    if (timed) HIPCHK(hipEventRecord(s->ev[1], st));
+    rt_render_opts oo = *o;
+    const size_t W = s->h.cam.W, H = s->h.cam.H;
+    const size_t n_rows = (H > (size_t)o->row0) ? (H - o->row0 + o->row_step - 1) / o->row_step : 0;
+    const size_t out_px = o->compact ? n_rows * W : W * H;
+    if (o->host_outputs) {                                   // stage through device buffers
+        if (s->d_out_px < W * H) {
+            for (auto& p : s->d_out) dfree(p);
+            HIPCHK(hipMalloc(&s->d_out[0], W * H * 4)); HIPCHK(hipMalloc(&s->d_out[1], W * H * 16));
+            HIPCHK(hipMalloc(&s->d_out[2], W * H * 4)); HIPCHK(hipMalloc(&s->d_out[3], W * H * 4));
+            s->d_out_px = W * H;
+        }
+        oo.rgba = o->rgba ? (uint32_t*)s->d_out[0] : nullptr;
+        oo.radiance = o->radiance ? (float*)s->d_out[1] : nullptr;
+        oo.hit_inst = o->hit_inst ? (int32_t*)s->d_out[2] : nullptr;
+        oo.hit_tri = o->hit_tri ? (int32_t*)s->d_out[3] : nullptr;
+    }
+    uint32_t* rgba = oo.rgba ? oo.rgba : s->d_canvas;
+    if ((r = launch_trace(s, oo, st, rgba, nullptr, -1, -1, timed, -1, te ? te[2] : nullptr, te ? te[3] : nullptr)) != RT_OK) {
+        if (te) s->tev_used -= 4;
+        return r;
+    }
+    if (timed) HIPCHK(hipEventRecord(s->ev[2], st));
+    if ((r = end_frame(s, st)) != RT_OK) return r;           // the slot is free again once this frame is done
+    if (o->sync || timed || o->host_outputs) HIPCHK(hipStreamSynchronize(st));
+    if (o->host_outputs) {
+        if (o->rgba) HIPCHK(hipMemcpy(o->rgba, oo.rgba, out_px * 4, hipMemcpyDeviceToHost));
+        if (o->radiance) HIPCHK(hipMemcpy(o->radiance, oo.radiance, out_px * 16, hipMemcpyDeviceToHost));
+        if (o->hit_inst) HIPCHK(hipMemcpy(o->hit_inst, oo.hit_inst, out_px * 4, hipMemcpyDeviceToHost));
+        if (o->hit_tri) HIPCHK(hipMemcpy(o->hit_tri, oo.hit_tri, out_px * 4, hipMemcpyDeviceToHost));
+    }
+    if (timed) {
+        unsigned long long v[4];
+        HIPCHK(hipMemcpy(v, s->d_stats, sizeof v, hipMemcpyDeviceToHost));
+        stats->rays = v[0]; stats->nodes = v[1]; stats->leaves = v[2]; stats->tri_tests = v[3];
+        float a = 0, b = 0;
+        HIPCHK(hipEventElapsedTime(&a, s->ev[0], s->ev[1]));
+        HIPCHK(hipEventElapsedTime(&b, s->ev[1], s->ev[2]));
+        stats->bvh_ms = a; stats->trace_ms = b;
+    }
+    return RT_OK;
+}
+
+
+int rt_scene_set_frame_slots(rt_scene* s, int n) {
+    CHECK_FINISHED(s);
+    if (n < 1 || n > rt_scene::MAX_SLOTS) return fail(RT_ERR_ARG, "frame slots: 1 to " + std::to_string(rt_scene::MAX_SLOTS));
+    if (n == s->n_slots) return RT_OK;
+    if (s->uploaded) { HIPCHK(hipSetDevice(s->device)); HIPCHK(hipDeviceSynchronize()); }   // nothing in flight
+    s->cur_slot = 0;
+    for (auto& f : s->slots) f.pending = false;
+    s->n_slots = n;
+    return (n > 1 && s->uploaded) ? ensure_other_slot(s) : RT_OK;
+}
+
+int rt_scene_set_overlap(rt_scene* s, int policy) {
+    CHECK_SCENE(s);
+    if (policy != RT_OVERLAP_HALF && policy != RT_OVERLAP_FULL && policy != RT_OVERLAP_STREAM)
+        return fail(RT_ERR_ARG, "overlap policy: RT_OVERLAP_HALF, RT_OVERLAP_FULL or RT_OVERLAP_STREAM");
+    s->overlap = policy;
+    if (s->multi) set_multi_overlap(s, policy);               // the replicas of rt_scene_set_devices too
+    return RT_OK;
+}
+
+int rt_timing_collect(rt_scene* s, double* bvh_ms, double* trace_ms, int* n) {
+    CHECK_FINISHED(s);
+    double a = 0, b = 0;
+    for (size_t i = 0; i + 4 <= s->tev_used; i += 4) {
+        HIPCHK(hipEventSynchronize(s->tev[i + 3]));
+        float x = 0, y = 0;
+        HIPCHK(hipEventElapsedTime(&x, s->tev[i], s->tev[i + 1]));
+        HIPCHK(hipEventElapsedTime(&y, s->tev[i + 2], s->tev[i + 3]));
+        a += x; b += y;
+    }
+    if (bvh_ms) *bvh_ms = a;
+    if (trace_ms) *trace_ms = b;
+    if (n) *n = (int)(s->tev_used / 4);
+    s->tev_used = 0;
+    return RT_OK;
+}
+
+int rt_update_scene(rt_scene* s, int kernel_dim, int optimize) {    // raytracer.cu:102-120
+    CHECK_FINISHED(s);
+    if (kernel_dim <= 0) return fail(RT_ERR_ARG, "kernel_dim must be positive");
+    rt_render_opts o;
+    rt_render_opts_default(&o);
+    o.use_bvh = optimize ? 1 : 0; o.rebuild_bvh = 1; o.kernel_dim = kernel_dim;
+    o.sync = s->multi ? 1 : 0;                                // split frames end on the slot's streams
+    int r = rt_render(s, &o, nullptr);
+    if (r != RT_OK) return r;
+    // the canvas is host-readable on return (canvas.cu:23-29): one copy-engine transfer into the
+    // pinned host canvas on the frame's stream, then wait for that stream only
+    hipStream_t st = sstream(s);
+    if (s->canvas.pinned)
+        HIPCHK(hipMemcpyAsync(s->canvas.data(), s->d_canvas, s->canvas.size() * sizeof(uint32_t), hipMemcpyDeviceToDeviceNoCU, st));
+    else
+        HIPCHK(hipMemcpyAsync(s->canvas.data(), s->d_canvas, s->canvas.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return RT_OK;
+}
+
+
+int rt_canvas_read(const rt_scene* s, uint32_t* dst, int64_t n) {
+    CHECK_FINISHED(s);
+    if (!dst || n < (int64_t)s->canvas.size()) return fail(RT_ERR_ARG, "destination too small");
+    memcpy(dst, s->canvas.data(), s->canvas.size() * sizeof(uint32_t));
+    return RT_OK;
+}
+const uint32_t* rt_canvas_host_ptr(const rt_scene* s) { return s ? s->canvas.data() : nullptr; }
+int rt_canvas_get_color(const rt_scene* s, int x, int y, uint8_t* c) {
+    CHECK_FINISHED(s);
+    if (!c || x < 0 || y < 0 || x >= s->h.cam.W || y >= s->h.cam.H) return fail(RT_ERR_ARG, "pixel out of range");
+    uint32_t e = s->canvas[(size_t)y * s->h.cam.W + x];                  // Color::from_encoding (color.cu:28-34)
+    c[0] = (uint8_t)(e >> 24); c[1] = (uint8_t)(e >> 16); c[2] = (uint8_t)(e >> 8); c[3] = (uint8_t)e;
+    return RT_OK;
+}
+
+int rt_debug_cast(rt_scene* s, int x, int y, char* buf, int64_t cap) {   // raytracer.cu:91-100
+    CHECK_FINISHED(s);
+    if (x < 0 || y < 0 || x >= s->h.cam.W || y >= s->h.cam.H) return fail(RT_ERR_ARG, "pixel out of range");
+    int r;
+    if ((r = upload(s)) != RT_OK) return r;
+    HIPCHK(hipSetDevice(s->device));
+    if ((r = ensure_spp(s, 1)) != RT_OK) return r;
+    // rebuilds the current slot's BVH: first wait for every frame in flight (any slot)
+    if ((r = begin_frame(s, sstream(s), true)) != RT_OK) return r;
+    if ((r = build_bvh(s, sstream(s))) != RT_OK) return r;
+    HIPCHK(hipMemsetAsync(s->d_dbg, 0, 4096 * sizeof(int), sstream(s)));
+    rt_render_opts o;
+    rt_render_opts_default(&o);
+    o.row0 = y; o.row_step = s->h.cam.H;                                  // just the row of (x, y)
+    if ((r = launch_trace(s, o, sstream(s), s->d_canvas, s->d_dbg, x, y, true)) != RT_OK) return r;
+    if ((r = end_frame(s, sstream(s))) != RT_OK) return r;
+    std::vector<int> log(4096);
+    HIPCHK(hipStreamSynchronize(sstream(s)));
+    HIPCHK(hipMemcpy(log.data(), s->d_dbg, log.size() * sizeof(int), hipMemcpyDeviceToHost));
+    static const char* names[] = {"", "shooting a ray", "preparing to shoot a reflection ray",
+                                  "preparing to shoot a refraction ray", "shooting shadow ray"};
+    std::string out;
+    int n = std::min(log[0], 4094);
+    for (int i = 0; i < n; i++) { int e = log[2 + i]; if (e >= 1 && e <= 4) { out += names[e]; out += '\n'; } }
+    if (buf && cap > 0) { size_t m = std::min<size_t>(out.size(), (size_t)cap - 1); memcpy(buf, out.data(), m); buf[m] = 0; }
+    return RT_OK;
+}
+
+// Profiling aid (not part of rt_amd.h's stable surface): run experiment `which` `reps`
+// times -- 4: the counted kernel with the occlusion early exit, 5: the counted kernel,
+// 6: the fast kernel's PROF variant (wave step counts, cycle split, and the queries the
+// fast kernel issues) -- and return the mean kernel ms and the counters.
+int rt_experiment(rt_scene* s, int which, int spp, int reps, double* ms, uint64_t* counters) {
+    CHECK_FINISHED(s);
+    int r;
+    if (which == 4 || which == 5 || which == 6) {             // full frame: counted kernel (4: occlusion exit on),
+                                                              // 6: the fast kernel's profiling variant (M_PROF)
+        if ((r = upload(s)) != RT_OK) return r;
+        HIPCHK(hipSetDevice(s->device));
+        if ((r = ensure_spp(s, spp)) != RT_OK) return r;
+        rt_render_opts o; rt_render_opts_default(&o); o.spp = spp;
+        if ((r = begin_frame(s, sstream(s), true)) != RT_OK) return r;   // nothing else in flight on this slot
+        if ((r = build_bvh(s, sstream(s))) != RT_OK) return r;
+        float total = 0;
+        for (int i = 0; i < reps; i++) {
+            HIPCHK(hipMemsetAsync(s->d_stats, 0, STATS_N * sizeof(unsigned long long), sstream(s)));
+            HIPCHK(hipMemsetAsync(s->d_stats + 15, 0xff, sizeof(unsigned long long), sstream(s)));
+            HIPCHK(hipMemsetAsync(s->d_stats + 19, 0xff, sizeof(unsigned long long), sstream(s)));
+            HIPCHK(hipEventRecord(s->ev[0], sstream(s)));
+            if ((r = (which == 6 ? launch_trace(s, o, sstream(s), s->d_canvas, nullptr, -1, -1, false, -1, nullptr, nullptr, true)
+                                 : launch_trace(s, o, sstream(s), s->d_canvas, nullptr, -1, -1, true, which == 4 ? 1 : 0))) != RT_OK)
+                return r;
+            HIPCHK(hipEventRecord(s->ev[1], sstream(s)));
+            HIPCHK(hipEventSynchronize(s->ev[1]));
+            float t = 0; HIPCHK(hipEventElapsedTime(&t, s->ev[0], s->ev[1]));
+            if (i > 0 || reps == 1) total += t;
+        }
+        if ((r = end_frame(s, sstream(s))) != RT_OK) return r;
+        unsigned long long v[22];
+        HIPCHK(hipMemcpy(v, s->d_stats, sizeof v, hipMemcpyDeviceToHost));
+        if (counters) for (int i = 0; i < 22; i++) counters[i] = v[i];
+        if (ms) *ms = total / (reps > 1 ? reps - 1 : 1);
+        return RT_OK;
+    }
+    return fail(RT_ERR_ARG, "experiment: 4 (counted, occlusion exit), 5 (counted), 6 (fast kernel, PROF counters)");
+}
+
+int rt_frame_work(rt_scene* s, const rt_render_opts* o, rt_work* w) {
+    CHECK_FINISHED(s);
+    if (!o || !w) return fail(RT_ERR_ARG, "null argument");
+    if (o->spp < 1 || o->spp > 64 || o->row_step < 1 || o->row0 < 0 || !o->use_bvh || o->textures)
+        return fail(RT_ERR_ARG, "rt_frame_work: BVH frames, 1 <= spp <= 64, untextured");
+    int r;
+    if ((r = upload(s)) != RT_OK) return r;
+    HIPCHK(hipSetDevice(s->device));
+    if ((r = ensure_spp(s, o->spp)) != RT_OK) return r;
+    const size_t rows = (s->h.cam.H > o->row0) ? (size_t)(s->h.cam.H - o->row0 + o->row_step - 1) / o->row_step : 0;
+    uint32_t* d_rgba = nullptr;
+    HIPCHK(hipMalloc((void**)&d_rgba, std::max<size_t>(1, (o->compact ? rows : (size_t)s->h.cam.H) * s->h.cam.W) * 4));
+    hipStream_t st = sstream(s);
+    r = begin_frame(s, st, true);                             // nothing else in flight on this slot
+    if (r == RT_OK) r = build_bvh(s, st);
+    if (r == RT_OK) {
+        HIPCHK(hipMemsetAsync(s->d_stats, 0, STATS_N * sizeof(unsigned long long), st));
+        HIPCHK(hipMemsetAsync(s->d_stats + 15, 0xff, sizeof(unsigned long long), st));
+        HIPCHK(hipMemsetAsync(s->d_stats + 19, 0xff, sizeof(unsigned long long), st));
+        rt_render_opts oo = *o;
+        oo.radiance = nullptr; oo.hit_inst = oo.hit_tri = nullptr;
+        r = launch_trace(s, oo, st, d_rgba, nullptr, -1, -1, false, -1, nullptr, nullptr, true);
+    }
+    if (r == RT_OK) r = end_frame(s, st);
+    unsigned long long v[STATS_N] = {};
+    if (r == RT_OK) {
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipMemcpy(v, s->d_stats, sizeof v, hipMemcpyDeviceToHost));
+        if (v[4] == 0 && rows > 0) r = fail(RT_ERR_STATE, "no profiling variant of the fast kernel for this scene");
+    }
+    (void)hipFree(d_rgba);
+    if (r != RT_OK) return r;
+    w->queries = v[0]; w->wave_queries = v[4]; w->pair_steps = v[5]; w->leaf_visits = v[6]; w->tri_iters = v[7];
+    w->leaf_lanes = v[2];
+    w->scene_bytes = scene_image_bytes(view_of(s, true));
+    w->lanes_primary = v[PROF_LANES_PRIMARY]; w->lanes_secondary = v[PROF_LANES_SECONDARY];
+    w->lanes_shadow = v[PROF_LANES_SHADOW]; w->lanes_unlit = v[PROF_LANES_UNLIT];
+    w->live_wave_queries = v[PROF_LIVE_WQ]; w->live_lanes = v[PROF_LIVE_LANES];
+    for (int i = 0; i < 8; i++) {
+        w->hist_wave_queries[i] = v[PROF_HIST_WQ + i];
+        w->hist_pair_steps[i] = v[PROF_HIST_PAIR + i];
+        w->hist_leaf_visits[i] = v[PROF_HIST_LEAF + i];
+    }
+    return RT_OK;
+}
+
+// Profiling aid (tools/group_profile.py, not on the product path): per-group durations
+// (100 MHz ticks) of the fast frame kernel over rows row0, row0 + row_step, ... (compact),
+// as bench.py's rank row0 of row_step renders them.  `reps` frames, each with the per-frame
+// BVH rebuild; the last one (scheduled from the previous frame's history) is recorded.
+// geo = {n_groups, gw, gh, n_gx}; *ms = the last frame's kernel time.  prof = 1: the recorded
+// frame runs the PROF variant (when the scene has one) and out[n_groups + 12 g ..] holds group
+// g's wave queries, child-pair steps, leaf visits, triangle iterations, then shader cycles in
+// queries, in leaf visits, in trace_sample, after queries (state machine), and in the group; then
+// (slots 9-11) cycles in the light step (ST_LIGHT), in the hit normal of a query's step, and in
+// parking (writes before the query, reads after it; the reads also count in the query's cycles).
+int rt_profile_groups(rt_scene* s, int spp, int row0, int row_step, int reps, int prof, uint32_t* out, int64_t cap,
+                      int* geo, double* ms) {
+    CHECK_FINISHED(s);
+    if (!out || !geo || cap <= 0 || reps < 1 || row_step < 1 || row0 < 0) return fail(RT_ERR_ARG, "bad arguments");
+    int r;
+    if ((r = upload(s)) != RT_OK) return r;
+    HIPCHK(hipSetDevice(s->device));
+    if ((r = ensure_spp(s, spp)) != RT_OK) return r;
+    const int rows = (s->h.cam.H - row0 + row_step - 1) / row_step;
+    if (rows <= 0) return fail(RT_ERR_ARG, "no rows in the slice");
+    rt_render_opts o; rt_render_opts_default(&o);
+    o.spp = spp; o.row0 = row0; o.row_step = row_step; o.compact = 1;
+    uint32_t* d_rgba = nullptr;
+    unsigned* d_g = nullptr;
+    HIPCHK(hipMalloc((void**)&d_rgba, (size_t)s->h.cam.W * rows * sizeof(uint32_t)));
+    geo[0] = geo[1] = geo[2] = geo[3] = 0;
+    reps = std::max(reps, 2);                                 // frame 0 sizes the buffer and seeds the history
+    const int nw = prof ? 13 : 1;                             // prof: + 12 counters per group (PROF kernel)
+    if ((r = begin_frame(s, sstream(s), true)) != RT_OK) { (void)hipFree(d_rgba); return r; }
+    for (int i = 0; i < reps && r == RT_OK; i++) {
+        const bool rec = i == reps - 1;
+        if (rec) {
+            if (geo[0] <= 0 || (int64_t)geo[0] * nw > cap) { r = fail(RT_ERR_LIMIT, "group buffer too small"); break; }
+            HIPCHK(hipMalloc((void**)&d_g, (size_t)geo[0] * nw * sizeof(unsigned)));
+            HIPCHK(hipMemsetAsync(d_g, 0, (size_t)geo[0] * nw * sizeof(unsigned), sstream(s)));
+        }
+        if ((r = build_bvh(s, sstream(s))) != RT_OK) break;
+        r = launch_trace(s, o, sstream(s), d_rgba, nullptr, -1, -1, false, -1, s->ev[0], s->ev[1], rec && prof,
+                         rec ? d_g : nullptr, geo);
+    }
+    if (r == RT_OK) r = end_frame(s, sstream(s));
+    if (r == RT_OK) {
+        HIPCHK(hipEventSynchronize(s->ev[1]));
+        float t = 0;
+        HIPCHK(hipEventElapsedTime(&t, s->ev[0], s->ev[1]));
+        if (ms) *ms = t;
+        HIPCHK(hipMemcpy(out, d_g, (size_t)geo[0] * nw * sizeof(unsigned), hipMemcpyDeviceToHost));
+    }
+    (void)hipFree(d_rgba);
+    (void)hipFree(d_g);
+    return r;
+}
+
+int rt_kat_device(const char* op, int n, const float* in0, const float* in1, const float* in2, float* of, int32_t* oi,
+                  uint64_t* ou) {
+    static const char* ops[] = {"normalize3", "cross", "reflect", "refract", "quat_rotate", "quat_inverse", "quat_mul",
+                                "tri_hit", "ray_ctor", "zorder", "to_mat3", "box_hit", "pow", "tri_hit_f", "box_hit_f",
+                                "box_pair", "rcp_cr", "sqrt_cr", "box_from_local", "box_merge", "entity"};
+    // per-op sizes (floats): in0, in1, in2, out_f, out_i, out_u per element
+    static const int sz[][6] = {{3, 0, 0, 3, 0, 0}, {3, 3, 0, 3, 0, 0}, {3, 3, 0, 3, 0, 0}, {3, 3, 2, 3, 1, 0},
+                                {4, 3, 0, 3, 0, 0}, {4, 0, 0, 4, 0, 0}, {4, 4, 0, 4, 0, 0}, {9, 6, 0, 3, 1, 0},
+                                {6, 0, 0, 6, 0, 0}, {3, 0, 0, 0, 0, 1}, {4, 0, 0, 9, 0, 0}, {7, 6, 0, 0, 1, 0},
+                                {1, 1, 0, 1, 0, 0}, {9, 6, 0, 3, 1, 0}, {7, 6, 0, 0, 1, 0}, {14, 6, 0, 0, 2, 0},
+                                {1, 0, 0, 1, 0, 0}, {1, 0, 0, 1, 0, 0}, {7, 7, 0, 6, 1, 0}, {7, 7, 0, 6, 1, 0},
+                                {7, 3, 0, 12, 0, 0}};
+    if (!op || n <= 0) return fail(RT_ERR_ARG, "bad arguments");
+    int k = -1;
+    for (int i = 0; i < (int)(sizeof ops / sizeof *ops); i++) if (!strcmp(op, ops[i])) k = i;
+    if (k < 0) return fail(RT_ERR_ARG, std::string("unknown op ") + op);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(RT_ERR_NODEV, "no HIP device available");
+    HIPCHK(hipSetDevice(g_device));
+    const float* hin[3] = {in0, in1, in2};
+    float* din[3] = {nullptr, nullptr, nullptr};
+    float* dof = nullptr; int* doi = nullptr; unsigned long long* dou = nullptr;
+    for (int i = 0; i < 3; i++)
+        if (sz[k][i]) {
+            if (!hin[i]) return fail(RT_ERR_ARG, "missing input");
+            HIPCHK(hipMalloc((void**)&din[i], (size_t)n * sz[k][i] * 4));
+            HIPCHK(hipMemcpy(din[i], hin[i], (size_t)n * sz[k][i] * 4, hipMemcpyHostToDevice));
+        }
+    if (sz[k][3]) HIPCHK(hipMalloc((void**)&dof, (size_t)n * sz[k][3] * 4));
+    if (sz[k][4]) HIPCHK(hipMalloc((void**)&doi, (size_t)n * sz[k][4] * 4));
+    if (sz[k][5]) HIPCHK(hipMalloc((void**)&dou, (size_t)n * 8));
+    launch_kat(k, n, din[0], din[1], din[2], dof, doi, dou);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    if (sz[k][3] && of) HIPCHK(hipMemcpy(of, dof, (size_t)n * sz[k][3] * 4, hipMemcpyDeviceToHost));
+    if (sz[k][4] && oi) HIPCHK(hipMemcpy(oi, doi, (size_t)n * sz[k][4] * 4, hipMemcpyDeviceToHost));
+    if (sz[k][5] && ou) HIPCHK(hipMemcpy(ou, dou, (size_t)n * 8, hipMemcpyDeviceToHost));
+    for (auto p : din) if (p) (void)hipFree(p);
+    if (dof) (void)hipFree(dof);
+    if (doi) (void)hipFree(doi);
+    if (dou) (void)hipFree(dou);
+    return RT_OK;
+}
+
+}  // extern "C"

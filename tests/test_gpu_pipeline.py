@@ -111,6 +111,33 @@ def test_pipeline_world2_gather_and_unpermute(gpu):
     assert torch.equal(pipe.finish(), full)
 
 
+def test_slot_count_changes_regrow_and_mirror(gpu):
+    """One scene driven through 1 -> 4 -> 2 -> 4 frame slots; at each setting 2 x depth frames at
+    1 spp, then at 8 spp, then (with several slots) at a spp whose group layout is larger than
+    any before it.  Loading reserves the 8-spp layout (2400 groups at this size), so 1 and 8 spp
+    grow nothing; 16 spp (4800 groups) at four slots and 32 spp (9600) at two regrow the current
+    slot's sky, live-list and history buffers and replace the smaller ones of the other slots
+    while the scene has had frames on them, and the return to four slots brings slots 2 and 3
+    from the 16-spp to the 32-spp capacity.  Every frame is the one-slot frame of that spp, bit
+    for bit, and the scene is freed with several slots allocated."""
+    import torch
+    w, h = 160, 120                                             # the committed golden frame's size
+    ref = {spp: _serial(gpu, "world8", w, h, spp) for spp in (1, 8, 16, 32)}
+    s = gpu.Scene.load_json(scene_path("world8"), w, h)
+    streams = [torch.cuda.Stream() for _ in range(4)]
+    for depth, spps in ((1, (1, 8)), (4, (1, 8, 16)), (2, (1, 8, 32)), (4, (1, 8, 32))):
+        s.set_frame_slots(depth)
+        for spp in spps:
+            bufs = [torch.zeros((h, w), dtype=torch.int32, device="cuda") for _ in range(2 * depth)]
+            torch.cuda.synchronize()
+            for k, buf in enumerate(bufs):
+                s.render_device(spp=spp, rgba_ptr=buf.data_ptr(), stream=streams[k % depth].cuda_stream)
+            torch.cuda.synchronize()
+            for k, buf in enumerate(bufs):
+                assert torch.equal(buf, ref[spp]), (depth, spp, k)
+    s.close()
+
+
 def _move(s, k, inst):
     """Frame k's poses: a few instances lifted / shifted (cumulative), one frame with a
     rotated instance (the general-pose kernels), so consecutive frames differ."""
