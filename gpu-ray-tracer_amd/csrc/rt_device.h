@@ -1,6 +1,7 @@
 // rt_device.h — what the host runtime (rt_runtime.cpp, rt_multi.cpp, rt_copy.cpp) and the
 // kernel translation unit (rt_kernels.hip) share: the kernel argument structs, the launch
-// geometry the host sizes buffers and grids by, and the launch layer's declarations.  The
+// geometry the host sizes buffers and grids by, the launch plan (rt_plan.h, included below:
+// LDS layout, kernel choice, frame geometry, grid) and the launch layer's declarations.  The
 // launch layer is defined at the end of rt_kernels.hip; its functions are the only ones that
 // name a kernel, so every kernel is instantiated in that one translation unit.
 #pragma once
@@ -160,20 +161,24 @@ struct TraceParams {
                               // and no phong term for it either (2)
 };
 
+}  // namespace rtd
+
+#include "rt_plan.h"   // the LDS layout and MODE bits; the launch plan (trace_variant_key and the rest)
+
+namespace rtd {
+
 // ---------------------------------------------------------------------------
 // Launch layer (defined in rt_kernels.hip)
 // ---------------------------------------------------------------------------
-// The trace kernel variant for a frame: which instantiation, its dynamic LDS, the blocks of it
-// a CU holds, and the decisions the host's launch set-up depends on.
-struct TraceVariant {
-    const void* fn;
-    size_t shm;
+// The trace kernel variant for a frame: its key (trace_variant_key: instantiation, dynamic LDS,
+// the decisions the host's launch set-up depends on), the kernel and the blocks of it a CU holds.
+struct TraceVariant : TraceKey {
+    const void* fn;           // null: no kernel with this key (a programming error; nothing is launched)
     int per_cu;
-    bool part_k;              // partial parking (M_PART): wide live-list tickets at 64 lanes per pixel
-    bool sky, sky_brute;      // sky pre-pass before the trace kernel; over the instances' grown boxes
 };
-// ns: suspended frames a sample needs (0: no refractive material).  Sets the function's dynamic
-// LDS limit and queries its occupancy.
+// ns: suspended frames a sample needs (0: no refractive material).  Looks trace_variant_key's
+// key up in the table of trace kernels, sets the function's dynamic LDS limit and queries its
+// occupancy.
 TraceVariant choose_trace_variant(const SceneView& S, int spp, bool tex, bool want_stats, bool prof, int ns);
 // e0 / e1 (optional): timestamps taken by the dispatch itself, no marker packets
 hipError_t launch_sky(bool brute, int blocks, TraceParams& P, SceneView& S, unsigned char* gsky, int* live,

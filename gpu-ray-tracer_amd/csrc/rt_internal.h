@@ -24,6 +24,16 @@ extern thread_local int g_device;             // rt_set_device: the device new s
 
 template <class T> void dfree(T*& p) { if (p) { (void)hipFree(p); p = nullptr; } }
 template <class T> void hfree(T*& p) { if (p) { (void)hipHostFree(p); p = nullptr; } }
+// A device allocation that lives as long as its scope (the side entries' temporary buffers):
+// freed on every return path, HIPCHK's early ones included.
+template <class T> struct DevBuf {
+    T* p = nullptr;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { dfree(p); }
+    hipError_t alloc(size_t n) { return hipMalloc((void**)&p, n * sizeof(T)); }   // n elements
+};
 
 // Host framebuffer in pinned memory: rt_update_scene's device-to-host copy of the frame (the
 // reference's post-condition, raytracer.cu:102-120) is then one direct transfer; into pageable

@@ -53,17 +53,10 @@ using rt::DTri;
 
 namespace {
 
-// (launch geometry, tuning macros and the kernel argument structs the host shares: rt_device.h)
-constexpr int LDS_LIMIT = 150 * 1024;    // above this the BVH is read from global memory
-constexpr int PARK_LDS_LIMIT = 158 * 1024;   // BVH image + parking area (160 KB per CU)
+// (launch geometry, tuning macros and the kernel argument structs the host shares: rt_device.h;
+// the LDS layout -- LDS limits, lds_bytes, parked fields, PROF slots -- and the MODE bits: rt_plan.h)
 // (work counter layout: WORK_INTS, rt_device.h)
 constexpr int WORK_HEAVY_LEN = 16 * (2 * NQ + 1);
-// PROF kernels keep the occupancy counters [24, PROF_END) per wave in LDS (a global atomic per wave
-// query on a few shared addresses serialised and perturbed the profile 30x) and add them to d_stats
-// once per wave at the end
-constexpr int PROF_WAVE_SLOTS = 32;
-static_assert(PROF_END - PROF_LANES_PRIMARY <= PROF_WAVE_SLOTS, "per-wave PROF counter slots");
-constexpr size_t PROF_LDS_BYTES = 16 * PROF_WAVE_SLOTS * sizeof(unsigned long long);   // 16 waves per block
 
 enum : int { F_NORMAL = 0, F_REFLECT = 1, F_REFRACT = 2 };
 enum : int { PH_NORMAL = 1, PH_SHADOW = 2, PH_DONE = 3 };
@@ -776,6 +769,7 @@ __device__ __forceinline__ KTP& kparams() {
 #endif
 typedef __attribute__((address_space(4))) const SceneView KSV;
 static_assert(sizeof(TraceParams) % alignof(SceneView) == 0, "SceneView follows TraceParams in the kernarg segment");
+static_assert(sizeof(TraceParams) == 400 && sizeof(SceneView) == 128, "kernarg layout (the kernels read it in place)");
 __device__ __forceinline__ SceneView kscene() {
     const __attribute__((address_space(4))) char* p =
         (const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr();
@@ -891,19 +885,11 @@ enum : int { ST_DONE = 0, ST_ADVANCE = 1, ST_WAIT_NORMAL = 2, ST_LIGHT = 3, ST_W
 // stop the compiler from forwarding the stored values and keeping them live.
 // The light's phong factor (phong.cu:14-53 without the incoming light) is formed once, when the
 // shadow query is set up, and parked: the light's term after the query is factor x incoming,
-// the same operations in the same order as the reference's phong.  NS = 0 kernels run only scenes without a
-// refractive material (launch_trace): there a shadow ray's light is never attenuated (rv = the
-// light's colour, reloaded after the query), so they park 4 fields fewer.
+// the same operations in the same order as the reference's phong.  NS = 0 kernels park 4 fields
+// fewer (park_fields, rt_plan.h; partial parking: PART_FIELDS there).
 // Parked kernels also park normalized(hit normal), formed once per hit for phong's reflect
 // (every light) and the reflection ray, instead of once per use (same value: frame -1.8%,
 // profiles/r04/ab_nn.log).
-constexpr int PARK_FIELDS = 29;
-__host__ __device__ constexpr int park_fields(int ns) { return ns == 0 ? 25 : PARK_FIELDS; }
-// Partial parking (M_PART): scenes whose ordered tree fills most of the LDS (world16: 93 KB)
-// park the first PART_FIELDS fields only (the ray, its attenuation and the accumulated
-// radiance); the rest stay in registers.  The instance records are then read from global
-// memory (L2-resident; as scalar loads they measured +1%) to leave the LDS to the tree.
-constexpr int PART_FIELDS = 14;
 template <int NS, bool STATS, bool PARK, bool TEX, bool FT, bool AXIS, bool PROF = false, bool BRUTE = false,
           bool PART = false>
 __device__ __forceinline__ V4 trace_sample(const SceneView& S, const BvhRefs& bv, bool valid,
@@ -1193,21 +1179,7 @@ __device__ __forceinline__ V4 trace_sample(const SceneView& S, const BvhRefs& bv
     return acc;
 }
 
-// stage_bvh's LDS image size (16-B multiple)
-__host__ __device__ inline size_t a16(size_t b) { return (b + 15) & ~(size_t)15; }
-// LDS shading cache (M_SHADE): mats | lights | tris | meshes, each 16-B aligned
-__host__ __device__ inline size_t shade_bytes(const SceneView& S) {
-    return a16(sizeof(DMat) * (size_t)S.n_mats) + a16(sizeof(DLight) * (size_t)S.n_lights) +
-           a16(sizeof(DTri) * (size_t)S.n_tris) + a16(sizeof(DMesh) * (size_t)S.n_meshes);
-}
-__host__ __device__ inline size_t lds_bytes(const SceneView& S, bool ft = false, bool shade = false, bool brute = false,
-                                            bool part = false) {
-    const size_t sh = shade ? shade_bytes(S) : 0;
-    if (brute) return a16(16 * (size_t)S.n_inst) + sh;        // inst4 only (M_BRUTE)
-    if (ft && part) return 64 * (size_t)(S.n_real - 1) + sh;   // the ordered tree only (M_PART)
-    if (ft) return 64 * (size_t)(S.n_real - 1) + 16 * (size_t)S.n_inst + sh;
-    return a16(48 * (size_t)S.n_leaf + 4 * (size_t)S.n_leaf) + a16(16 * (size_t)S.n_inst) + sh;
-}
+// (stage_bvh's LDS image sizes: a16, shade_bytes, lds_bytes, rt_plan.h)
 // word copy of n records of T into LDS at `dst` (block-cooperative)
 template <class T> __device__ __forceinline__ const T* stage_words(unsigned char* dst, const T* src, int n) {
     static_assert(sizeof(T) % 4 == 0 && alignof(T) <= 16, "word-granular records");
@@ -1277,22 +1249,7 @@ __device__ __forceinline__ V4 shfl4(V4 v, int src) {
 // A group = `px_per_wave` pixels x `lanes_per_px` samples; lane (pixel p, sub s)
 // traces samples k = round*L + s and the group leader sums the clamped sample
 // radiance in k order (build-defined spp extension).
-// MODE bit 0 (MULTI): spp > 64 -- several rounds of samples per lane (the per-pixel sums
-// then stay live across rounds, which the common single-round kernel avoids).
-// MODE bit 1 (STATS): exact work counters.  The divergent state machine keeps 64-bit
-// counters in VGPRs, so frames without statistics use a kernel without them.
-// MODE bit 2 (PARK): park integrator state in LDS during queries (trace_sample); needs
-// PARK_FIELDS x 4 B x TRACE_BLOCK_P of LDS beside the BVH image.
-// MODE bit 3 (TEX): textured shading (hit_kd), generic frame depth only.
-// MODE bit 4 (FT): traverse the ordered LBVH (closest_hit) instead of the reference heap.
-// MODE bit 5 (AXIS): FT with the axis-plane triangle path (S.tri_ax, cast_local).
-// MODE bit 6 (PROF): profiling variant of the fast kernel -- wave-level step counts and
-// s_memtime cycle accounting (rt_experiment 6); results identical, timing perturbed.
-// MODE bit 8 (BRUTE): brute-force frames (use_bvh = 0) with only the instance loop compiled
-// (closest_hit); LDS image = inst4 (+ the shading cache, parking area).
-// MODE bit 9 (PART): partial parking (PART_FIELDS) with the tree alone in LDS (see PART_FIELDS).
-constexpr int M_MULTI = 1, M_STATS = 2, M_PARK = 4, M_TEX = 8, M_FT = 16, M_AXIS = 32, M_PROF = 64, M_SHADE = 128,
-              M_BRUTE = 256, M_PART = 512;
+// MODE: the M_* bits (rt_plan.h, each described there).
 template <int NS, bool LDS, int MODE>
 __global__ __launch_bounds__(TRACE_BLOCK_P) void trace_kernel(TraceParams P_arg, SceneView S) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -2313,91 +2270,47 @@ namespace rtd {
 
 size_t scene_image_bytes(const SceneView& S) { return lds_bytes(S, true, true); }
 
+// The trace kernels: every instantiation of trace_kernel is named here, once, and nowhere else.
+// trace_variant_key (rt_plan.h) decides which of them a frame gets.
+struct TraceEntry { int ns; bool lds; int mode; const void* fn; };
+constexpr int NG = MAX_FRAMES - 1;                         // generic frame-stack depth
+#define TK(NS, LDS, MODE) TraceEntry{NS, LDS, MODE, (const void*)trace_kernel<NS, LDS, MODE>}
+#define TK3(LDS, MODE) TK(0, LDS, MODE), TK(2, LDS, MODE), TK(NG, LDS, MODE)   // one per frame-stack bucket
+#define TKG(MODE) TK(NG, false, MODE), TK(NG, true, MODE)                      // generic depth, BVH in HBM / LDS
+static const TraceEntry trace_kernels[] = {
+    // reference heap traversal: plain, parked
+    TK3(false, 0), TK3(true, 0), TK3(true, M_PARK),
+    // counted / multi-round frames and the generic textured kernels
+    TKG(M_MULTI), TKG(M_STATS), TKG(M_MULTI | M_STATS),
+    TKG(M_TEX), TKG(M_TEX | M_MULTI), TKG(M_TEX | M_STATS), TKG(M_TEX | M_MULTI | M_STATS),
+    // fast frames (ordered LBVH): unparked, parked, + axis-plane triangles, + PROF, + LDS shading cache
+    TK3(true, M_FT), TK3(true, M_PARK | M_FT), TK3(true, M_PARK | M_FT | M_AXIS),
+    TK3(true, M_PARK | M_FT | M_AXIS | M_PROF), TK3(true, M_PARK | M_FT | M_AXIS | M_SHADE),
+    // textured fast frames: unparked, NS 2 and NG only
+    TK(2, true, M_TEX | M_FT), TK(NG, true, M_TEX | M_FT),
+    TK(2, true, M_TEX | M_FT | M_AXIS), TK(NG, true, M_TEX | M_FT | M_AXIS),
+    // brute-force fast frames
+    TK3(true, M_BRUTE | M_PARK | M_SHADE | M_AXIS),
+    // partial parking: NS = 0 only
+    TK(0, true, M_PARK | M_FT | M_AXIS | M_SHADE | M_PART), TK(0, true, M_PARK | M_FT | M_AXIS | M_SHADE | M_PART | M_TEX),
+};
+#undef TKG
+#undef TK3
+#undef TK
+static_assert(sizeof trace_kernels / sizeof *trace_kernels == 47, "the trace kernels of the build");
+
 TraceVariant choose_trace_variant(const SceneView& S, int spp, bool tex, bool want_stats, bool prof, int ns) {
-    const int mode0 = (spp > 64 ? M_MULTI : 0) | (want_stats ? M_STATS : 0);
-    // brute force (the reference's -r): no tree kernel (closest_hit's FT path assumes a tree)
-    const bool brute = !S.use_bvh || S.n_leaf == 0;
-    const bool ft = !brute && mode0 == 0 && S.ftree && lds_bytes(S, true) <= (size_t)LDS_LIMIT;
-    const size_t lds = lds_bytes(S, ft);
-    const bool use_lds = lds <= (size_t)LDS_LIMIT;
-    const void* fn;
-    const int mode = (spp > 64 ? M_MULTI : 0) | (want_stats ? M_STATS : 0);
-    constexpr int NG = MAX_FRAMES - 1;                     // generic frame-stack depth
-    static const void* const generic[2][4] = {
-        {(const void*)trace_kernel<NG, false, 0>, (const void*)trace_kernel<NG, false, 1>,
-         (const void*)trace_kernel<NG, false, 2>, (const void*)trace_kernel<NG, false, 3>},
-        {(const void*)trace_kernel<NG, true, 0>, (const void*)trace_kernel<NG, true, 1>,
-         (const void*)trace_kernel<NG, true, 2>, (const void*)trace_kernel<NG, true, 3>}};
-    static const void* const textured[2][4] = {
-        {(const void*)trace_kernel<NG, false, 8>, (const void*)trace_kernel<NG, false, 9>,
-         (const void*)trace_kernel<NG, false, 10>, (const void*)trace_kernel<NG, false, 11>},
-        {(const void*)trace_kernel<NG, true, 8>, (const void*)trace_kernel<NG, true, 9>,
-         (const void*)trace_kernel<NG, true, 10>, (const void*)trace_kernel<NG, true, 11>}};
-    const size_t park_bytes = (size_t)park_fields(ns <= 0 ? 0 : 2) * 4 * TRACE_BLOCK_P;
-    const bool park = !tex && mode == 0 && use_lds && lds + park_bytes + (prof ? PROF_LDS_BYTES : 0) <= (size_t)PARK_LDS_LIMIT;
-    // LDS shading cache beside the parked main kernel (not with the profiling variant)
-    const bool shade = park && ft && S.tri_ax && !prof &&
-                       lds + shade_bytes(S) + park_bytes <= (size_t)PARK_LDS_LIMIT;
-    // brute-force fast frames: the instance loop only (M_BRUTE), axis-plane triangles, parked
-    // state and the LDS shading cache beside the instance records
-    const size_t lds_br = lds_bytes(S, false, true, true);
-    const bool brute_k = brute && !tex && mode == 0 && !prof && S.tri_ax && lds_br + park_bytes <= (size_t)PARK_LDS_LIMIT;
-    // ordered tree in LDS but no room for the whole parking area beside the instance records
-    // (world16: 93 KB tree + 23 KB instances): partial parking, instances from global memory
-    const size_t lds_pt = lds_bytes(S, true, true, false, true);
-    const size_t part_bytes = (size_t)PART_FIELDS * 4 * TRACE_BLOCK_P;
-    // (textured frames too: the hit's atlas colour stays in registers)
-    const bool part_k = !brute_k && ft && (!park || tex) && mode == 0 && !prof && S.tri_ax && ns <= 0 &&
-                        lds_pt + part_bytes <= (size_t)PARK_LDS_LIMIT && !getenv("RT_NO_PART");
-    if (part_k) {
-        constexpr int PT = M_PARK | M_FT | M_AXIS | M_SHADE | M_PART;
-        fn = tex ? (const void*)trace_kernel<0, true, PT | M_TEX> : (const void*)trace_kernel<0, true, PT>;
-    } else if (brute_k) {
-        constexpr int BR = M_BRUTE | M_PARK | M_SHADE | M_AXIS;
-        fn = ns <= 0 ? (const void*)trace_kernel<0, true, BR> : ns <= 2 ? (const void*)trace_kernel<2, true, BR>
-                                                               : (const void*)trace_kernel<NG, true, BR>;
-    } else if (tex && ft) {                                    // textured fast frames: ordered LBVH, unparked
-        constexpr int TF = M_TEX | M_FT, TA = M_TEX | M_FT | M_AXIS;
-        fn = S.tri_ax ? (ns <= 2 ? (const void*)trace_kernel<2, true, TA> : (const void*)trace_kernel<NG, true, TA>)
-                      : (ns <= 2 ? (const void*)trace_kernel<2, true, TF> : (const void*)trace_kernel<NG, true, TF>);
-    } else if (tex) {
-        fn = textured[use_lds ? 1 : 0][mode];
-    } else if (ft && park && S.tri_ax && prof) {
-        constexpr int PP = M_PARK | M_FT | M_AXIS | M_PROF;
-        fn = ns <= 0 ? (const void*)trace_kernel<0, true, PP> : ns <= 2 ? (const void*)trace_kernel<2, true, PP>
-                                                                 : (const void*)trace_kernel<NG, true, PP>;
-    } else if (ft && park && S.tri_ax && shade) {
-        constexpr int PS = M_PARK | M_FT | M_AXIS | M_SHADE;
-        fn = ns <= 0 ? (const void*)trace_kernel<0, true, PS> : ns <= 2 ? (const void*)trace_kernel<2, true, PS>
-                                                                 : (const void*)trace_kernel<NG, true, PS>;
-    } else if (ft && park && S.tri_ax) {
-        constexpr int PA = M_PARK | M_FT | M_AXIS;
-        fn = ns <= 0 ? (const void*)trace_kernel<0, true, PA> : ns <= 2 ? (const void*)trace_kernel<2, true, PA>
-                                                                 : (const void*)trace_kernel<NG, true, PA>;
-    } else if (ft) {
-        constexpr int PF = M_PARK | M_FT;
-        fn = park ? (ns <= 0 ? (const void*)trace_kernel<0, true, PF> : ns <= 2 ? (const void*)trace_kernel<2, true, PF>
-                                                                         : (const void*)trace_kernel<NG, true, PF>)
-                  : (ns <= 0 ? (const void*)trace_kernel<0, true, M_FT> : ns <= 2 ? (const void*)trace_kernel<2, true, M_FT>
-                                                                           : (const void*)trace_kernel<NG, true, M_FT>);
-    } else if (park) {
-        fn = ns <= 0 ? (const void*)trace_kernel<0, true, M_PARK> : ns <= 2 ? (const void*)trace_kernel<2, true, M_PARK>
-                     : (const void*)trace_kernel<NG, true, M_PARK>;
-    } else if (mode != 0 || ns > 2) fn = generic[use_lds ? 1 : 0][mode];
-    else if (use_lds) fn = ns <= 0 ? (const void*)trace_kernel<0, true, 0> : (const void*)trace_kernel<2, true, 0>;
-    else fn = ns <= 0 ? (const void*)trace_kernel<0, false, 0> : (const void*)trace_kernel<2, false, 0>;
-    const size_t shm = part_k ? lds_pt + part_bytes : brute_k ? lds_br + park_bytes
-                               : (park ? lds + park_bytes : use_lds ? lds : 0) + (shade ? shade_bytes(S) : 0) +
-                                     (prof ? PROF_LDS_BYTES : 0);
-    if (shm > 64 * 1024) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-    int per_cu = 1;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, TRACE_BLOCK_P, shm) != hipSuccess || per_cu < 1) per_cu = 1;
-    // sky pre-pass: the fast (ordered-LBVH) kernels, one round of samples, a tree to test
-    // (brute-force frames: the instances' grown boxes instead, when the pruning claim holds)
-    const bool sky_brute = brute_k && !prof && !want_stats && spp <= 64 && S.prune_abs >= 0.0f && S.n_inst >= 1 &&
-                           S.n_inst <= 64 && !getenv("RT_NO_BRUTE_SKY");
-    const bool sky = (ft && !prof && spp <= 64 && S.use_bvh && S.n_leaf > 0) || sky_brute;
-    return TraceVariant{fn, shm, per_cu, part_k, sky, sky_brute};
+    TraceVariant v{};
+    static_cast<TraceKey&>(v) = trace_variant_key(S, spp, tex, want_stats, prof, ns, getenv("RT_NO_PART") != nullptr,
+                                                  getenv("RT_NO_BRUTE_SKY") != nullptr);
+    v.per_cu = 1;
+    for (const TraceEntry& e : trace_kernels)
+        if (e.ns == v.ns_bucket && e.lds == v.lds && e.mode == v.mode) v.fn = e.fn;
+    if (!v.fn) return v;                                       // no such kernel: the caller reports the key
+    if (v.shm > 64 * 1024) (void)hipFuncSetAttribute(v.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v.shm);
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&v.per_cu, v.fn, TRACE_BLOCK_P, v.shm) != hipSuccess || v.per_cu < 1)
+        v.per_cu = 1;
+    return v;
 }
 
 hipError_t launch_sky(bool brute, int blocks, TraceParams& P, SceneView& S, unsigned char* gsky, int* live,

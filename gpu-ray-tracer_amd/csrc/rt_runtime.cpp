@@ -450,15 +450,6 @@ int ensure_atlas(rt_scene* s) {
     return RT_OK;
 }
 
-// A factor coprime with the queue length, so t -> t * f mod len is a permutation
-// (checked with gcd; f near len * 0.618 spreads consecutive tickets across the image).
-int ticket_scramble(int len) {
-    if (len <= 2) return 1;
-    int f = (int)(len * 0.6180339887) | 1;
-    while (std::gcd(f % len, len) != 1) f++;
-    return f % len;
-}
-
 // (Re)allocate / reset the current slot's scheduling history when the launch layout changes.
 int ensure_history(rt_scene* s, int n_groups, const long long* key, hipStream_t st) {
     int r;
@@ -552,163 +543,92 @@ SceneView view_of(const rt_scene* s, bool use_bvh) {
     return v;
 }
 
-bool opaque_scene(const rt_scene* s) {
-    for (const DMat& m : s->h.d_mats) if (m.refractive) return false;
-    return true;
+// Bind the slot's scheduling history for a frame of mode `hist` (history_mode: 1 or 2): the
+// previous frame's buffers to read, the other parity's to record into.  Returns that parity,
+// which is the slot's from now on.
+int bind_history(TraceParams& P, FrameSlot& f, int hist, int heavy_q) {
+    const int prev = f.hist_parity, next = 1 - prev;
+    P.hist = hist;
+    P.heavy_q = heavy_q;
+    P.hl_prev = f.d_hlist[prev]; P.hl_next = f.d_hlist[next];
+    P.hf_prev = f.d_hflag[prev]; P.hf_next = f.d_hflag[next];
+    P.hctl_prev = f.d_hctl + 2 * prev; P.hctl_next = f.d_hctl + 2 * next;
+    f.hist_parity = next;
+    return next;
 }
 
-int launch_trace(rt_scene* s, const rt_render_opts& o, hipStream_t st, uint32_t* rgba, int* dbg, int dbg_x, int dbg_y,
-                 bool want_stats, int occl_force = -1, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr,
-                 bool prof = false, unsigned* gdur = nullptr, int* geo = nullptr) {
-    TraceParams P{};
-    P.gdur = gdur;
+// What a trace launch is asked for beside the render options (each caller sets what it uses).
+struct TraceRequest {
+    hipStream_t stream = nullptr;
+    uint32_t* rgba = nullptr;
+    int* dbg = nullptr; int dbg_x = -1, dbg_y = -1;           // debug_cast's event log and its pixel
+    bool want_stats = false;                                   // the counted kernel (d_stats)
+    int occl_force = -1;                                       // shade_shortcuts
+    hipEvent_t e0 = nullptr, e1 = nullptr;                     // timestamps taken by the dispatches themselves
+    bool prof = false;                                         // the fast kernel's profiling variant (M_PROF)
+    unsigned* gdur = nullptr;                                  // per-group durations (rt_profile_groups)
+    int* geo = nullptr;                                        // out: {n_groups, gw, gh, n_gx}
+};
+
+// Fill TraceParams from the launch plan (rt_plan.h), ensure the slot's buffers, launch.
+int launch_trace(rt_scene* s, const rt_render_opts& o, const TraceRequest& q) {
+    hipStream_t st = q.stream;
     FrameSlot& f = s->cur();
     const rt::Scene& h = s->h;
-    P.cam = h.d_cam; P.dist_atten = h.dist_atten; P.ambience = h.ambience;
-    P.W = h.cam.W; P.H = h.cam.H; P.row0 = o.row0; P.row_step = o.row_step;
-    P.n_rows = (P.H - o.row0 + o.row_step - 1) / o.row_step;
-    if (P.n_rows <= 0) {
-        if (e0) { HIPCHK(hipEventRecord(e0, st)); HIPCHK(hipEventRecord(e1, st)); }
+    const FrameGeometry g = frame_geometry(h.cam.W, h.cam.H, o.row0, o.row_step, o.spp);
+    if (g.n_rows <= 0) {
+        if (q.e0) { HIPCHK(hipEventRecord(q.e0, st)); HIPCHK(hipEventRecord(q.e1, st)); }
         return RT_OK;
     }
+    TraceParams P{};
+    P.gdur = q.gdur;
+    P.cam = h.d_cam; P.dist_atten = h.dist_atten; P.ambience = h.ambience;
+    P.W = h.cam.W; P.H = h.cam.H; P.row0 = o.row0; P.row_step = o.row_step; P.n_rows = g.n_rows;
     P.compact = o.compact; P.spp = o.spp; P.depth = h.depth;
     P.spp_recip = (o.spp & (o.spp - 1)) == 0 ? 1.0f / (float)o.spp : 0.0f;
     P.spp_off = s->d_spp;
-    P.rgba = rgba; P.radiance = reinterpret_cast<float4*>(o.radiance); P.hit_inst = o.hit_inst; P.hit_tri = o.hit_tri;
-    P.stats = (want_stats || prof) ? s->d_stats : nullptr; P.dbg_log = dbg; P.dbg_x = dbg_x; P.dbg_y = dbg_y;
+    P.rgba = q.rgba; P.radiance = reinterpret_cast<float4*>(o.radiance); P.hit_inst = o.hit_inst; P.hit_tri = o.hit_tri;
+    P.stats = (q.want_stats || q.prof) ? s->d_stats : nullptr; P.dbg_log = q.dbg; P.dbg_x = q.dbg_x; P.dbg_y = q.dbg_y;
     if (o.textures) {
         int r;
         if ((r = ensure_atlas(s)) != RT_OK) return r;
         P.atlas = s->d_atlas; P.atlas_w = s->h.atlas_w; P.atlas_h = s->h.atlas_h;
     }
     SceneView S = view_of(s, o.use_bvh != 0);
-    // sample-parallel mapping: L lanes per pixel (one sample each per round), 64/L pixels per wave
-    P.lanes_per_px = std::min(o.spp, 64);
-    P.px_per_wave = 64 / P.lanes_per_px;
-    int gw = 1;
-    if ((P.px_per_wave & (P.px_per_wave - 1)) == 0) { while (gw * gw < P.px_per_wave) gw <<= 1; }
-    else gw = P.px_per_wave;
-    // Row slices with rows >= 8 frame rows apart (N >= 8 ranks): a 2-row group would pair
-    // rows that far apart, so groups are one row (8 x 1 at 8 spp).  Measured with four frames
-    // in flight: 8-way slice 0.234 -> 0.229 ms; whole frames and 2-way slices keep 4 x 2
-    // (8 x 1 there: +3.4% / +2%; profiles/r01/ab_group_shape_v31.log).
-    if (o.row_step >= 8) gw = P.px_per_wave;
-    P.gw = gw; P.gh = P.px_per_wave / gw;
-    auto log2_exact = [](int v) { int k = 0; while ((1 << k) < v) k++; return (1 << k) == v ? k : -1; };
-    P.l_shift = log2_exact(P.lanes_per_px); P.gw_shift = log2_exact(P.gw);
-    P.n_gx = (P.W + P.gw - 1) / P.gw;
-    P.n_groups = P.n_gx * ((P.n_rows + P.gh - 1) / P.gh);
-    if (geo) { geo[0] = P.n_groups; geo[1] = P.gw; geo[2] = P.gh; geo[3] = P.n_gx; }
-    P.scramble = ticket_scramble((P.n_groups + NQ - 1) / NQ);
-    P.scramble_small = (unsigned long long)((P.n_groups + NQ - 1) / NQ + TPC) * (unsigned long long)P.scramble < (1ull << 32);
-    P.div_ngx = udiv_make((unsigned)P.n_gx);
-    P.div_perq = udiv_make((unsigned)((P.n_groups + NQ - 1) / NQ));
+    P.lanes_per_px = g.lanes_per_px; P.px_per_wave = g.px_per_wave; P.gw = g.gw; P.gh = g.gh;
+    P.l_shift = g.l_shift; P.gw_shift = g.gw_shift; P.n_gx = g.n_gx; P.n_groups = g.n_groups;
+    if (q.geo) { q.geo[0] = g.n_groups; q.geo[1] = g.gw; q.geo[2] = g.gh; q.geo[3] = g.n_gx; }
+    P.scramble = g.scramble; P.scramble_small = g.scramble_small;
+    P.div_ngx = g.div_ngx; P.div_perq = g.div_perq;
     P.work = f.d_work; P.tpc = TPC;
-    {   // unlit skip (trace_sample, ST_LIGHT): every incoming light must be >= +0 and finite
-        bool ok = !want_stats && !dbg;                        // (the PROF variant profiles the fast frame: on)
-        auto pos0 = [](float v) { return std::isfinite(v) && !std::signbit(v); };
-        for (const DLight& l : h.d_lights) ok = ok && pos0(l.col.x) && pos0(l.col.y) && pos0(l.col.z) && pos0(l.col.w);
-        for (const DMat& m : h.d_mats)
-            ok = ok && pos0(m.Kt.x) && pos0(m.Kt.y) && pos0(m.Kt.z) && pos0(m.Kt.w) && m.Kt.x <= 1.0f && m.Kt.y <= 1.0f &&
-                 m.Kt.z <= 1.0f && m.Kt.w <= 1.0f;
-        bool start_ok = true;                                  // no -0 channel in Ke + Ka * ambience (org_light)
-        for (const DMat& m : h.d_mats) {
-            const V4 o = m.Ke + m.Ka * h.ambience;
-            for (float v : {o.x, o.y, o.z, o.w}) start_ok = start_ok && !(v == 0.0f && std::signbit(v));
-        }
-        P.unlit_skip = ok ? (start_ok ? 2 : 1) : 0;
-    }
-    P.occl_exit = (opaque_scene(s) && (occl_force == 1 || (occl_force < 0 && !want_stats))) ? 1 : 0;
+    const ShadeShortcuts sc = shade_shortcuts(h, q.want_stats, q.dbg != nullptr, q.occl_force);
+    P.unlit_skip = sc.unlit_skip; P.occl_exit = sc.occl_exit;
     if (!f.work_zeroed) HIPCHK(hipMemsetAsync(f.d_work, 0, WORK_INTS * sizeof(int), st));
-    // suspended frames needed (<= MAX_FRAMES - 1); none without a refractive material, where a
-    // reflection child replaces its parent (trace_sample, F_REFLECT)
-    // (NS = 0 kernels assume that: a depth-0 scene with refraction takes the NS = 2 bucket)
-    const int ns = opaque_scene(s) ? 0 : std::max(h.depth, 1);
-    const TraceVariant V = choose_trace_variant(S, o.spp, o.textures != 0, want_stats, prof, ns);
-    const int per_cu = V.per_cu;
-    const int waves_needed = P.n_groups;
-    // Frames in flight: a launch issued while the scene's previous frame is still running takes
-    // half the CUs.  A persistent block holds its CU (the LDS image) until its slowest wave
-    // ends; fewer blocks, each running twice the groups, leave fewer CUs held by one wave's last
-    // group, and two frames' blocks still cover the GPU.  Measured with four in flight
-    // (tools/pipe_slices.py, per-rank ms per frame at N = 1/2/4/8, same box): 0.655-0.665 /
-    // 0.374 / 0.226 / 0.156-0.157 with every CU, 0.646-0.654 / 0.347-0.354 / 0.200-0.205 /
-    // 0.137-0.140 with half; 3/8, 5/8 and 3/4 of the CUs in between (profiles/r03/ab_grid/).
-    // A frame issued alone (no other frame running) keeps every CU.  Requiring two or three
-    // running frames instead of one measured the same (profiles/r03/ab_grid/grid2.log).  A
-    // pipeline that copies every frame to the host measured 12% slower this way, with the copy
-    // anywhere (render stream, copy stream, high priority, fewer blit workgroups) and with the
-    // optional second half of the grid gated on later frames being queued
-    // (profiles/r03/ab_grid/readback.log): such callers set RT_OVERLAP_FULL.
-    int cap = s->n_cu * per_cu;
-    // another frame of the scene still in flight (any slot count, any overlap policy): the heavy
-    // list's static dealing below is for frames whose blocks all start at once
+    const TraceVariant V = choose_trace_variant(S, o.spp, o.textures != 0, q.want_stats, q.prof, sc.ns);
+    if (!V.fn)
+        return fail(RT_ERR_STATE, "no trace kernel <" + std::to_string(V.ns_bucket) + ", " + std::to_string((int)V.lds) + ", " +
+                                      std::to_string(V.mode) + ">");
+    // another frame of the scene still in flight (grid_policy)
     bool other_running = false;
     for (int i = 1; i < s->n_slots && !other_running; i++) {
         const int sl = (s->cur_slot + s->n_slots - i) % s->n_slots;
         other_running = s->slots[sl].pending && hipEventQuery(s->slots[sl].done) == hipErrorNotReady;
     }
-    if (s->n_slots >= 4 && s->overlap != RT_OVERLAP_FULL) {
-        const bool running = s->overlap == RT_OVERLAP_STREAM || other_running;   // or a stream
-        // Small frames (row slices of N >= 4 ranks: under ~48 groups per wave on half the CUs)
-        // take a quarter: four frames' blocks share the GPU, each block runs twice the groups,
-        // so its LDS staging and its slowest wave's tail weigh half as much.  Measured per-rank
-        // ms per frame, 60-frame streams, same box (profiles/r04/grid_div.log): N = 8 0.112 ->
-        // 0.101, N = 4 0.175 -> 0.171; whole frames unchanged by it (0.597 / 0.599), kept at half.
-        const long long half_waves = (long long)(cap / 2) * (TRACE_BLOCK_P / 64);
-        // (Not with virtual ranks, several slices of one frame per device from one scene: those
-        // slices share frame slots, and a quarter measured slower there: --gpus 1 --ranks 8 per
-        // slice 0.153 -> 0.173 ms, profiles/r04/grid_div.log.)
-        const int div = ((long long)P.n_groups < RT_SMALL_FRAME_GPW * half_waves && s->ranks_per_device == 1) ? 4 : 2;
-        if (running) cap = std::max(1, cap / div);
-    }
-    int blocks = std::min(cap, (waves_needed + TRACE_BLOCK_P / 64 - 1) / (TRACE_BLOCK_P / 64));
-    blocks = std::max(blocks, 1);
-    P.grid_waves = blocks * (TRACE_BLOCK_P / 64);              // the launch below: dim3(blocks)
-    // every block starts at once: a full grid and no other frame of the scene running (RT_OVERLAP_FULL
-    // and 2-3 frame slots keep the full grid for overlapping frames; those frames keep the counter)
-    P.heavy_static = (blocks == s->n_cu * per_cu && !other_running) ? 1 : 0;
-    P.heavy_cap = std::max(2 * blocks * (TRACE_BLOCK_P / 64), P.n_groups / 4);   // a bound, not a target
-    // longest-first history (fast frames): valid while the launch layout is unchanged
-    // Only where a wave runs few groups (1080p 8-way row slices: ~8 per wave): with more (63
-    // for a whole 1080p frame, 16 for a 4-way slice) the dynamic queues already balance the
-    // frame and the two clock reads per group cost as much as the shorter tail saves or more
-    // (measured, four frames in flight, ms per frame with / without: whole frame 0.919 / 0.914,
-    // 4-way 0.360 / 0.360, 8-way 0.179-0.186 / 0.200-0.204; profiles/r02/hist_policy.log).
-    P.hist = 0;
-    const long long waves = (long long)blocks * (TRACE_BLOCK_P / 64);
-    const bool sky = V.sky;                                    // sky pre-pass (choose_trace_variant)
-    // Heavy-first by work (hist = 2) where groups per wave are many: a group whose samples took
-    // >= heavy_q wave queries (mirror pixels: primary, shadow and reflection chains) is flagged,
-    // and the next frame of the slot runs the flagged groups first off a heavy live list the sky
-    // pre-pass builds.  No clock reads (the timed history's cost, item 17), one byte store per
-    // heavy group.  RT_HEAVY_Q (environment) sets heavy_q; 0 turns it off.
-    // The mode must not depend on the grid (half or whole, frames in flight or alone): the two
-    // modes' flags mean different things (hist = 1 flags only the groups on its heavy list and
-    // skips them in the normal queues; hist = 2 flags by work and lists nothing), so the history
-    // key includes the mode and a change of mode resets the flags.
+    const GridPlan grid = grid_policy(s->n_cu, V.per_cu, g.n_groups, s->n_slots, s->overlap, other_running, s->ranks_per_device);
+    P.grid_waves = grid.grid_waves; P.heavy_static = grid.heavy_static; P.heavy_cap = grid.heavy_cap;
     static const int heavy_q = [] { const char* e = getenv("RT_HEAVY_Q"); return e ? atoi(e) : RT_HEAVY_Q_DEFAULT; }();
-    const long long full_waves = (long long)s->n_cu * per_cu * (TRACE_BLOCK_P / 64);
-    const bool hist2 = !want_stats && !dbg && sky && heavy_q > 0;
-    const bool hist1 = !hist2 && !want_stats && !dbg && (prof || (long long)P.n_groups <= RT_HIST_GROUPS_PER_WAVE * full_waves);
-    (void)waves;
-    if (hist1 || hist2) {
-        const long long key[8] = {P.W, P.H, P.row0, P.row_step, P.n_rows, P.spp, P.n_groups,
-                                  (long long)o.textures | (hist2 ? 2 : 1) << 8};
+    const long long full_waves = (long long)s->n_cu * V.per_cu * (TRACE_BLOCK_P / 64);
+    const int hist = history_mode(q.want_stats, q.dbg != nullptr, V.sky, q.prof, heavy_q, g.n_groups, full_waves);
+    if (hist) {
+        const long long key[8] = {P.W, P.H, P.row0, P.row_step, P.n_rows, P.spp, P.n_groups, (long long)o.textures | hist << 8};
         int r;
         if ((r = ensure_history(s, P.n_groups, key, st)) != RT_OK) return r;
-        const int prev = f.hist_parity, next = 1 - prev;
-        P.hist = hist1 ? 1 : 2;
-        P.heavy_q = heavy_q;
-        P.hl_prev = f.d_hlist[prev]; P.hl_next = f.d_hlist[next];
-        P.hf_prev = f.d_hflag[prev]; P.hf_next = f.d_hflag[next];
-        P.hctl_prev = f.d_hctl + 2 * prev; P.hctl_next = f.d_hctl + 2 * next;
-        if (hist1 && f.hctl_zeroed != next) HIPCHK(hipMemsetAsync(f.d_hctl + 2 * next, 0, 2 * sizeof(unsigned long long), st));
-        f.hist_parity = next;
+        const int next = bind_history(P, f, hist, heavy_q);
+        if (hist == 1 && f.hctl_zeroed != next) HIPCHK(hipMemsetAsync(f.d_hctl + 2 * next, 0, 2 * sizeof(unsigned long long), st));
     }
     f.work_zeroed = false;                                    // this launch consumes the counters
     f.hctl_zeroed = -1;
-    if (sky) {
+    if (V.sky) {
         int r;
         if ((r = ensure_layout(s, P.n_groups, true, false)) != RT_OK) return r;
         const Layout l = layout_of(P.n_groups);
@@ -716,10 +636,31 @@ int launch_trace(rt_scene* s, const rt_render_opts& o, hipStream_t st, uint32_t*
         P.live = f.d_live; P.live_cap = l.live_q;
         P.tpc = (V.part_k && P.lanes_per_px == 64) ? RT_TPC_WIDE : RT_TPC_LIVE;
         // (brute-force frames: the grown boxes' slack)
-        HIPCHK(launch_sky(V.sky_brute, l.sky_blocks, P, S, f.d_gsky, f.d_live, s->d_mesh_box, S.prune_abs, 0x1p-12f, st, e0));
+        HIPCHK(launch_sky(V.sky_brute, l.sky_blocks, P, S, f.d_gsky, f.d_live, s->d_mesh_box, S.prune_abs, 0x1p-12f, st, q.e0));
     }
-    HIPCHK(launch_trace_kernel(V, blocks, P, S, st, sky ? nullptr : e0, e1));
+    HIPCHK(launch_trace_kernel(V, grid.blocks, P, S, st, V.sky ? nullptr : q.e0, q.e1));
     HIPCHK(hipGetLastError());
+    return RT_OK;
+}
+
+// The side entries' prologue (debug_cast, experiments, profiles; they do not rotate slots): the
+// scene on its device, the sample offsets, the scene's stream waiting for every frame in flight
+// (any slot), and with `bvh` the current slot's BVH rebuilt.
+int begin_side_entry(rt_scene* s, int spp, bool bvh) {
+    int r;
+    if ((r = upload(s)) != RT_OK) return r;
+    HIPCHK(hipSetDevice(s->device));
+    if ((r = ensure_spp(s, spp)) != RT_OK) return r;
+    if ((r = begin_frame(s, sstream(s), true)) != RT_OK) return r;   // nothing else in flight on this slot
+    return bvh ? build_bvh(s, sstream(s)) : RT_OK;
+}
+
+// Zero the counters; the two minima (slots 15 and 19: the waves' earliest start and earliest end,
+// trace_kernel) start at all ones.
+int clear_stats(rt_scene* s, hipStream_t st) {
+    HIPCHK(hipMemsetAsync(s->d_stats, 0, STATS_N * sizeof(unsigned long long), st));
+    HIPCHK(hipMemsetAsync(s->d_stats + 15, 0xff, sizeof(unsigned long long), st));
+    HIPCHK(hipMemsetAsync(s->d_stats + 19, 0xff, sizeof(unsigned long long), st));
     return RT_OK;
 }
 
@@ -1144,8 +1085,10 @@ int rt_render(rt_scene* s, const rt_render_opts* o, rt_stats* stats) {
         oo.hit_inst = o->hit_inst ? (int32_t*)s->d_out[2] : nullptr;
         oo.hit_tri = o->hit_tri ? (int32_t*)s->d_out[3] : nullptr;
     }
-    uint32_t* rgba = oo.rgba ? oo.rgba : s->d_canvas;
-    if ((r = launch_trace(s, oo, st, rgba, nullptr, -1, -1, timed, -1, te ? te[2] : nullptr, te ? te[3] : nullptr)) != RT_OK) {
+    TraceRequest q;
+    q.stream = st; q.rgba = oo.rgba ? oo.rgba : s->d_canvas; q.want_stats = timed;
+    if (te) { q.e0 = te[2]; q.e1 = te[3]; }
+    if ((r = launch_trace(s, oo, q)) != RT_OK) {
         if (te) s->tev_used -= 4;
         return r;
     }
@@ -1248,17 +1191,15 @@ int rt_debug_cast(rt_scene* s, int x, int y, char* buf, int64_t cap) {   // rayt
     CHECK_FINISHED(s);
     if (x < 0 || y < 0 || x >= s->h.cam.W || y >= s->h.cam.H) return fail(RT_ERR_ARG, "pixel out of range");
     int r;
-    if ((r = upload(s)) != RT_OK) return r;
-    HIPCHK(hipSetDevice(s->device));
-    if ((r = ensure_spp(s, 1)) != RT_OK) return r;
     // rebuilds the current slot's BVH: first wait for every frame in flight (any slot)
-    if ((r = begin_frame(s, sstream(s), true)) != RT_OK) return r;
-    if ((r = build_bvh(s, sstream(s))) != RT_OK) return r;
+    if ((r = begin_side_entry(s, 1, true)) != RT_OK) return r;
     HIPCHK(hipMemsetAsync(s->d_dbg, 0, 4096 * sizeof(int), sstream(s)));
     rt_render_opts o;
     rt_render_opts_default(&o);
     o.row0 = y; o.row_step = s->h.cam.H;                                  // just the row of (x, y)
-    if ((r = launch_trace(s, o, sstream(s), s->d_canvas, s->d_dbg, x, y, true)) != RT_OK) return r;
+    TraceRequest q;
+    q.stream = sstream(s); q.rgba = s->d_canvas; q.dbg = s->d_dbg; q.dbg_x = x; q.dbg_y = y; q.want_stats = true;
+    if ((r = launch_trace(s, o, q)) != RT_OK) return r;
     if ((r = end_frame(s, sstream(s))) != RT_OK) return r;
     std::vector<int> log(4096);
     HIPCHK(hipStreamSynchronize(sstream(s)));
@@ -1281,21 +1222,17 @@ int rt_experiment(rt_scene* s, int which, int spp, int reps, double* ms, uint64_
     int r;
     if (which == 4 || which == 5 || which == 6) {             // full frame: counted kernel (4: occlusion exit on),
                                                               // 6: the fast kernel's profiling variant (M_PROF)
-        if ((r = upload(s)) != RT_OK) return r;
-        HIPCHK(hipSetDevice(s->device));
-        if ((r = ensure_spp(s, spp)) != RT_OK) return r;
+        if ((r = begin_side_entry(s, spp, true)) != RT_OK) return r;
         rt_render_opts o; rt_render_opts_default(&o); o.spp = spp;
-        if ((r = begin_frame(s, sstream(s), true)) != RT_OK) return r;   // nothing else in flight on this slot
-        if ((r = build_bvh(s, sstream(s))) != RT_OK) return r;
+        TraceRequest q;
+        q.stream = sstream(s); q.rgba = s->d_canvas;
+        if (which == 6) q.prof = true;
+        else { q.want_stats = true; q.occl_force = which == 4 ? 1 : 0; }
         float total = 0;
         for (int i = 0; i < reps; i++) {
-            HIPCHK(hipMemsetAsync(s->d_stats, 0, STATS_N * sizeof(unsigned long long), sstream(s)));
-            HIPCHK(hipMemsetAsync(s->d_stats + 15, 0xff, sizeof(unsigned long long), sstream(s)));
-            HIPCHK(hipMemsetAsync(s->d_stats + 19, 0xff, sizeof(unsigned long long), sstream(s)));
+            if ((r = clear_stats(s, sstream(s))) != RT_OK) return r;
             HIPCHK(hipEventRecord(s->ev[0], sstream(s)));
-            if ((r = (which == 6 ? launch_trace(s, o, sstream(s), s->d_canvas, nullptr, -1, -1, false, -1, nullptr, nullptr, true)
-                                 : launch_trace(s, o, sstream(s), s->d_canvas, nullptr, -1, -1, true, which == 4 ? 1 : 0))) != RT_OK)
-                return r;
+            if ((r = launch_trace(s, o, q)) != RT_OK) return r;
             HIPCHK(hipEventRecord(s->ev[1], sstream(s)));
             HIPCHK(hipEventSynchronize(s->ev[1]));
             float t = 0; HIPCHK(hipEventElapsedTime(&t, s->ev[0], s->ev[1]));
@@ -1317,32 +1254,22 @@ int rt_frame_work(rt_scene* s, const rt_render_opts* o, rt_work* w) {
     if (o->spp < 1 || o->spp > 64 || o->row_step < 1 || o->row0 < 0 || !o->use_bvh || o->textures)
         return fail(RT_ERR_ARG, "rt_frame_work: BVH frames, 1 <= spp <= 64, untextured");
     int r;
-    if ((r = upload(s)) != RT_OK) return r;
-    HIPCHK(hipSetDevice(s->device));
-    if ((r = ensure_spp(s, o->spp)) != RT_OK) return r;
+    if ((r = begin_side_entry(s, o->spp, true)) != RT_OK) return r;
     const size_t rows = (s->h.cam.H > o->row0) ? (size_t)(s->h.cam.H - o->row0 + o->row_step - 1) / o->row_step : 0;
-    uint32_t* d_rgba = nullptr;
-    HIPCHK(hipMalloc((void**)&d_rgba, std::max<size_t>(1, (o->compact ? rows : (size_t)s->h.cam.H) * s->h.cam.W) * 4));
+    DevBuf<uint32_t> d_rgba;
+    HIPCHK(d_rgba.alloc(std::max<size_t>(1, (o->compact ? rows : (size_t)s->h.cam.H) * s->h.cam.W)));
     hipStream_t st = sstream(s);
-    r = begin_frame(s, st, true);                             // nothing else in flight on this slot
-    if (r == RT_OK) r = build_bvh(s, st);
-    if (r == RT_OK) {
-        HIPCHK(hipMemsetAsync(s->d_stats, 0, STATS_N * sizeof(unsigned long long), st));
-        HIPCHK(hipMemsetAsync(s->d_stats + 15, 0xff, sizeof(unsigned long long), st));
-        HIPCHK(hipMemsetAsync(s->d_stats + 19, 0xff, sizeof(unsigned long long), st));
-        rt_render_opts oo = *o;
-        oo.radiance = nullptr; oo.hit_inst = oo.hit_tri = nullptr;
-        r = launch_trace(s, oo, st, d_rgba, nullptr, -1, -1, false, -1, nullptr, nullptr, true);
-    }
-    if (r == RT_OK) r = end_frame(s, st);
+    if ((r = clear_stats(s, st)) != RT_OK) return r;
+    rt_render_opts oo = *o;
+    oo.radiance = nullptr; oo.hit_inst = oo.hit_tri = nullptr;
+    TraceRequest q;
+    q.stream = st; q.rgba = d_rgba.p; q.prof = true;
+    if ((r = launch_trace(s, oo, q)) != RT_OK) return r;
+    if ((r = end_frame(s, st)) != RT_OK) return r;
     unsigned long long v[STATS_N] = {};
-    if (r == RT_OK) {
-        HIPCHK(hipStreamSynchronize(st));
-        HIPCHK(hipMemcpy(v, s->d_stats, sizeof v, hipMemcpyDeviceToHost));
-        if (v[4] == 0 && rows > 0) r = fail(RT_ERR_STATE, "no profiling variant of the fast kernel for this scene");
-    }
-    (void)hipFree(d_rgba);
-    if (r != RT_OK) return r;
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipMemcpy(v, s->d_stats, sizeof v, hipMemcpyDeviceToHost));
+    if (v[4] == 0 && rows > 0) return fail(RT_ERR_STATE, "no profiling variant of the fast kernel for this scene");
     w->queries = v[0]; w->wave_queries = v[4]; w->pair_steps = v[5]; w->leaf_visits = v[6]; w->tri_iters = v[7];
     w->leaf_lanes = v[2];
     w->scene_bytes = scene_image_bytes(view_of(s, true));
@@ -1372,42 +1299,36 @@ int rt_profile_groups(rt_scene* s, int spp, int row0, int row_step, int reps, in
     CHECK_FINISHED(s);
     if (!out || !geo || cap <= 0 || reps < 1 || row_step < 1 || row0 < 0) return fail(RT_ERR_ARG, "bad arguments");
     int r;
-    if ((r = upload(s)) != RT_OK) return r;
-    HIPCHK(hipSetDevice(s->device));
-    if ((r = ensure_spp(s, spp)) != RT_OK) return r;
+    if ((r = begin_side_entry(s, spp, false)) != RT_OK) return r;   // (the BVH: per repetition, below)
     const int rows = (s->h.cam.H - row0 + row_step - 1) / row_step;
     if (rows <= 0) return fail(RT_ERR_ARG, "no rows in the slice");
     rt_render_opts o; rt_render_opts_default(&o);
     o.spp = spp; o.row0 = row0; o.row_step = row_step; o.compact = 1;
-    uint32_t* d_rgba = nullptr;
-    unsigned* d_g = nullptr;
-    HIPCHK(hipMalloc((void**)&d_rgba, (size_t)s->h.cam.W * rows * sizeof(uint32_t)));
+    DevBuf<uint32_t> d_rgba;
+    DevBuf<unsigned> d_g;
+    HIPCHK(d_rgba.alloc((size_t)s->h.cam.W * rows));
     geo[0] = geo[1] = geo[2] = geo[3] = 0;
     reps = std::max(reps, 2);                                 // frame 0 sizes the buffer and seeds the history
     const int nw = prof ? 13 : 1;                             // prof: + 12 counters per group (PROF kernel)
-    if ((r = begin_frame(s, sstream(s), true)) != RT_OK) { (void)hipFree(d_rgba); return r; }
-    for (int i = 0; i < reps && r == RT_OK; i++) {
-        const bool rec = i == reps - 1;
-        if (rec) {
-            if (geo[0] <= 0 || (int64_t)geo[0] * nw > cap) { r = fail(RT_ERR_LIMIT, "group buffer too small"); break; }
-            HIPCHK(hipMalloc((void**)&d_g, (size_t)geo[0] * nw * sizeof(unsigned)));
-            HIPCHK(hipMemsetAsync(d_g, 0, (size_t)geo[0] * nw * sizeof(unsigned), sstream(s)));
+    TraceRequest q;
+    q.stream = sstream(s); q.rgba = d_rgba.p; q.e0 = s->ev[0]; q.e1 = s->ev[1]; q.geo = geo;
+    for (int i = 0; i < reps; i++) {
+        if (i == reps - 1) {                                  // the recorded frame
+            if (geo[0] <= 0 || (int64_t)geo[0] * nw > cap) return fail(RT_ERR_LIMIT, "group buffer too small");
+            HIPCHK(d_g.alloc((size_t)geo[0] * nw));
+            HIPCHK(hipMemsetAsync(d_g.p, 0, (size_t)geo[0] * nw * sizeof(unsigned), sstream(s)));
+            q.prof = prof != 0; q.gdur = d_g.p;
         }
-        if ((r = build_bvh(s, sstream(s))) != RT_OK) break;
-        r = launch_trace(s, o, sstream(s), d_rgba, nullptr, -1, -1, false, -1, s->ev[0], s->ev[1], rec && prof,
-                         rec ? d_g : nullptr, geo);
+        if ((r = build_bvh(s, sstream(s))) != RT_OK) return r;
+        if ((r = launch_trace(s, o, q)) != RT_OK) return r;
     }
-    if (r == RT_OK) r = end_frame(s, sstream(s));
-    if (r == RT_OK) {
-        HIPCHK(hipEventSynchronize(s->ev[1]));
-        float t = 0;
-        HIPCHK(hipEventElapsedTime(&t, s->ev[0], s->ev[1]));
-        if (ms) *ms = t;
-        HIPCHK(hipMemcpy(out, d_g, (size_t)geo[0] * nw * sizeof(unsigned), hipMemcpyDeviceToHost));
-    }
-    (void)hipFree(d_rgba);
-    (void)hipFree(d_g);
-    return r;
+    if ((r = end_frame(s, sstream(s))) != RT_OK) return r;
+    HIPCHK(hipEventSynchronize(s->ev[1]));
+    float t = 0;
+    HIPCHK(hipEventElapsedTime(&t, s->ev[0], s->ev[1]));
+    if (ms) *ms = t;
+    HIPCHK(hipMemcpy(out, d_g.p, (size_t)geo[0] * nw * sizeof(unsigned), hipMemcpyDeviceToHost));
+    return RT_OK;
 }
 
 int rt_kat_device(const char* op, int n, const float* in0, const float* in1, const float* in2, float* of, int32_t* oi,
@@ -1430,27 +1351,24 @@ int rt_kat_device(const char* op, int n, const float* in0, const float* in1, con
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(RT_ERR_NODEV, "no HIP device available");
     HIPCHK(hipSetDevice(g_device));
     const float* hin[3] = {in0, in1, in2};
-    float* din[3] = {nullptr, nullptr, nullptr};
-    float* dof = nullptr; int* doi = nullptr; unsigned long long* dou = nullptr;
+    DevBuf<float> din[3], dof;
+    DevBuf<int> doi;
+    DevBuf<unsigned long long> dou;
     for (int i = 0; i < 3; i++)
         if (sz[k][i]) {
             if (!hin[i]) return fail(RT_ERR_ARG, "missing input");
-            HIPCHK(hipMalloc((void**)&din[i], (size_t)n * sz[k][i] * 4));
-            HIPCHK(hipMemcpy(din[i], hin[i], (size_t)n * sz[k][i] * 4, hipMemcpyHostToDevice));
+            HIPCHK(din[i].alloc((size_t)n * sz[k][i]));
+            HIPCHK(hipMemcpy(din[i].p, hin[i], (size_t)n * sz[k][i] * 4, hipMemcpyHostToDevice));
         }
-    if (sz[k][3]) HIPCHK(hipMalloc((void**)&dof, (size_t)n * sz[k][3] * 4));
-    if (sz[k][4]) HIPCHK(hipMalloc((void**)&doi, (size_t)n * sz[k][4] * 4));
-    if (sz[k][5]) HIPCHK(hipMalloc((void**)&dou, (size_t)n * 8));
-    launch_kat(k, n, din[0], din[1], din[2], dof, doi, dou);
+    if (sz[k][3]) HIPCHK(dof.alloc((size_t)n * sz[k][3]));
+    if (sz[k][4]) HIPCHK(doi.alloc((size_t)n * sz[k][4]));
+    if (sz[k][5]) HIPCHK(dou.alloc((size_t)n));
+    launch_kat(k, n, din[0].p, din[1].p, din[2].p, dof.p, doi.p, dou.p);
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
-    if (sz[k][3] && of) HIPCHK(hipMemcpy(of, dof, (size_t)n * sz[k][3] * 4, hipMemcpyDeviceToHost));
-    if (sz[k][4] && oi) HIPCHK(hipMemcpy(oi, doi, (size_t)n * sz[k][4] * 4, hipMemcpyDeviceToHost));
-    if (sz[k][5] && ou) HIPCHK(hipMemcpy(ou, dou, (size_t)n * 8, hipMemcpyDeviceToHost));
-    for (auto p : din) if (p) (void)hipFree(p);
-    if (dof) (void)hipFree(dof);
-    if (doi) (void)hipFree(doi);
-    if (dou) (void)hipFree(dou);
+    if (sz[k][3] && of) HIPCHK(hipMemcpy(of, dof.p, (size_t)n * sz[k][3] * 4, hipMemcpyDeviceToHost));
+    if (sz[k][4] && oi) HIPCHK(hipMemcpy(oi, doi.p, (size_t)n * sz[k][4] * 4, hipMemcpyDeviceToHost));
+    if (sz[k][5] && ou) HIPCHK(hipMemcpy(ou, dou.p, (size_t)n * 8, hipMemcpyDeviceToHost));
     return RT_OK;
 }
 
