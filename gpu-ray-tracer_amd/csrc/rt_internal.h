@@ -152,6 +152,11 @@ struct rt_scene {
     static constexpr int MAX_SLOTS = RT_MAX_SLOTS;
     rti::FrameSlot slots[MAX_SLOTS];             // slots[0, n_slots) are in rotation (FrameSlot)
     int n_slots = 1, cur_slot = 0;
+    // the most recent trace launch (rt_scene_last_trace): the key launch_trace launched with and
+    // the SceneView::ftree it saw; host state only
+    rtd::TraceKey last_key{};
+    int last_ftree = 0;
+    bool has_last_trace = false;
     rti::FrameSlot& cur() { return slots[cur_slot]; }
     const rti::FrameSlot& cur() const { return slots[cur_slot]; }
     ~rt_scene();

@@ -640,6 +640,7 @@ int launch_trace(rt_scene* s, const rt_render_opts& o, const TraceRequest& q) {
     }
     HIPCHK(launch_trace_kernel(V, grid.blocks, P, S, st, V.sky ? nullptr : q.e0, q.e1));
     HIPCHK(hipGetLastError());
+    s->last_key = V; s->last_ftree = S.ftree; s->has_last_trace = true;   // rt_scene_last_trace
     return RT_OK;
 }
 
@@ -1256,20 +1257,24 @@ int rt_frame_work(rt_scene* s, const rt_render_opts* o, rt_work* w) {
     int r;
     if ((r = begin_side_entry(s, o->spp, true)) != RT_OK) return r;
     const size_t rows = (s->h.cam.H > o->row0) ? (size_t)(s->h.cam.H - o->row0 + o->row_step - 1) / o->row_step : 0;
+    // the frame: the caller's device buffer, or a private one (dropped, or copied to the caller's host buffer)
+    const size_t out_px = (o->compact ? rows : (size_t)s->h.cam.H) * s->h.cam.W;
+    const bool to_caller = o->rgba && !o->host_outputs;
     DevBuf<uint32_t> d_rgba;
-    HIPCHK(d_rgba.alloc(std::max<size_t>(1, (o->compact ? rows : (size_t)s->h.cam.H) * s->h.cam.W)));
+    if (!to_caller) HIPCHK(d_rgba.alloc(std::max<size_t>(1, out_px)));
     hipStream_t st = sstream(s);
     if ((r = clear_stats(s, st)) != RT_OK) return r;
     rt_render_opts oo = *o;
     oo.radiance = nullptr; oo.hit_inst = oo.hit_tri = nullptr;
     TraceRequest q;
-    q.stream = st; q.rgba = d_rgba.p; q.prof = true;
+    q.stream = st; q.rgba = to_caller ? o->rgba : d_rgba.p; q.prof = true;
     if ((r = launch_trace(s, oo, q)) != RT_OK) return r;
     if ((r = end_frame(s, st)) != RT_OK) return r;
     unsigned long long v[STATS_N] = {};
     HIPCHK(hipStreamSynchronize(st));
     HIPCHK(hipMemcpy(v, s->d_stats, sizeof v, hipMemcpyDeviceToHost));
     if (v[4] == 0 && rows > 0) return fail(RT_ERR_STATE, "no profiling variant of the fast kernel for this scene");
+    if (o->rgba && o->host_outputs && out_px) HIPCHK(hipMemcpy(o->rgba, d_rgba.p, out_px * 4, hipMemcpyDeviceToHost));
     w->queries = v[0]; w->wave_queries = v[4]; w->pair_steps = v[5]; w->leaf_visits = v[6]; w->tri_iters = v[7];
     w->leaf_lanes = v[2];
     w->scene_bytes = scene_image_bytes(view_of(s, true));
@@ -1281,6 +1286,17 @@ int rt_frame_work(rt_scene* s, const rt_render_opts* o, rt_work* w) {
         w->hist_pair_steps[i] = v[PROF_HIST_PAIR + i];
         w->hist_leaf_visits[i] = v[PROF_HIST_LEAF + i];
     }
+    return RT_OK;
+}
+
+int rt_scene_last_trace(const rt_scene* s, int32_t* out8) {
+    CHECK_FINISHED(s);
+    if (!out8) return fail(RT_ERR_ARG, "null argument");
+    if (!s->has_last_trace) return fail(RT_ERR_STATE, "no trace launch yet");
+    const TraceKey& k = s->last_key;
+    const int32_t v[8] = {k.ns_bucket, (int32_t)k.lds, k.mode, (int32_t)k.shm, (int32_t)k.part_k, (int32_t)k.sky,
+                          (int32_t)k.sky_brute, s->last_ftree};
+    std::copy(v, v + 8, out8);
     return RT_OK;
 }
 

@@ -37,7 +37,7 @@ SYMBOLS = [
     "rt_builder_add_triangle_tex", "rt_builder_build_cube_tex", "rt_scene_set_atlas", "rt_scene_load_atlas",
     "rt_scene_atlas_info", "rt_scene_set_frame_slots", "rt_scene_set_overlap", "rt_frame_work",
     "rt_scene_set_devices", "rt_profile_marker", "rt_host_alloc", "rt_host_free", "rt_copy_to_host_async",
-    "rt_copy_engines_warm",
+    "rt_copy_engines_warm", "rt_scene_last_trace",
 ]
 
 
@@ -140,6 +140,7 @@ def lib():
     L.rt_scene_set_overlap.argtypes = [vp, ip]
     L.rt_frame_work.argtypes = [vp, ctypes.POINTER(RenderOpts), ctypes.POINTER(Work)]
     L.rt_scene_set_devices.argtypes = [vp, vp, ip, ip]
+    L.rt_scene_last_trace.argtypes = [vp, vp]
     if hasattr(L, "rt_profile_marker"):         # (absent from libraries older than ABI 3's round 5: A/B runs)
         L.rt_profile_marker.argtypes = [ip, vp]
     if hasattr(L, "rt_copy_to_host_async"):     # ABI 4
@@ -441,15 +442,28 @@ class Scene:
         _check(lib().rt_render(self._h, ctypes.byref(o), ctypes.byref(st) if stats else None))
         return st.as_dict() if stats else None
 
-    def frame_work(self, spp=1, row0=0, row_step=1, compact=True):
+    def frame_work(self, spp=1, row0=0, row_step=1, compact=True, want_rgba=False):
         """What the fast kernels do for this frame (rt_frame_work): queries issued after the
-        exact skips, wave-level traversal steps."""
+        exact skips, wave-level traversal steps.  want_rgba: also the profiling frame itself,
+        returned as (work, rgba)."""
         o = RenderOpts()
         lib().rt_render_opts_default(ctypes.byref(o))
         o.spp, o.row0, o.row_step, o.compact = spp, row0, row_step, int(compact)
+        rgba = None
+        if want_rgba:
+            rows = len(range(row0, self.height, row_step)) if compact else self.height
+            rgba = np.zeros((rows, self.width), np.uint32)
+            o.rgba, o.host_outputs = _ptr(rgba), 1
         w = Work()
         _check(lib().rt_frame_work(self._h, ctypes.byref(o), ctypes.byref(w)))
-        return w.as_dict()
+        return (w.as_dict(), rgba) if want_rgba else w.as_dict()
+
+    def last_trace(self):
+        """The trace kernel of the scene's most recent trace launch (rt_scene_last_trace)."""
+        v = np.zeros(8, np.int32)
+        _check(lib().rt_scene_last_trace(self._h, _ptr(v)))
+        keys = ["ns_bucket", "lds", "mode", "shm", "part_k", "sky", "sky_brute", "ftree"]
+        return dict(zip(keys, [int(x) for x in v]))
 
     def set_devices(self, devices, n_ranks=None):
         """Split every whole frame row-cyclically over `devices` from this process (n_ranks

@@ -25,8 +25,10 @@ extern "C" {
 /* 3: rt_work gained the query-occupancy fields; RT_EXPORT_TRIS / RT_EXPORT_TEXCOORDS list
  *    triangles in the flattened mesh order (the index space of hit_tri)
  * 4: rt_host_alloc / rt_host_free / rt_copy_to_host_async / rt_copy_engines_warm (host-readable
- *    frames through a copy engine); a finished scene is uploaded and warmed at creation when a gfx950 device is present */
-#define RT_ABI_VERSION 4
+ *    frames through a copy engine); a finished scene is uploaded and warmed at creation when a gfx950 device is present
+ * 5: rt_scene_last_trace (test hook: the trace kernel a launch used); rt_frame_work keeps its
+ *    frame when rt_render_opts.rgba is set */
+#define RT_ABI_VERSION 5
 
 enum {
     RT_OK = 0,
@@ -150,7 +152,7 @@ void rt_render_opts_default(rt_render_opts* o);
 int rt_render(rt_scene* s, const rt_render_opts* opts, rt_stats* stats);
 
 /* The work the fast (statistics-free) kernels do for one frame of `opts`, from a profiling
- * run of the fast kernel with wave-level counters (not timed, outputs discarded).  rt_stats
+ * run of the fast kernel with wave-level counters (not timed; the frame is kept on request, below).  rt_stats
  * counts the reference's units (every cast_ray of propagate_ray, raytracer.cu:17-43); the
  * fast kernel proves some of them unnecessary and skips them (unlit shadow rays, pruned
  * subtrees, occluded-shadow early exits): this is what it does instead. */
@@ -178,7 +180,11 @@ typedef struct rt_work {
     uint64_t hist_leaf_visits[8];   /* their leaf visits */
 } rt_work;
 /* BVH frames with 1 <= spp <= 64, untextured; RT_ERR_STATE when the scene has no profiling
- * variant (the fast kernel needs the ordered tree in LDS). */
+ * variant (the fast kernel needs the ordered tree in LDS).
+ * opts->rgba non-NULL: the profiling frame is rendered there (a device pointer, or with
+ * host_outputs a host pointer it is copied to, as rt_render does; indexed as `compact` says);
+ * NULL: the frame is dropped.  radiance / hit_inst / hit_tri are never written.  opts->stream is
+ * ignored: the call runs on the scene's own stream and returns when the frame is done. */
 int rt_frame_work(rt_scene* s, const rt_render_opts* opts, rt_work* work);
 
 /* Frame slots (1 = default, up to 8).  The reference rebuilds its BVH inside every
@@ -260,6 +266,14 @@ int rt_debug_cast(rt_scene* s, int x, int y, char* buf, int64_t cap);
  * Host pointers in/out. */
 int rt_kat_device(const char* op, int n, const float* in0, const float* in1, const float* in2,
                   float* out_f, int32_t* out_i, uint64_t* out_u);
+
+/* The trace kernel of the scene's most recent trace launch (test hook), from any entry that
+ * launches one (rt_render, rt_update_scene, rt_frame_work, rt_debug_cast): what the launch used,
+ * recorded when it was issued.  out8 = {NS, LDS, MODE of trace_kernel<NS, LDS, MODE>, dynamic LDS
+ * bytes, partial parking, sky pre-pass, sky pre-pass over the instances' boxes, ordered tree
+ * usable}.  RT_ERR_STATE before the first launch.  Host state only: no device call.  A scene
+ * split by rt_scene_set_devices launches on its replicas, which this does not see. */
+int rt_scene_last_trace(const rt_scene* s, int32_t out8[8]);
 
 /* Profiling hook: launches an empty marker kernel of `tag` (1..64) workgroups on `stream` (a
  * hipStream_t; NULL = the default stream), so a rocprofv3 kernel or counter trace can find the

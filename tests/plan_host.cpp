@@ -3,6 +3,12 @@
 // machine without a GPU.  Host pass only; nothing calls HIP.
 //   plan_host variants                          one line per case of the grid below:
 //                                               ns_bucket lds mode shm part_k sky sky_brute
+//   plan_host key n_inst n_real ftree tri_ax use_bvh n_tris n_mats n_lights n_meshes prune_abs
+//                 spp tex stats prof ns no_part no_brute_sky
+//                                               the same seven fields for one SceneView of those counts
+//                                               (n_leaf padded from n_inst; tests/kernel_recipes.py)
+//   plan_host scene_bytes n_inst n_real n_tris n_mats n_lights n_meshes
+//                                               lds_bytes(S, true, true), rt_work.scene_bytes
 //   plan_host geometry W H row0 row_step spp    frame_geometry's fields
 //   plan_host grid n_cu per_cu n_groups n_slots overlap other_running ranks_per_device
 //   plan_host history want_stats dbg sky prof heavy_q n_groups full_waves
@@ -55,6 +61,26 @@ int main(int argc, char** argv) {
     auto arg = [&](int i) { return i < argc ? atoll(argv[i]) : 0ll; };
     if (argc >= 2 && !strcmp(argv[1], "variants")) {
         variants();
+    } else if (argc == 19 && !strcmp(argv[1], "key")) {
+        // one SceneView of the given counts, as upload and view_of (rt_runtime.cpp) set them
+        static const rtm::TriAx some_tri_ax{};
+        SceneView S{};
+        S.n_inst = (int)arg(2); S.n_real = (int)arg(3); S.ftree = (int)arg(4);
+        S.tri_ax = arg(5) ? &some_tri_ax : nullptr; S.ident_all = arg(5) != 0;
+        S.use_bvh = (int)arg(6);
+        S.n_tris = (int)arg(7); S.n_mats = (int)arg(8); S.n_lights = (int)arg(9); S.n_meshes = (int)arg(10);
+        S.prune_abs = (float)atof(argv[11]);
+        S.n_leaf = 0;                                          // padded(): 1 << ceil(log2(n)), 0 for none
+        if (S.n_inst > 0) { S.n_leaf = 1; while (S.n_leaf < S.n_inst) S.n_leaf <<= 1; }
+        const TraceKey k = trace_variant_key(S, (int)arg(12), arg(13) != 0, arg(14) != 0, arg(15) != 0, (int)arg(16),
+                                             arg(17) != 0, arg(18) != 0);
+        printf("%d %d %d %zu %d %d %d\n", k.ns_bucket, (int)k.lds, k.mode, k.shm, (int)k.part_k, (int)k.sky, (int)k.sky_brute);
+    } else if (argc == 8 && !strcmp(argv[1], "scene_bytes")) {
+        // lds_bytes(S, true, true): the scene image of a fast kernel's block (rt_work.scene_bytes)
+        SceneView S{};
+        S.n_inst = (int)arg(2); S.n_real = (int)arg(3);
+        S.n_tris = (int)arg(4); S.n_mats = (int)arg(5); S.n_lights = (int)arg(6); S.n_meshes = (int)arg(7);
+        printf("scene_bytes %zu\n", lds_bytes(S, true, true));
     } else if (argc == 7 && !strcmp(argv[1], "geometry")) {
         const FrameGeometry g = frame_geometry((int)arg(2), (int)arg(3), (int)arg(4), (int)arg(5), (int)arg(6));
         printf("n_rows %d lanes_per_px %d px_per_wave %d gw %d gh %d l_shift %d gw_shift %d n_gx %d n_groups %d scramble %d "
@@ -67,7 +93,7 @@ int main(int argc, char** argv) {
     } else if (argc == 9 && !strcmp(argv[1], "history")) {
         printf("hist %d\n", history_mode(arg(2) != 0, arg(3) != 0, arg(4) != 0, arg(5) != 0, (int)arg(6), arg(7), arg(8)));
     } else {
-        fprintf(stderr, "usage: plan_host variants | geometry ... | grid ... | history ...\n");
+        fprintf(stderr, "usage: plan_host variants | key ... | scene_bytes ... | geometry ... | grid ... | history ...\n");
         return 2;
     }
     return 0;
