@@ -2,7 +2,7 @@
 //
 //   rtracer -c world8.json [-b] [-r] [-s] [-d DIM] [--frames N] [--spp K]
 //           [--width W --height H] [--out frame.ppm] [--debug X,Y] [--textures [ATLAS.png]]
-//           [--gpus N [--ranks R]] [--in-flight D]
+//           [--gpus N [--ranks R]] [--in-flight D] [--pick X,Y]
 //
 // -c config (worldN.json), -b benchmark (one timed frame, "Time: X ms" as main.cc:210-216),
 // -r unoptimize (brute force, no BVH), -d kernel dimension (accepted; the HIP path
@@ -18,6 +18,8 @@
 // flight (rt_scene_set_frame_slots), each into its own device buffer on its own stream, then
 // one wait; prints the time per frame and per slice.  --out then writes the last frame.
 // --overlap sets the frames' grid policy (rt_scene_set_overlap; default stream).
+// --pick X,Y (build extension, rt_query): the instance under pixel (X, Y) -- one line,
+// "pick X Y inst I tri T t <distance>" or "pick X Y miss" -- and nothing is rendered.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -35,7 +37,7 @@ static void usage() {
     std::fprintf(stderr,
                  "usage: rtracer -c CONFIG [-b] [-r] [-s] [-d DIM] [--frames N] [--spp K] [--width W --height H]\n"
                  "               [--out FILE.ppm] [--debug X,Y] [--textures [ATLAS.png]] [--gpus N [--ranks R]]\n"
-                 "               [--in-flight D [--readback] [--overlap stream|half|full]]\n");
+                 "               [--in-flight D [--readback] [--overlap stream|half|full]] [--pick X,Y]\n");
 }
 
 static bool write_ppm(const char* path, const uint32_t* px, int w, int h) {
@@ -58,7 +60,7 @@ int main(int argc, char** argv) {
     std::string config, out;
     bool bench = false, unopt = false, serial = false, textures = false, readback = false;
     std::string atlas, overlap = "stream";
-    int dim = 16, frames = 1, spp = 1, width = 0, height = 0, dbg_x = -1, dbg_y = -1, gpus = 1, ranks = 0, in_flight = 0;
+    int dim = 16, frames = 1, spp = 1, width = 0, height = 0, dbg_x = -1, dbg_y = -1, pick_x = -1, pick_y = -1, gpus = 1, ranks = 0, in_flight = 0;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto val = [&](const char* name) -> const char* {
@@ -89,6 +91,8 @@ int main(int argc, char** argv) {
         }
         else if (a == "--debug") {
             if (std::sscanf(val("--debug"), "%d,%d", &dbg_x, &dbg_y) != 2) { usage(); return 2; }
+        } else if (a == "--pick") {
+            if (std::sscanf(val("--pick"), "%d,%d", &pick_x, &pick_y) != 2 || pick_x < 0 || pick_y < 0) { usage(); return 2; }
         } else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); usage(); return 2; }
     }
     if (config.empty()) { usage(); return 2; }
@@ -116,6 +120,24 @@ int main(int argc, char** argv) {
     if (textures && rt_scene_load_atlas(handle, atlas.empty() ? nullptr : atlas.c_str()) != RT_OK) {
         std::fprintf(stderr, "cannot load the atlas: %s\n", rt_last_error());
         return 1;
+    }
+    if (pick_x >= 0) {                                     // one closest-hit query for the pixel's camera ray
+        const int32_t px[2] = {pick_x, pick_y};
+        float t = 0.0f;
+        int32_t inst = -1, tri = -1;
+        rt_query_opts q;
+        rt_query_opts_default(&q);
+        q.n = 1; q.pixel = px; q.host = 1; q.use_bvh = unopt ? 0 : 1;
+        q.t = &t; q.inst = &inst; q.tri = &tri;
+        if (rt_query(handle, &q, nullptr) != RT_OK) {
+            std::fprintf(stderr, "pick failed: %s\n", rt_last_error());
+            rt_scene_free(handle);
+            return 1;
+        }
+        if (inst >= 0) std::printf("pick %d %d inst %d tri %d t %.9g\n", pick_x, pick_y, inst, tri, (double)t);
+        else std::printf("pick %d %d miss\n", pick_x, pick_y);
+        rt_scene_free(handle);
+        return 0;
     }
     renv::gpu::Scene* scene = new renv::gpu::Scene(handle);
     renv::Environment& env = scene->get_environment();

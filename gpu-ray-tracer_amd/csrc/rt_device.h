@@ -161,6 +161,25 @@ struct TraceParams {
                               // and no phong term for it either (2)
 };
 
+// query_kernel's arguments (rt_query): n caller-supplied rays (origin / dir, normalised on the
+// device as rmath::Ray does) or the camera's sample-0 rays of n pixels (pixel), and the
+// per-ray outputs, each optional.  Device pointers.
+struct QueryParams {
+    rt::DCamera cam;          // pixel mode: camera_at
+    long long n;
+    const float* origin; const float* dir;      // [3n]
+    const float* tmax;                          // [n] or null (+inf)
+    float any_margin;                           // occlusion early exit at time <= tmax (1 - any_margin); < 0: off
+    float zcut_scene;                           // zero-axis cut: the scene's part of a ray's slack (+ 2^-14 |o|); < 0: off
+    const int* pixel;                           // [2n] (x, y), or null
+    float* t; int* inst; int* tri;              // miss: +inf, -1, -1
+    float* uv;                                  // [2n]
+    float* normal;                              // [3n]
+    unsigned char* hit;                         // [n]
+    float* rays_out;                            // [6n] origin, normalised direction
+    unsigned long long* stats;                  // counted kernels: rays, nodes, leaves, triangle tests
+};
+
 }  // namespace rtd
 
 #include "rt_plan.h"   // the LDS layout and MODE bits; the launch plan (trace_variant_key and the rest)
@@ -185,6 +204,12 @@ hipError_t launch_sky(bool brute, int blocks, TraceParams& P, SceneView& S, unsi
                       const rtm::Box* mesh_box, float slack_a, float slack_b, hipStream_t st, hipEvent_t e0);
 hipError_t launch_trace_kernel(const TraceVariant& v, int blocks, TraceParams& P, SceneView& S, hipStream_t st,
                                hipEvent_t e0, hipEvent_t e1);
+// The query kernel for a batch (query_plan's key looked up in the table of query kernels; null fn:
+// no kernel with this key, a programming error) and its launch.  S: view_of's scene with the
+// camera-ray shortcuts off (rt_query).
+struct QueryVariant : QueryKey { const void* fn; };
+QueryVariant choose_query_variant(long long n_rays, const SceneView& S, bool any_hit, bool counted, int n_cu, int form);
+hipError_t launch_query_kernel(const QueryVariant& v, QueryParams& Q, SceneView& S, hipStream_t st);
 // The single-workgroup BVH build (A.n <= BVH_WG_LEAVES) with `lds` bytes of dynamic LDS.
 hipError_t launch_bvh_build(rtb::BvhArgs& A, bool lds_tree, size_t lds, hipStream_t st, hipEvent_t e0, hipEvent_t e1);
 size_t scene_image_bytes(const SceneView& S);   // the scene image a fast kernel's block stages in LDS

@@ -139,7 +139,10 @@ struct rt_scene {
     float4* d_atlas = nullptr;                   // atlas texels (float4, byte / 255)
     bool atlas_dirty = false;
     void* d_out[4] = {nullptr, nullptr, nullptr, nullptr};   // staging for host_outputs
-    std::vector<hipEvent_t> tev;      // timing=1 events, 4 per frame: bvh start/stop, trace start/stop (pool)
+    // rt_query with host pointers: one pinned host image of the batch (inputs, then outputs) and
+    // its device copy; they grow and are kept, so a warm call allocates nothing
+    unsigned char* q_host = nullptr; unsigned char* q_dev = nullptr; size_t q_cap = 0;
+    std::vector<hipEvent_t> tev;     // timing=1 events, 4 per frame: bvh start/stop, trace start/stop (pool)
     size_t tev_used = 0;
     size_t d_out_px = 0;
     int n_leaf = 0;

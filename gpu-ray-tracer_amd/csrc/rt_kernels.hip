@@ -445,13 +445,16 @@ __device__ __forceinline__ V3 hit_normal(const SceneView& S, const BvhRefs& bv, 
 // binds (every nonzero axis bounds t by ~1e3; lo <= 0 is below any acceptable
 // time, so entry bounds stay valid).  closest_hit's `im` keeps the nonzero axes only.
 // Fast (ordered-LBVH) kernels only.
-__device__ __forceinline__ void zero_axis_cut(const SceneView& S, const Ray& r, RayInv& ri) {
-    if (!(S.prune_abs >= 0.0f)) return;
+// `slack`: the scene's prune_abs (camera rays: |cam.pos| is folded into it), or a caller ray's own
+// (query_kernel: the same bound with the ray's origin in the camera's place; < 0 for a lane: off).
+__device__ __forceinline__ void zero_axis_cut(float slack, const Ray& r, RayInv& ri) {
+    if (!(slack >= 0.0f)) return;
     constexpr float K = 0x1p32f;
-    if (r.d.x == 0.0f) { ri.ix = K; ri.bx = K * S.prune_abs; }
-    if (r.d.y == 0.0f) { ri.iy = K; ri.by = K * S.prune_abs; }
-    if (r.d.z == 0.0f) { ri.iz = K; ri.bz = K * S.prune_abs; }
+    if (r.d.x == 0.0f) { ri.ix = K; ri.bx = K * slack; }
+    if (r.d.y == 0.0f) { ri.iy = K; ri.by = K * slack; }
+    if (r.d.z == 0.0f) { ri.iz = K; ri.bz = K * slack; }
 }
+__device__ __forceinline__ void zero_axis_cut(const SceneView& S, const Ray& r, RayInv& ri) { zero_axis_cut(S.prune_abs, r, ri); }
 
 // First step of the fast traversal for a ray (closest_hit, FT path, node 0 with an empty
 // closest hit): whether it hits either child of the ordered LBVH's root.  A lane for which
@@ -502,7 +505,7 @@ __device__ __forceinline__ bool ft_root_hit(const SceneView& S, const BvhRefs& b
 template <bool NOLEAF, bool STATS, bool FT = false, bool AXIS = false, bool PROF = false, bool BRUTE = false>
 __device__ __forceinline__ bool closest_hit(const SceneView& S, const BvhRefs& bv, bool active_in, const Ray& r,
                                             Best& b, WaveCounters& wc, float occl_t = -1.0f,
-                                            float lim = INFINITY) {
+                                            float lim = INFINITY, float zcut = -1.0f) {
     const bool prune = !STATS && S.prune_abs >= 0.0f;
     float im = 0.0f;                                           // max_a |1/d_a| (set below)
     auto slack = [&](float t) { return (S.prune_abs + 0x1p-14f * fabsf(t)) * im + 0x1p-14f * fabsf(t); };
@@ -549,6 +552,7 @@ __device__ __forceinline__ bool closest_hit(const SceneView& S, const BvhRefs& b
     RayInv ri = ray_inv(r);
     im = ri.exact ? INFINITY : fmaxf(fabsf(ri.ix), fmaxf(fabsf(ri.iy), fabsf(ri.iz)));
     if (FT) zero_axis_cut(S, r, ri);
+    if (FT) zero_axis_cut(zcut, r, ri);                       // (caller rays, per lane: query_kernel)
     if (FT) {
         // Ordered LBVH (fast kernel, S.ftree): same leaves and leaf order as the heap, so
         // each lane meets exactly the leaves its ray hits, in the heap's DFS order (a
@@ -1967,6 +1971,123 @@ __global__ __launch_bounds__(SKY_THREADS) void sky_kernel(TraceParams P, SceneVi
 }
 
 // ---------------------------------------------------------------------------
+// Ray queries (rt_query): renv::gpu::cast_ray (scene.cu:42-73) for caller-supplied rays.
+// One ray per lane, one wave per 64 consecutive rays (a chunk), the tail lanes of the last
+// chunk inactive; waves stride statically over the chunks (small form: one chunk per wave).
+// TREE: QT_ORDERED (the ordered LBVH, closest_hit's FT path), QT_HEAP (the reference heap
+// walk) or QT_BRUTE (the instance loop).  LDS: the tree and inst4 staged once per block
+// (persistent form).  ANY: occlusion query with the early exit.  STATS: the counted reference
+// walk (heap, or the instance loop when there is no tree): rt_stats' four counters.
+// The scene comes with the camera-ray shortcuts off (prune_abs < 0: no distance pruning, no
+// triangle skip; never the axis-plane triangle path): their bounds fold the camera position
+// in, and a caller's origin is anywhere.  What stays on is exact for every
+// ray: the filtered slab and plane tests with their exact fallbacks, the per-query direction
+// chain of identity-pose scenes (dir_pre: a function of the direction only), and the zero-axis
+// cut with a slack formed per ray from its own origin (below).
+// A ray with a non-finite component, or whose direction normalises to zero (rmath::Ray:
+// shorter than 1e-5, or too long for its length to be finite), is inactive from the start: it
+// reports a miss and takes no part in the wave's ballots.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ bool finite3(V3 v) { return isfinite(v.x) && isfinite(v.y) && isfinite(v.z); }
+
+// The batch's QueryParams read in place from the kernel-argument segment, through a pointer made
+// fresh at each use (kparams' reason: by value, its pointers and the camera were loaded once and
+// held in SGPRs across the traversal, and the scalar file overflowed into VGPR lanes).
+typedef __attribute__((address_space(4))) const QueryParams KQP;
+__device__ __forceinline__ KQP& qparams() {
+    KQP* p = (KQP*)__builtin_amdgcn_kernarg_segment_ptr();     // the first kernel argument
+    asm volatile("" : "+s"(p));
+    return *p;
+}
+
+template <int TREE, bool LDS, bool ANY, bool STATS>
+__global__ __launch_bounds__(TRACE_BLOCK_P) void query_kernel(QueryParams Q_arg, SceneView S) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    (void)Q_arg;                                               // read in place: qparams()
+    constexpr bool FT = TREE == QT_ORDERED, BRUTE = TREE == QT_BRUTE;
+    static_assert(!(STATS && (FT || ANY)), "a counted query is the whole reference walk");
+    const BvhRefs bv = stage_bvh<LDS, FT, false, BRUTE>(S, smem);
+    const int lane = threadIdx.x & 63;
+    const int block_waves = (int)(blockDim.x >> 6);
+    const long long chunks = (qparams().n + 63) >> 6;
+    const long long stride = (long long)gridDim.x * block_waves;
+    WaveCounters wc{0, 0, 0, 0};
+    for (long long c = (long long)blockIdx.x * block_waves + (long long)(threadIdx.x >> 6); c < chunks; c += stride) {
+        const long long i = c * 64 + lane;
+        const bool in = i < qparams().n;
+        Ray r{v3(0, 0, 0), v3(0, 0, 1)};
+        bool ok = in;
+        if (in) {
+            KQP& Q = qparams();
+            if (Q.pixel) {                                     // the camera's sample-0 ray (trace_kernel's primary)
+                r = camera_at(kld(Q.cam), (float)Q.pixel[2 * i], (float)Q.pixel[2 * i + 1]);
+            } else {
+                const V3 o = v3(Q.origin[3 * i], Q.origin[3 * i + 1], Q.origin[3 * i + 2]);
+                const V3 d = v3(Q.dir[3 * i], Q.dir[3 * i + 1], Q.dir[3 * i + 2]);
+                r = make_ray(o, d);                            // Ray ctor (geometry.h:216)
+                ok = finite3(d);
+            }
+            ok = ok && finite3(r.o) && finite3(r.d) && (r.d.x != 0.0f || r.d.y != 0.0f || r.d.z != 0.0f);
+            if (Q.rays_out) {
+                float* ro = Q.rays_out + 6 * i;
+                ro[0] = r.o.x; ro[1] = r.o.y; ro[2] = r.o.z; ro[3] = r.d.x; ro[4] = r.d.y; ro[5] = r.d.z;
+            }
+            if (!ok) r = Ray{v3(0, 0, 0), v3(0, 0, 1)};        // nothing non-finite enters the wave's arithmetic
+        }
+        const float tm = (in && qparams().tmax) ? qparams().tmax[i] : INFINITY;
+        // Occlusion early exit: a lane stops at an accepted hit with time <= tm (1 - margin).  Each
+        // later accept (at most one per instance: cast_local sets the time once) is below the
+        // previous time in its own local units, so it raises the world time by the rescaling's
+        // rounding at most (a factor < 1 + 2^-20); `margin` >= n_inst 2^-19 covers the chain, so the
+        // closest hit is < tm as well and the boolean is the closest-hit query's.
+        float occl = -1.0f;
+        if (ANY && qparams().any_margin >= 0.0f && tm > 0.0f) occl = tm * (1.0f - qparams().any_margin);
+        Best b;
+        b.time = INFINITY; b.inst = -1; b.tri = -1; b.u = 0.0f; b.v = 0.0f;
+        // Zero-axis cut with the ray's own slack (zero_axis_cut; ordered tree, pure translations:
+        // zcut_scene >= 0).  Its bound is the camera rays' with this origin in the camera's place:
+        // on an axis where d_a = 0 the ray keeps its coordinate o_a exactly, world and local, so an
+        // accepted point is within the triangle tolerance and the origin's rounding of the leaf
+        // box there; 4e-4 x the largest vertex coordinate + 2^-14 x (scene radius + |o|) is 20x
+        // that.  Without it one axis-parallel ray (a frame's centre column, a line of sight along
+        // an axis) visits every leaf of its row: the 1024-ray batch holding the centre column's
+        // end measured 333 us without the cut, 92 us with it.
+        // Origins beyond 2^64 (where K x slack leaves the float range) go without.
+        float zc = -1.0f;
+        if (FT && qparams().zcut_scene >= 0.0f) {
+            const float oa = fmaxf(fabsf(r.o.x), fmaxf(fabsf(r.o.y), fabsf(r.o.z)));
+            if (oa <= 0x1p64f) zc = qparams().zcut_scene + 0x1p-14f * oa;
+        }
+        closest_hit<false, STATS, FT, false, false, BRUTE && !STATS>(S, bv, ok, r, b, wc, occl, INFINITY, zc);
+        const bool hit = ok && b.time < tm;                    // (nothing accepted: b.time = +inf)
+        if (in) {
+            KQP& Q = qparams();
+            if (Q.hit) Q.hit[i] = hit ? 1 : 0;
+            if (!ANY) {                                        // (an early exit leaves b short of the closest hit)
+                if (Q.t) Q.t[i] = hit ? b.time : INFINITY;
+                if (Q.inst) Q.inst[i] = hit ? b.inst : -1;
+                if (Q.tri) Q.tri[i] = hit ? b.tri : -1;
+                if (Q.uv) { Q.uv[2 * i] = hit ? b.u : 0.0f; Q.uv[2 * i + 1] = hit ? b.v : 0.0f; }
+                if (Q.normal) {
+                    V3 nrm = v3(0, 0, 0);
+                    int mat = 0;
+                    if (hit) nrm = hit_normal(S, bv, b, mat);
+                    (void)mat;
+                    Q.normal[3 * i] = nrm.x; Q.normal[3 * i + 1] = nrm.y; Q.normal[3 * i + 2] = nrm.z;
+                }
+            }
+        }
+    }
+    if (STATS && qparams().stats && lane == 0) {
+        KQP& Q = qparams();
+        if (wc.rays) atomicAdd(&Q.stats[0], wc.rays);
+        if (wc.nodes) atomicAdd(&Q.stats[1], wc.nodes);
+        if (wc.leaves) atomicAdd(&Q.stats[2], wc.leaves);
+        if (wc.tris) atomicAdd(&Q.stats[3], wc.tris);
+    }
+}
+
+// ---------------------------------------------------------------------------
 // BVH build: ropt::gpu::BVH::BVH (bvh.cu:74-91) + create_boxes (raytracer.cu:54-74)
 // in one workgroup.  Output: heap-ordered nodes[1 .. 2n-1].
 // ---------------------------------------------------------------------------
@@ -2311,6 +2432,35 @@ TraceVariant choose_trace_variant(const SceneView& S, int spp, bool tex, bool wa
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&v.per_cu, v.fn, TRACE_BLOCK_P, v.shm) != hipSuccess || v.per_cu < 1)
         v.per_cu = 1;
     return v;
+}
+
+// The query kernels (rt_query): every instantiation of query_kernel, named here once.  query_plan
+// (rt_plan.h) decides which of them a batch gets.
+struct QueryEntry { int tree; bool lds, any_hit, counted; const void* fn; };
+#define QK(TREE, LDS, ANY, STATS) QueryEntry{TREE, LDS, ANY, STATS, (const void*)query_kernel<TREE, LDS, ANY, STATS>}
+#define QK4(TREE) QK(TREE, false, false, false), QK(TREE, true, false, false), QK(TREE, false, true, false), QK(TREE, true, true, false)
+static const QueryEntry query_kernels[] = {
+    QK4(QT_ORDERED), QK4(QT_HEAP), QK4(QT_BRUTE),
+    // counted: the reference heap walk, or the reference's instance loop
+    QK(QT_HEAP, false, false, true), QK(QT_HEAP, true, false, true),
+    QK(QT_BRUTE, false, false, true), QK(QT_BRUTE, true, false, true),
+};
+#undef QK4
+#undef QK
+static_assert(sizeof query_kernels / sizeof *query_kernels == 16, "the query kernels of the build");
+
+QueryVariant choose_query_variant(long long n_rays, const SceneView& S, bool any_hit, bool counted, int n_cu, int form) {
+    QueryVariant v{};
+    static_cast<QueryKey&>(v) = query_plan(n_rays, S, any_hit, counted, n_cu, form);
+    for (const QueryEntry& e : query_kernels)
+        if (e.tree == v.tree && e.lds == v.lds && e.any_hit == v.any_hit && e.counted == v.counted) v.fn = e.fn;
+    if (v.fn && v.shm > 64 * 1024) (void)hipFuncSetAttribute(v.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v.shm);
+    return v;
+}
+
+hipError_t launch_query_kernel(const QueryVariant& v, QueryParams& Q, SceneView& S, hipStream_t st) {
+    void* args[] = {&Q, &S};
+    return hipExtLaunchKernel(v.fn, dim3(v.blocks), dim3(v.block), args, v.shm, st, nullptr, nullptr, 0);
 }
 
 hipError_t launch_sky(bool brute, int blocks, TraceParams& P, SceneView& S, unsigned char* gsky, int* live,

@@ -6,8 +6,10 @@
 //    (trace_variant_key; the table of kernels it indexes is choose_trace_variant's, in
 //    rt_kernels.hip), the frame's lane mapping and group geometry (frame_geometry), its shading
 //    shortcuts (shade_shortcuts), its grid (grid_policy) and its scheduling history mode
-//    (history_mode).  launch_trace (rt_runtime.cpp) fills TraceParams from them;
-//    tests/test_plan_host.py checks them on a machine without a GPU.
+//    (history_mode), and which query kernel a batch of caller-supplied rays gets (query_plan,
+//    rt_query).  launch_trace and rt_query (rt_runtime.cpp) fill the kernels' parameters from
+//    them; tests/test_plan_host.py and tests/test_query_host.py check them on a machine without
+//    a GPU.
 #pragma once
 
 #include <algorithm>
@@ -296,6 +298,62 @@ inline int history_mode(bool want_stats, bool dbg, bool sky, bool prof, int heav
     if (want_stats || dbg) return 0;
     if (sky && heavy_q > 0) return 2;
     return (prof || n_groups <= RT_HIST_GROUPS_PER_WAVE * full_waves) ? 1 : 0;
+}
+
+// ---- Ray queries (rt_query): which query_kernel a batch of caller-supplied rays gets
+// The fast traversal's stack holds <= FT_MAX_DEPTH entries (closest_hit, FT path); a deeper
+// ordered tree, or one with fewer than two real leaves, is unusable (SceneView::ftree = 0).
+constexpr int FT_MAX_DEPTH = 31;
+inline bool ordered_tree_usable(int n_real, int depth) { return n_real >= 2 && depth <= FT_MAX_DEPTH; }
+
+enum : int { QT_ORDERED = 0, QT_HEAP = 1, QT_BRUTE = 2 };   // tree form of a query kernel
+constexpr int QUERY_BLOCK_SMALL = 256;                     // small form: 4 waves, the tree read from global memory / L2
+// Batches of at least this many rays take the persistent form.  Measured (tools/query_bench.py,
+// profiles/query/query_bench.log): on world8_stress the small form was as fast or
+// faster at every batch size up to a 1080p frame (2.07 M rays: 218 against 259 us in pixel order,
+// 2.80 against 3.60 ms permuted): 20 waves per CU against the persistent block's 16, and blocks
+// dealt out as CUs free up against a static stride; the 45-KB tree is L2-resident either way.
+// No crossover was found, so the persistent form is kept for frame-sized batches only.
+#ifndef RT_QUERY_PERSIST_RAYS
+#define RT_QUERY_PERSIST_RAYS (1 << 20)
+#endif
+struct QueryKey {
+    int tree;                 // QT_*
+    bool lds;                 // the tree (brute force: inst4) staged in LDS; persistent form only
+    bool any_hit;             // occlusion early exit compiled in
+    bool counted;             // the reference heap walk with rt_stats' counters (STATS form)
+    bool persistent;          // 1024-thread blocks, at most one per CU, striding over 64-ray chunks
+    int block, blocks;        // the launch: dim3(blocks), dim3(block)
+    size_t shm;               // dynamic LDS
+};
+// One ray per lane, one wave per 64 consecutive rays (a chunk).  Small batches (picking: one
+// ray) run 256-thread blocks over ceil(n / 256) chunks' worth of rays and stage nothing;
+// large ones run one 1024-thread block per CU that stages the scene image once (stage_bvh)
+// when it fits LDS_LIMIT and reads it from global memory otherwise.  A counted query runs the
+// whole reference walk (the heap, or the instance loop without a tree) so that its counters
+// are the reference's: no ordered tree and no early exit.  An unusable ordered tree falls back
+// to the heap walk.  form: < 0 by batch size, 0 small, 1 persistent (measurements).
+inline QueryKey query_plan(long long n_rays, const SceneView& S, bool any_hit, bool counted, int n_cu, int form = -1) {
+    QueryKey k{};
+    const bool brute = !S.use_bvh || S.n_leaf == 0;
+    k.tree = brute ? QT_BRUTE : (S.ftree && !counted) ? QT_ORDERED : QT_HEAP;
+    k.counted = counted;
+    k.any_hit = any_hit && !counted;
+    k.persistent = form < 0 ? n_rays >= (long long)RT_QUERY_PERSIST_RAYS : form != 0;
+    const long long chunks = (n_rays + 63) / 64;
+    if (k.persistent) {
+        const size_t image = lds_bytes(S, k.tree == QT_ORDERED, false, k.tree == QT_BRUTE);
+        k.lds = image <= (size_t)LDS_LIMIT;
+        k.shm = k.lds ? image : 0;
+        k.block = TRACE_BLOCK_P;
+        constexpr int BLOCK_WAVES = TRACE_BLOCK_P / 64;
+        k.blocks = (int)std::max(1ll, std::min((long long)std::max(n_cu, 1), (chunks + BLOCK_WAVES - 1) / BLOCK_WAVES));
+    } else {
+        constexpr int BLOCK_WAVES = QUERY_BLOCK_SMALL / 64;
+        k.block = QUERY_BLOCK_SMALL;
+        k.blocks = (int)std::max(1ll, std::min((chunks + BLOCK_WAVES - 1) / BLOCK_WAVES, (long long)INT32_MAX));
+    }
+    return k;
 }
 
 }  // namespace rtd

@@ -120,8 +120,7 @@ std::vector<TriAx> tri_axis_records(const rt::Scene& h) {
 
 // Leaf count and depth (internal nodes on the longest root-leaf path) of the ordered
 // LBVH bvh_build_kernel will build: the same box, Morton and sort arithmetic on the
-// host (RT_HD functions).  The fast traversal's stack holds <= FT_MAX_DEPTH entries.
-constexpr int FT_MAX_DEPTH = 31;
+// host (RT_HD functions).  The fast traversal's stack holds <= FT_MAX_DEPTH entries (rt_plan.h).
 // Mesh boxes: Trimesh::compute_bounding_box (trimesh.cu:21-32, sequential fit order) and
 // the mesh pose.  They depend only on the immutable mesh data, so they are computed once
 // here; the per-frame build (bvh_build_kernel) redoes everything per instance.
@@ -514,31 +513,40 @@ int build_bvh(rt_scene* s, hipStream_t st, hipEvent_t e0 = nullptr, hipEvent_t e
     return RT_OK;
 }
 
+// The pruning slack (closest_hit) for rays starting within origin_amax (largest |coordinate|) of
+// the world's origin, or -1 when the boxes do not provably contain their triangles: that holds
+// only for pure translations with zero mesh offsets (the BVH boxes ignore the mesh pose,
+// raytracer.cu:54-89).  Slack: 4e-4 x mesh size + 2^-14 x scene radius.
+float prune_slack(const rt_scene* s, float origin_amax) {
+    bool prune_ok = true;
+    for (const auto& i : s->h.d_insts) prune_ok = prune_ok && i.pose.identity;
+    for (const auto& m : s->h.d_meshes) prune_ok = prune_ok && m.pose.identity;
+    float vmax = 0.0f, pmax = 0.0f;
+    for (const auto& m : s->h.d_meshes) prune_ok = prune_ok && m.pose.p.x == 0 && m.pose.p.y == 0 && m.pose.p.z == 0;
+    auto amax = [](rtm::V3 a) { return std::max(std::fabs(a.x), std::max(std::fabs(a.y), std::fabs(a.z))); };
+    for (const auto& t : s->h.d_tris) vmax = std::max(vmax, std::max(amax(t.a), std::max(amax(t.b), amax(t.c))));
+    for (const auto& i : s->h.d_insts) pmax = std::max(pmax, amax(i.pose.p));
+    const float radius = pmax + vmax + origin_amax + 1.0f;
+    prune_ok = prune_ok && std::isfinite(radius);
+    return prune_ok ? 4e-4f * vmax + 0x1p-14f * radius : -1.0f;
+}
+
 SceneView view_of(const rt_scene* s, bool use_bvh) {
     const FrameSlot& f = s->cur();
     SceneView v;
     v.tris = s->d_tris; v.meshes = s->d_meshes; v.insts = f.d_insts; v.mats = s->d_mats; v.lights = s->d_lights;
     v.node_pair = f.d_node_pair; v.leaf_inst = f.d_leaf;
     v.fnode = f.d_fnode; v.n_real = s->n_real;
-    v.ftree = (s->n_real >= 2 && s->fdepth <= FT_MAX_DEPTH) ? 1 : 0; v.inst4 = f.d_inst4;
+    v.ftree = ordered_tree_usable(s->n_real, s->fdepth) ? 1 : 0; v.inst4 = f.d_inst4;
     v.n_leaf = s->n_leaf; v.n_inst = (int)s->h.d_insts.size();
     v.n_lights = (int)s->h.d_lights.size(); v.use_bvh = use_bvh ? 1 : 0;
     v.n_mats = (int)s->h.d_mats.size(); v.n_tris = (int)s->h.d_tris.size(); v.n_meshes = (int)s->h.d_meshes.size();
     v.ident_all = 1;
     for (const auto& i : s->h.d_insts) v.ident_all &= i.pose.identity ? 1 : 0;
     for (const auto& m : s->h.d_meshes) v.ident_all &= m.pose.identity ? 1 : 0;
-    // Distance pruning (closest_hit): boxes provably contain their triangles only for
-    // pure translations with zero mesh offsets (the BVH boxes ignore the mesh pose,
-    // raytracer.cu:54-89).  Slack: 1e-4 x mesh size + 2^-14 x scene radius.
-    bool prune_ok = v.ident_all != 0;
-    float vmax = 0.0f, pmax = 0.0f;
-    for (const auto& m : s->h.d_meshes) prune_ok = prune_ok && m.pose.p.x == 0 && m.pose.p.y == 0 && m.pose.p.z == 0;
-    auto amax = [](rtm::V3 a) { return std::max(std::fabs(a.x), std::max(std::fabs(a.y), std::fabs(a.z))); };
-    for (const auto& t : s->h.d_tris) vmax = std::max(vmax, std::max(amax(t.a), std::max(amax(t.b), amax(t.c))));
-    for (const auto& i : s->h.d_insts) pmax = std::max(pmax, amax(i.pose.p));
-    const float radius = pmax + vmax + amax(s->h.d_cam.pos) + 1.0f;
-    prune_ok = prune_ok && std::isfinite(radius);
-    v.prune_abs = prune_ok ? 4e-4f * vmax + 0x1p-14f * radius : -1.0f;
+    // Distance pruning (closest_hit): the camera's rays
+    const rtm::V3 cp = s->h.d_cam.pos;
+    v.prune_abs = prune_slack(s, std::max(std::fabs(cp.x), std::max(std::fabs(cp.y), std::fabs(cp.z))));
     v.tri_ax = (v.ident_all && !s->h.d_tris.empty()) ? s->d_tri_ax : nullptr;
     return v;
 }
@@ -712,6 +720,7 @@ rt_scene::~rt_scene() {
     dfree(d_tris); dfree(d_meshes); dfree(d_mats); dfree(d_lights); dfree(d_tri_ax);
     dfree(d_mesh_box); dfree(d_spp); dfree(d_stats); dfree(d_canvas); dfree(d_dbg);
     for (auto& p : d_out) dfree(p);
+    dfree(q_dev); hfree(q_host);
     for (auto& e : ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : tev) (void)hipEventDestroy(e);
     for (auto& f : slots) f.release();
@@ -1285,6 +1294,114 @@ int rt_frame_work(rt_scene* s, const rt_render_opts* o, rt_work* w) {
         w->hist_wave_queries[i] = v[PROF_HIST_WQ + i];
         w->hist_pair_steps[i] = v[PROF_HIST_PAIR + i];
         w->hist_leaf_visits[i] = v[PROF_HIST_LEAF + i];
+    }
+    return RT_OK;
+}
+
+void rt_query_opts_default(rt_query_opts* o) {
+    if (!o) return;
+    memset(o, 0, sizeof *o);
+    o->use_bvh = 1; o->rebuild_bvh = 1;
+}
+
+// Ray queries (rt_amd.h): a side entry like rt_debug_cast, but its kernel is query_kernel, not a
+// trace kernel: the scene's last trace launch and the slots' scheduling history stay as they were.
+int rt_query(rt_scene* s, const rt_query_opts* o, rt_stats* stats) {
+    CHECK_FINISHED(s);
+    if (!o) return fail(RT_ERR_ARG, "null options");
+    if (o->n < 0) return fail(RT_ERR_ARG, "rt_query: n >= 0 required");
+    if (o->n == 0) return RT_OK;
+    const bool by_pixel = o->pixel != nullptr;
+    if (by_pixel ? (o->origin || o->dir) : !(o->origin && o->dir))
+        return fail(RT_ERR_ARG, "rt_query: give either pixel, or both origin and dir");
+    const bool any = o->any_hit != 0;
+    if (any ? !o->hit : !(o->t || o->inst || o->tri || o->uv || o->normal || o->hit || o->rays_out))
+        return fail(RT_ERR_ARG, any ? "rt_query: an occlusion query writes `hit`" : "rt_query: no output requested");
+    const size_t n = (size_t)o->n;
+    if (o->host && by_pixel)
+        for (size_t i = 0; i < n; i++) {
+            const int x = o->pixel[2 * i], y = o->pixel[2 * i + 1];
+            if (x < 0 || y < 0 || x >= s->h.cam.W || y >= s->h.cam.H)
+                return fail(RT_ERR_ARG, "rt_query: pixel " + std::to_string(i) + " is outside the canvas");
+        }
+    int r;
+    if ((r = begin_side_entry(s, 1, false)) != RT_OK) return r;   // upload, frames in flight, current poses
+    hipStream_t st = sstream(s);
+    const bool counted = stats != nullptr;
+    if (counted) { HIPCHK(hipMemsetAsync(s->d_stats, 0, STATS_N * sizeof(unsigned long long), st)); HIPCHK(hipEventRecord(s->ev[0], st)); }
+    if (o->use_bvh && (o->rebuild_bvh || !s->cur().bvh_valid) && (r = build_bvh(s, st)) != RT_OK) return r;
+    if (counted) HIPCHK(hipEventRecord(s->ev[1], st));
+
+    QueryParams Q{};
+    Q.cam = s->h.d_cam; Q.n = o->n;
+    Q.origin = o->origin; Q.dir = o->dir; Q.tmax = o->tmax; Q.pixel = o->pixel;
+    Q.t = any ? nullptr : o->t; Q.inst = any ? nullptr : o->inst; Q.tri = any ? nullptr : o->tri;
+    Q.uv = any ? nullptr : o->uv; Q.normal = any ? nullptr : o->normal;
+    Q.hit = o->hit; Q.rays_out = o->rays_out;
+    Q.stats = counted ? s->d_stats : nullptr;
+    // host pointers: the batch as one pinned image (inputs, then outputs) and its device copy
+    struct Part { const void* src; void* dst; size_t bytes, off; };
+    Part in[4] = {{o->origin, nullptr, 12 * n, 0}, {o->dir, nullptr, 12 * n, 0}, {o->tmax, nullptr, 4 * n, 0}, {o->pixel, nullptr, 8 * n, 0}};
+    Part out[7] = {{nullptr, Q.t, 4 * n, 0}, {nullptr, Q.inst, 4 * n, 0}, {nullptr, Q.tri, 4 * n, 0}, {nullptr, Q.uv, 8 * n, 0},
+                   {nullptr, Q.normal, 12 * n, 0}, {nullptr, Q.hit, n, 0}, {nullptr, Q.rays_out, 24 * n, 0}};
+    size_t in_bytes = 0, total = 0;
+    if (o->host) {
+        for (Part& p : in) if (p.src) { p.off = total; total += a16(p.bytes); }
+        in_bytes = total;
+        for (Part& p : out) if (p.dst) { p.off = total; total += a16(p.bytes); }
+        if (total > s->q_cap) {
+            const size_t cap = std::max(total, 2 * s->q_cap);
+            dfree(s->q_dev); hfree(s->q_host); s->q_cap = 0;
+            HIPCHK(hipMalloc((void**)&s->q_dev, cap));
+            HIPCHK(hipHostMalloc((void**)&s->q_host, cap, hipHostMallocDefault));
+            s->q_cap = cap;
+        }
+        for (const Part& p : in) if (p.src) memcpy(s->q_host + p.off, p.src, p.bytes);
+        HIPCHK(hipMemcpyAsync(s->q_dev, s->q_host, in_bytes, hipMemcpyHostToDevice, st));
+        auto dev = [&](const Part& p) { return (void*)(s->q_dev + p.off); };
+        if (o->origin) { Q.origin = (const float*)dev(in[0]); Q.dir = (const float*)dev(in[1]); }
+        if (o->tmax) Q.tmax = (const float*)dev(in[2]);
+        if (o->pixel) Q.pixel = (const int*)dev(in[3]);
+        if (Q.t) Q.t = (float*)dev(out[0]);
+        if (Q.inst) Q.inst = (int*)dev(out[1]);
+        if (Q.tri) Q.tri = (int*)dev(out[2]);
+        if (Q.uv) Q.uv = (float*)dev(out[3]);
+        if (Q.normal) Q.normal = (float*)dev(out[4]);
+        if (Q.hit) Q.hit = (unsigned char*)dev(out[5]);
+        if (Q.rays_out) Q.rays_out = (float*)dev(out[6]);
+    }
+    // The camera-ray shortcuts off (query_kernel): view_of's pruning slack folds |cam.pos| in and
+    // the axis-plane path's error bound is checked for rays from there; a caller's origin is anywhere.
+    SceneView S = view_of(s, o->use_bvh != 0);
+    S.prune_abs = -1.0f; S.tri_ax = nullptr;
+    // The zero-axis cut alone stays, with the origin's term added per ray on the device
+    Q.zcut_scene = prune_slack(s, 0.0f);
+    // occlusion early exit (query_kernel): one rescaling per instance at most, each < 1 + 2^-20
+    const float margin = (float)S.n_inst * 0x1p-19f;
+    Q.any_margin = margin <= 0.125f ? margin : -1.0f;
+    int form = -1;                                             // RT_QUERY_FORM (measurements): small / persistent
+    if (const char* e = getenv("RT_QUERY_FORM")) form = !strcmp(e, "small") ? 0 : !strcmp(e, "persistent") ? 1 : -1;
+    const QueryVariant V = choose_query_variant(o->n, S, any, counted, s->n_cu, form);
+    if (!V.fn)
+        return fail(RT_ERR_STATE, "no query kernel <" + std::to_string(V.tree) + ", " + std::to_string((int)V.lds) + ", " +
+                                      std::to_string((int)V.any_hit) + ", " + std::to_string((int)V.counted) + ">");
+    HIPCHK(launch_query_kernel(V, Q, S, st));
+    HIPCHK(hipGetLastError());
+    if (counted) HIPCHK(hipEventRecord(s->ev[2], st));
+    if (o->host && total > in_bytes)
+        HIPCHK(hipMemcpyAsync(s->q_host + in_bytes, s->q_dev + in_bytes, total - in_bytes, hipMemcpyDeviceToHost, st));
+    if ((r = end_frame(s, st)) != RT_OK) return r;
+    HIPCHK(hipStreamSynchronize(st));
+    if (o->host)
+        for (const Part& p : out) if (p.dst) memcpy(p.dst, s->q_host + p.off, p.bytes);   // (dst: the caller's arrays)
+    if (counted) {
+        unsigned long long v[4];
+        HIPCHK(hipMemcpy(v, s->d_stats, sizeof v, hipMemcpyDeviceToHost));
+        stats->rays = v[0]; stats->nodes = v[1]; stats->leaves = v[2]; stats->tri_tests = v[3];
+        float a = 0, b = 0;
+        HIPCHK(hipEventElapsedTime(&a, s->ev[0], s->ev[1]));
+        HIPCHK(hipEventElapsedTime(&b, s->ev[1], s->ev[2]));
+        stats->bvh_ms = a; stats->trace_ms = b;
     }
     return RT_OK;
 }

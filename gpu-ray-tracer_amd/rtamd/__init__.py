@@ -10,6 +10,8 @@ Mirrors the reference's render-path API (wtzhang23/gpu-ray-tracer):
   Scene.update_scene(kd, opt)    ~ rtracer::gpu::update_scene (raytracer.h:18-22)
   Scene.debug_cast(x, y)         ~ rtracer::gpu::debug_cast (raytracer.h:21)
   Scene.render(...)              the spp / row-slice / device-output extension
+  Scene.query(...) / pick(x, y)  closest hit or occlusion of caller-supplied rays (rt_query; the
+                                 reference's cast_ray, scene.cu:42-73, which it never exposes)
 """
 import ctypes
 import os
@@ -37,7 +39,7 @@ SYMBOLS = [
     "rt_builder_add_triangle_tex", "rt_builder_build_cube_tex", "rt_scene_set_atlas", "rt_scene_load_atlas",
     "rt_scene_atlas_info", "rt_scene_set_frame_slots", "rt_scene_set_overlap", "rt_frame_work",
     "rt_scene_set_devices", "rt_profile_marker", "rt_host_alloc", "rt_host_free", "rt_copy_to_host_async",
-    "rt_copy_engines_warm", "rt_scene_last_trace",
+    "rt_copy_engines_warm", "rt_scene_last_trace", "rt_query_opts_default", "rt_query",
 ]
 
 
@@ -54,6 +56,19 @@ class RenderOpts(ctypes.Structure):
                 ("radiance", ctypes.c_void_p), ("hit_inst", ctypes.c_void_p), ("hit_tri", ctypes.c_void_p),
                 ("sync", ctypes.c_int), ("host_outputs", ctypes.c_int), ("timing", ctypes.c_int),
                 ("textures", ctypes.c_int)]
+
+
+class QueryOpts(ctypes.Structure):
+    _fields_ = [("n", ctypes.c_int64), ("origin", ctypes.c_void_p), ("dir", ctypes.c_void_p), ("tmax", ctypes.c_void_p),
+                ("pixel", ctypes.c_void_p), ("use_bvh", ctypes.c_int), ("rebuild_bvh", ctypes.c_int),
+                ("any_hit", ctypes.c_int), ("host", ctypes.c_int),
+                ("t", ctypes.c_void_p), ("inst", ctypes.c_void_p), ("tri", ctypes.c_void_p), ("uv", ctypes.c_void_p),
+                ("normal", ctypes.c_void_p), ("hit", ctypes.c_void_p), ("rays_out", ctypes.c_void_p)]
+
+
+# rt_query's outputs: name -> (components per ray, dtype)
+QUERY_OUTPUTS = {"t": (1, np.float32), "inst": (1, np.int32), "tri": (1, np.int32), "uv": (2, np.float32),
+                 "normal": (3, np.float32), "hit": (1, np.uint8), "rays_out": (6, np.float32)}
 
 
 class Stats(ctypes.Structure):
@@ -141,6 +156,9 @@ def lib():
     L.rt_frame_work.argtypes = [vp, ctypes.POINTER(RenderOpts), ctypes.POINTER(Work)]
     L.rt_scene_set_devices.argtypes = [vp, vp, ip, ip]
     L.rt_scene_last_trace.argtypes = [vp, vp]
+    L.rt_query_opts_default.argtypes = [ctypes.POINTER(QueryOpts)]
+    L.rt_query_opts_default.restype = None
+    L.rt_query.argtypes = [vp, ctypes.POINTER(QueryOpts), ctypes.POINTER(Stats)]
     if hasattr(L, "rt_profile_marker"):         # (absent from libraries older than ABI 3's round 5: A/B runs)
         L.rt_profile_marker.argtypes = [ip, vp]
     if hasattr(L, "rt_copy_to_host_async"):     # ABI 4
@@ -457,6 +475,62 @@ class Scene:
         w = Work()
         _check(lib().rt_frame_work(self._h, ctypes.byref(o), ctypes.byref(w)))
         return (w.as_dict(), rgba) if want_rgba else w.as_dict()
+
+    # ---- ray queries (rt_query) ----
+    def query(self, origins=None, dirs=None, pixels=None, tmax=None, any_hit=False, use_bvh=True, rebuild_bvh=True,
+              want=("t", "inst", "tri"), stats=False):
+        """Closest hit (or, any_hit, occlusion) of caller-supplied rays: origins / dirs (n, 3), or
+        pixels (n, 2) for the camera's sample-0 rays.  Returns a dict of numpy arrays, one per
+        name in `want` (QUERY_OUTPUTS; any_hit: "hit" and "rays_out" only), plus "stats" on request."""
+        o = QueryOpts()
+        lib().rt_query_opts_default(ctypes.byref(o))
+        keep = []
+        if pixels is not None:
+            keep.append(np.ascontiguousarray(pixels, dtype=np.int32).reshape(-1, 2))
+            o.pixel, n = _ptr(keep[-1]), keep[-1].shape[0]
+        if origins is not None:
+            keep.append(_f(origins).reshape(-1, 3))
+            o.origin, n = _ptr(keep[-1]), keep[-1].shape[0]
+        if dirs is not None:
+            keep.append(_f(dirs).reshape(-1, 3))
+            o.dir, n = _ptr(keep[-1]), keep[-1].shape[0]
+        if not keep:
+            raise RtError(RT_ERR_ARG, "query: give origins and dirs, or pixels")
+        assert all(a.shape[0] == n for a in keep), "origins and dirs differ in length"
+        if tmax is not None:
+            keep.append(_f(np.broadcast_to(np.asarray(tmax, np.float32), (n,)), n))
+            o.tmax = _ptr(keep[-1])
+        o.n, o.use_bvh, o.rebuild_bvh, o.any_hit, o.host = n, int(use_bvh), int(rebuild_bvh), int(any_hit), 1
+        out = {}
+        for k in want:
+            c, dt = QUERY_OUTPUTS[k]
+            out[k] = np.zeros((n, c) if c > 1 else (n,), dt)
+            setattr(o, k, _ptr(out[k]))
+        st = Stats()
+        _check(lib().rt_query(self._h, ctypes.byref(o), ctypes.byref(st) if stats else None))
+        if stats:
+            out["stats"] = st.as_dict()
+        return out
+
+    def query_device(self, n, origin_ptr=None, dir_ptr=None, pixel_ptr=None, tmax_ptr=None, any_hit=False, use_bvh=True,
+                     rebuild_bvh=True, t_ptr=None, inst_ptr=None, tri_ptr=None, uv_ptr=None, normal_ptr=None,
+                     hit_ptr=None, rays_out_ptr=None, stats=False):
+        """rt_query on caller-owned DEVICE buffers (e.g. torch tensors' data_ptr()): float32
+        origins / dirs / tmax, int32 pixels and ids, uint8 hit.  Returns when the results are written."""
+        o = QueryOpts()
+        lib().rt_query_opts_default(ctypes.byref(o))
+        o.n, o.origin, o.dir, o.pixel, o.tmax = int(n), origin_ptr, dir_ptr, pixel_ptr, tmax_ptr
+        o.use_bvh, o.rebuild_bvh, o.any_hit, o.host = int(use_bvh), int(rebuild_bvh), int(any_hit), 0
+        o.t, o.inst, o.tri, o.uv, o.normal, o.hit, o.rays_out = t_ptr, inst_ptr, tri_ptr, uv_ptr, normal_ptr, hit_ptr, rays_out_ptr
+        st = Stats()
+        _check(lib().rt_query(self._h, ctypes.byref(o), ctypes.byref(st) if stats else None))
+        return st.as_dict() if stats else None
+
+    def pick(self, x, y):
+        """The instance under pixel (x, y): (inst, tri, t) of the camera's sample-0 ray, or
+        (-1, -1, inf) for the sky."""
+        r = self.query(pixels=[(int(x), int(y))])
+        return int(r["inst"][0]), int(r["tri"][0]), float(r["t"][0])
 
     def last_trace(self):
         """The trace kernel of the scene's most recent trace launch (rt_scene_last_trace)."""

@@ -27,7 +27,9 @@ extern "C" {
  * 4: rt_host_alloc / rt_host_free / rt_copy_to_host_async / rt_copy_engines_warm (host-readable
  *    frames through a copy engine); a finished scene is uploaded and warmed at creation when a gfx950 device is present
  * 5: rt_scene_last_trace (test hook: the trace kernel a launch used); rt_frame_work keeps its
- *    frame when rt_render_opts.rgba is set */
+ *    frame when rt_render_opts.rgba is set
+ *    (still 5: rt_query / rt_query_opts_default were added later; the change is additive, no
+ *    existing entry or struct changed, so the version callers compare against stays) */
 #define RT_ABI_VERSION 5
 
 enum {
@@ -186,6 +188,45 @@ typedef struct rt_work {
  * NULL: the frame is dropped.  radiance / hit_inst / hit_tri are never written.  opts->stream is
  * ignored: the call runs on the scene's own stream and returns when the frame is done. */
 int rt_frame_work(rt_scene* s, const rt_render_opts* opts, rt_work* work);
+
+/* ---- ray queries: closest hit or occlusion for caller-supplied rays ----
+ * The reference has no counterpart: its cast_ray (scene.cu:42-73) is reachable only through the
+ * integrator.  This entry runs that query for a batch of rays: the result of each ray is the
+ * reference's cast_ray, the accepted triangle the integrator's primary query would find.
+ * A side entry: it runs on the scene's own stream, waits for frames in flight, rotates no frame
+ * slot, launches no trace kernel (rt_scene_last_trace and the scheduling history are untouched)
+ * and returns when the results are complete.  A scene split by rt_scene_set_devices answers on
+ * its own device.
+ * A ray with a non-finite component, or whose direction normalises to the zero vector
+ * (rmath::Ray: a length <= 1e-5, or one that overflows float), reports a miss. */
+typedef struct rt_query_opts {
+    int64_t n;              /* rays */
+    const float* origin;    /* n*3 */
+    const float* dir;       /* n*3, any length > 0: normalised as rmath::Ray(o, d) does */
+    const float* tmax;      /* n, or NULL = +inf: hits with t >= tmax are not reported */
+    const int32_t* pixel;   /* n*2 (x, y): the camera's sample-0 ray of that pixel, made on the device by
+                               camera_at; exclusive with origin/dir */
+    int use_bvh, rebuild_bvh;   /* as rt_render_opts */
+    int any_hit;            /* 1: occlusion query, only `hit` is written (and rays_out, if asked for) */
+    int host;               /* 1: every pointer is host memory (staged); 0: device pointers */
+    /* outputs, each may be NULL */
+    float* t; int32_t* inst; int32_t* tri;   /* miss: +inf, -1, -1 */
+    float* uv;              /* n*2 barycentric weights of vertices 1, 2 (miss: 0) */
+    float* normal;          /* n*3 world normal as Isect::norm after cast_local (miss: 0) */
+    uint8_t* hit;           /* n: 1 = an accepted hit with THRESHOLD <= t < tmax */
+    float* rays_out;        /* n*6: origin and normalised direction the kernel traced */
+} rt_query_opts;
+/* zeros, use_bvh = rebuild_bvh = 1 */
+void rt_query_opts_default(rt_query_opts* o);
+/* stats NULL: the fast query.  Non-NULL: the reference's walk (the heap, or every instance with
+ * use_bvh = 0) runs instead and rays / nodes / leaves / tri_tests count it in the reference's
+ * units (rays: the rays that were traced; an occlusion query then runs without its early exit);
+ * bvh_ms / trace_ms are the BVH build and the query kernel.
+ * RT_ERR_ARG: null opts, n < 0, neither pixel nor both of origin and dir, pixel together with
+ * either, no output requested, any_hit without `hit`, and with host = 1 a pixel outside the canvas
+ * (device pixels are the caller's to keep inside it).  n = 0: RT_OK, nothing is done.
+ * RT_ERR_NODEV: no usable device. */
+int rt_query(rt_scene* s, const rt_query_opts* opts, rt_stats* stats);
 
 /* Frame slots (1 = default, up to 8).  The reference rebuilds its BVH inside every
  * update_scene call (raytracer.cu:103-119), so a frame owns per-frame state: BVH, work
