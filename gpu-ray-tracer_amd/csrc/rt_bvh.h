@@ -149,4 +149,11 @@ __device__ __forceinline__ void bvh_fnode(const BvhArgs& A, const unsigned long 
 size_t bvh_large_scratch_bytes(int n);
 hipError_t bvh_build_large(const BvhArgs& A, void* scratch, hipStream_t st, hipEvent_t e0, hipEvent_t e1);
 
+// The same stable radix sort for rt_query's coherence order (RT_QUERY_ORDER_SORTED): n (ray key,
+// ray index) pairs by the keys' low key_bits bits, on `st`; the sorted pairs land in k_out /
+// v_out.  `temp` holds ray_sort_temp_bytes(n, key_bits) bytes (hipCUB's temporary storage).
+size_t ray_sort_temp_bytes(long long n, int key_bits);
+hipError_t ray_sort_pairs(void* temp, size_t temp_bytes, const unsigned long long* k_in, unsigned long long* k_out,
+                          const uint32_t* v_in, uint32_t* v_out, long long n, int key_bits, hipStream_t st);
+
 }  // namespace rtb

@@ -112,4 +112,16 @@ hipError_t bvh_build_large(const BvhArgs& A, void* scratch, hipStream_t st, hipE
     return hipSuccess;
 }
 
+size_t ray_sort_temp_bytes(long long n, int key_bits) {
+    size_t tb = 0;
+    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, tb, (unsigned long long*)nullptr, (unsigned long long*)nullptr,
+                                             (uint32_t*)nullptr, (uint32_t*)nullptr, (int)n, 0, key_bits);
+    return tb;
+}
+
+hipError_t ray_sort_pairs(void* temp, size_t temp_bytes, const unsigned long long* k_in, unsigned long long* k_out,
+                          const uint32_t* v_in, uint32_t* v_out, long long n, int key_bits, hipStream_t st) {
+    return hipcub::DeviceRadixSort::SortPairs(temp, temp_bytes, k_in, k_out, v_in, v_out, (int)n, 0, key_bits, st);
+}
+
 }  // namespace rtb

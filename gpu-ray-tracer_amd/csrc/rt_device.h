@@ -13,6 +13,7 @@
 
 #include "rt_bvh.h"
 #include "rt_math.h"
+#include "rt_raykey.h"
 #include "rt_scene.h"
 
 // Tuning parameters (build switches; the A/B logs under profiles/ record the values tried).
@@ -178,6 +179,7 @@ struct QueryParams {
     unsigned char* hit;                         // [n]
     float* rays_out;                            // [6n] origin, normalised direction
     unsigned long long* stats;                  // counted kernels: rays, nodes, leaves, triangle tests
+    const uint32_t* order;                      // ORD kernels: lane l of chunk c traces ray order[64 c + l] (a permutation of [0, n))
 };
 
 }  // namespace rtd
@@ -207,9 +209,14 @@ hipError_t launch_trace_kernel(const TraceVariant& v, int blocks, TraceParams& P
 // The query kernel for a batch (query_plan's key looked up in the table of query kernels; null fn:
 // no kernel with this key, a programming error) and its launch.  S: view_of's scene with the
 // camera-ray shortcuts off (rt_query).
-struct QueryVariant : QueryKey { const void* fn; };
-QueryVariant choose_query_variant(long long n_rays, const SceneView& S, bool any_hit, bool counted, int n_cu, int form);
+// ordered: the ORD = 1 instantiation, which traces the rays in QueryParams::order's order (uncounted only).
+struct QueryVariant : QueryKey { const void* fn; bool ordered; };
+QueryVariant choose_query_variant(long long n_rays, const SceneView& S, bool any_hit, bool counted, int n_cu, int form,
+                                  bool ordered = false);
 hipError_t launch_query_kernel(const QueryVariant& v, QueryParams& Q, SceneView& S, hipStream_t st);
+// ray_key_kernel (RT_QUERY_ORDER_SORTED): keys[i] = ray_key of ray i of the batch as query_kernel
+// would trace it (Q's origin / dir or pixel and camera) in `box`, idx[i] = i.
+hipError_t launch_ray_keys(QueryParams& Q, const rtk::KeyBox& box, unsigned long long* keys, uint32_t* idx, hipStream_t st);
 // The single-workgroup BVH build (A.n <= BVH_WG_LEAVES) with `lds` bytes of dynamic LDS.
 hipError_t launch_bvh_build(rtb::BvhArgs& A, bool lds_tree, size_t lds, hipStream_t st, hipEvent_t e0, hipEvent_t e1);
 size_t scene_image_bytes(const SceneView& S);   // the scene image a fast kernel's block stages in LDS

@@ -142,6 +142,19 @@ struct rt_scene {
     // rt_query with host pointers: one pinned host image of the batch (inputs, then outputs) and
     // its device copy; they grow and are kept, so a warm call allocates nothing
     unsigned char* q_host = nullptr; unsigned char* q_dev = nullptr; size_t q_cap = 0;
+    // rt_query_set_order: the mode (host state), and the sorted mode's scratch for qo_rays rays
+    // (query_order_plan: keys and ray indices, double-buffered, then hipCUB's qo_temp bytes); it
+    // grows like q_dev and is kept.  q_box: the keys' quantisation box, for the poses of q_box_gen.
+    int query_order = RT_QUERY_ORDER_CALLER;
+    unsigned char* qo_dev = nullptr; long long qo_rays = 0; size_t qo_temp = 0;
+    rtk::KeyBox q_box{{0, 0, 0}, {0, 0, 0}};
+    unsigned q_box_gen = 0;
+    // the most recent rt_query (rt_query_last): its kernel and launch, whether the batch was
+    // sorted, its size, the box its keys used and the device array of its order; host state
+    rtd::QueryVariant last_query{};
+    bool has_last_query = false, last_query_sorted = false;
+    long long last_query_n = 0;
+    const uint32_t* last_query_order = nullptr;
     std::vector<hipEvent_t> tev;     // timing=1 events, 4 per frame: bvh start/stop, trace start/stop (pool)
     size_t tev_used = 0;
     size_t d_out_px = 0;

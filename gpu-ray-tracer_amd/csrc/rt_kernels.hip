@@ -1986,9 +1986,11 @@ __global__ __launch_bounds__(SKY_THREADS) void sky_kernel(TraceParams P, SceneVi
 // cut with a slack formed per ray from its own origin (below).
 // A ray with a non-finite component, or whose direction normalises to zero (rmath::Ray:
 // shorter than 1e-5, or too long for its length to be finite), is inactive from the start: it
-// reports a miss and takes no part in the wave's ballots.
+// reports a miss and takes no part in the wave's ballots.  That test is rtk::caller_ray /
+// rtk::ray_traceable (rt_raykey.h), shared with the coherence key.
+// ORD (RT_QUERY_ORDER_SORTED, uncounted kernels): lane l of chunk c traces ray order[64 c + l]
+// instead of ray 64 c + l, and writes every output at that ray's own index; otherwise the same code.
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ bool finite3(V3 v) { return isfinite(v.x) && isfinite(v.y) && isfinite(v.z); }
 
 // The batch's QueryParams read in place from the kernel-argument segment, through a pointer made
 // fresh at each use (kparams' reason: by value, its pointers and the camera were loaded once and
@@ -2000,12 +2002,13 @@ __device__ __forceinline__ KQP& qparams() {
     return *p;
 }
 
-template <int TREE, bool LDS, bool ANY, bool STATS>
+template <int TREE, bool LDS, bool ANY, bool STATS, bool ORD = false>
 __global__ __launch_bounds__(TRACE_BLOCK_P) void query_kernel(QueryParams Q_arg, SceneView S) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     (void)Q_arg;                                               // read in place: qparams()
     constexpr bool FT = TREE == QT_ORDERED, BRUTE = TREE == QT_BRUTE;
     static_assert(!(STATS && (FT || ANY)), "a counted query is the whole reference walk");
+    static_assert(!(STATS && ORD), "a counted query runs in caller order");
     const BvhRefs bv = stage_bvh<LDS, FT, false, BRUTE>(S, smem);
     const int lane = threadIdx.x & 63;
     const int block_waves = (int)(blockDim.x >> 6);
@@ -2013,8 +2016,9 @@ __global__ __launch_bounds__(TRACE_BLOCK_P) void query_kernel(QueryParams Q_arg,
     const long long stride = (long long)gridDim.x * block_waves;
     WaveCounters wc{0, 0, 0, 0};
     for (long long c = (long long)blockIdx.x * block_waves + (long long)(threadIdx.x >> 6); c < chunks; c += stride) {
-        const long long i = c * 64 + lane;
-        const bool in = i < qparams().n;
+        const long long slot = c * 64 + lane;
+        const bool in = slot < qparams().n;
+        const long long i = (ORD && in) ? (long long)qparams().order[slot] : slot;   // the sorted batch: this slot's ray
         Ray r{v3(0, 0, 0), v3(0, 0, 1)};
         bool ok = in;
         if (in) {
@@ -2025,9 +2029,11 @@ __global__ __launch_bounds__(TRACE_BLOCK_P) void query_kernel(QueryParams Q_arg,
                 const V3 o = v3(Q.origin[3 * i], Q.origin[3 * i + 1], Q.origin[3 * i + 2]);
                 const V3 d = v3(Q.dir[3 * i], Q.dir[3 * i + 1], Q.dir[3 * i + 2]);
                 r = make_ray(o, d);                            // Ray ctor (geometry.h:216)
-                ok = finite3(d);
+                ok = rtk::finite3(d);
             }
-            ok = ok && finite3(r.o) && finite3(r.d) && (r.d.x != 0.0f || r.d.y != 0.0f || r.d.z != 0.0f);
+            // (rtk::caller_ray's value, kept in these two steps: one call per branch measured one
+            // VGPR more in every instantiation)
+            ok = ok && rtk::ray_traceable(r);
             if (Q.rays_out) {
                 float* ro = Q.rays_out + 6 * i;
                 ro[0] = r.o.x; ro[1] = r.o.y; ro[2] = r.o.z; ro[3] = r.d.x; ro[4] = r.d.y; ro[5] = r.d.z;
@@ -2085,6 +2091,31 @@ __global__ __launch_bounds__(TRACE_BLOCK_P) void query_kernel(QueryParams Q_arg,
         if (wc.leaves) atomicAdd(&Q.stats[2], wc.leaves);
         if (wc.tris) atomicAdd(&Q.stats[3], wc.tris);
     }
+}
+
+// The coherence keys of a batch (RT_QUERY_ORDER_SORTED): keys[i] = rtk::ray_key of ray i as
+// query_kernel traces it (the same caller_ray / camera_at and the same test), idx[i] = i; the
+// stable sort of the pairs is the order the ORD kernels read.  One ray per lane.  A lane's
+// origin and direction are three dwords 12 bytes apart: a wave's three loads each touch the
+// same 768 contiguous bytes, so every fetched line is used whole, and the key and index stores
+// are contiguous (8 and 4 bytes a lane).  The box and pointers come as kernel arguments.
+constexpr int KEY_BLOCK = 256;
+__global__ __launch_bounds__(KEY_BLOCK) void ray_key_kernel(QueryParams Q, rtk::KeyBox box, unsigned long long* __restrict__ keys,
+                                                            uint32_t* __restrict__ idx) {
+    const long long i = (long long)blockIdx.x * KEY_BLOCK + threadIdx.x;
+    if (i >= Q.n) return;
+    Ray r;
+    bool ok;
+    if (Q.pixel) {
+        r = camera_at(Q.cam, (float)Q.pixel[2 * i], (float)Q.pixel[2 * i + 1]);
+        ok = rtk::ray_traceable(r);
+    } else {
+        const V3 o = v3(Q.origin[3 * i], Q.origin[3 * i + 1], Q.origin[3 * i + 2]);
+        const V3 d = v3(Q.dir[3 * i], Q.dir[3 * i + 1], Q.dir[3 * i + 2]);
+        ok = rtk::caller_ray(o, d, r);
+    }
+    keys[i] = rtk::ray_key(r, ok, box);
+    idx[i] = (uint32_t)i;
 }
 
 // ---------------------------------------------------------------------------
@@ -2351,6 +2382,11 @@ __global__ void kat_kernel(int op, int n, const float* a, const float* b, const 
             oi[2 * i] = h0; oi[2 * i + 1] = h1;
             break;
         }
+        case 21: {   // ray_key (rt_raykey.h): a ray as traced (origin, unit direction) in a box (mn, mx)
+            const Ray r{L3(a + 6 * i), L3(a + 6 * i + 3)};
+            ou[i] = rtk::ray_key(r, rtk::KeyBox{L3(b + 6 * i), L3(b + 6 * i + 3)});
+            break;
+        }
         default: break;
     }
 }
@@ -2436,24 +2472,32 @@ TraceVariant choose_trace_variant(const SceneView& S, int spp, bool tex, bool wa
 
 // The query kernels (rt_query): every instantiation of query_kernel, named here once.  query_plan
 // (rt_plan.h) decides which of them a batch gets.
-struct QueryEntry { int tree; bool lds, any_hit, counted; const void* fn; };
-#define QK(TREE, LDS, ANY, STATS) QueryEntry{TREE, LDS, ANY, STATS, (const void*)query_kernel<TREE, LDS, ANY, STATS>}
+struct QueryEntry { int tree; bool lds, any_hit, counted, ordered; const void* fn; };
+#define QK(TREE, LDS, ANY, STATS) QueryEntry{TREE, LDS, ANY, STATS, false, (const void*)query_kernel<TREE, LDS, ANY, STATS>}
 #define QK4(TREE) QK(TREE, false, false, false), QK(TREE, true, false, false), QK(TREE, false, true, false), QK(TREE, true, true, false)
+#define QKO(TREE, LDS, ANY) QueryEntry{TREE, LDS, ANY, false, true, (const void*)query_kernel<TREE, LDS, ANY, false, true>}
+#define QKO4(TREE) QKO(TREE, false, false), QKO(TREE, true, false), QKO(TREE, false, true), QKO(TREE, true, true)
 static const QueryEntry query_kernels[] = {
     QK4(QT_ORDERED), QK4(QT_HEAP), QK4(QT_BRUTE),
     // counted: the reference heap walk, or the reference's instance loop
     QK(QT_HEAP, false, false, true), QK(QT_HEAP, true, false, true),
     QK(QT_BRUTE, false, false, true), QK(QT_BRUTE, true, false, true),
+    // ORD: the uncounted kernels over a sorted batch (RT_QUERY_ORDER_SORTED)
+    QKO4(QT_ORDERED), QKO4(QT_HEAP), QKO4(QT_BRUTE),
 };
+#undef QKO4
+#undef QKO
 #undef QK4
 #undef QK
-static_assert(sizeof query_kernels / sizeof *query_kernels == 16, "the query kernels of the build");
+static_assert(sizeof query_kernels / sizeof *query_kernels == 28, "the query kernels of the build");
 
-QueryVariant choose_query_variant(long long n_rays, const SceneView& S, bool any_hit, bool counted, int n_cu, int form) {
+QueryVariant choose_query_variant(long long n_rays, const SceneView& S, bool any_hit, bool counted, int n_cu, int form,
+                                  bool ordered) {
     QueryVariant v{};
     static_cast<QueryKey&>(v) = query_plan(n_rays, S, any_hit, counted, n_cu, form);
+    v.ordered = ordered;
     for (const QueryEntry& e : query_kernels)
-        if (e.tree == v.tree && e.lds == v.lds && e.any_hit == v.any_hit && e.counted == v.counted) v.fn = e.fn;
+        if (e.tree == v.tree && e.lds == v.lds && e.any_hit == v.any_hit && e.counted == v.counted && e.ordered == ordered) v.fn = e.fn;
     if (v.fn && v.shm > 64 * 1024) (void)hipFuncSetAttribute(v.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v.shm);
     return v;
 }
@@ -2461,6 +2505,11 @@ QueryVariant choose_query_variant(long long n_rays, const SceneView& S, bool any
 hipError_t launch_query_kernel(const QueryVariant& v, QueryParams& Q, SceneView& S, hipStream_t st) {
     void* args[] = {&Q, &S};
     return hipExtLaunchKernel(v.fn, dim3(v.blocks), dim3(v.block), args, v.shm, st, nullptr, nullptr, 0);
+}
+
+hipError_t launch_ray_keys(QueryParams& Q, const rtk::KeyBox& box, unsigned long long* keys, uint32_t* idx, hipStream_t st) {
+    hipLaunchKernelGGL(ray_key_kernel, dim3((unsigned)((Q.n + KEY_BLOCK - 1) / KEY_BLOCK)), dim3(KEY_BLOCK), 0, st, Q, box, keys, idx);
+    return hipGetLastError();
 }
 
 hipError_t launch_sky(bool brute, int blocks, TraceParams& P, SceneView& S, unsigned char* gsky, int* live,

@@ -356,4 +356,29 @@ inline QueryKey query_plan(long long n_rays, const SceneView& S, bool any_hit, b
     return k;
 }
 
+// ---- The coherence order of a batch (rt_query_set_order): whether rt_query sorts the batch
+// by ray key (rt_raykey.h) before it traces, the key bits the sort looks at, and the scene's
+// scratch for it: keys (8 B) and ray indices (4 B), double-buffered, each buffer rounded up to
+// 256 B; hipCUB's temporary storage follows them (its size is the library's to say).  A counted
+// query stays in caller order (its counters are sums over the rays, whatever their waves) and
+// so does a batch of one wave.  Ray indices are 32-bit: the caller checks n < 2^31 first.
+enum : int { QUERY_ORDER_CALLER = 0, QUERY_ORDER_SORTED = 1 };
+struct QueryOrderPlan {
+    bool sort;
+    int key_bits;             // SortPairs' end_bit (begin_bit 0)
+    size_t keys_bytes, idx_bytes;   // one buffer of each
+    size_t scratch_bytes;     // 2 keys_bytes + 2 idx_bytes
+};
+inline QueryOrderPlan query_order_plan(long long n_rays, int mode, bool counted) {
+    QueryOrderPlan p{};
+    p.sort = mode == QUERY_ORDER_SORTED && !counted && n_rays > 64;
+    if (!p.sort) return p;
+    auto a256 = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    p.key_bits = rtk::RAYKEY_BITS;
+    p.keys_bytes = a256(8 * (size_t)n_rays);
+    p.idx_bytes = a256(4 * (size_t)n_rays);
+    p.scratch_bytes = 2 * p.keys_bytes + 2 * p.idx_bytes;
+    return p;
+}
+
 }  // namespace rtd

@@ -664,6 +664,45 @@ int begin_side_entry(rt_scene* s, int spp, bool bvh) {
     return bvh ? build_bvh(s, sstream(s)) : RT_OK;
 }
 
+// The quantisation box of rt_query's coherence keys (rt_raykey.h): the instances' world boxes
+// (bvh_inst_box's arithmetic: the mesh box moved by the instance pose) merged, on the host,
+// for the current poses; the same box with and without the BVH.  Degenerate and non-finite
+// boxes are left out (no box at all: zeros, every origin in cell 0).
+void refresh_query_box(rt_scene* s) {
+    if (s->q_box_gen == s->inst_gen) return;
+    const std::vector<Box> mbox = mesh_boxes(s->h);
+    rtk::KeyBox kb{v3(INFINITY, INFINITY, INFINITY), v3(-INFINITY, -INFINITY, -INFINITY)};
+    bool any = false;
+    for (const DInst& in : s->h.d_insts) {
+        const Box b = from_local(mbox[in.mesh], in.pose);
+        if (!b.nd || !rtk::finite3(b.mn) || !rtk::finite3(b.mx)) continue;
+        kb.mn = v3(std::min(kb.mn.x, b.mn.x), std::min(kb.mn.y, b.mn.y), std::min(kb.mn.z, b.mn.z));
+        kb.mx = v3(std::max(kb.mx.x, b.mx.x), std::max(kb.mx.y, b.mx.y), std::max(kb.mx.z, b.mx.z));
+        any = true;
+    }
+    s->q_box = any ? kb : rtk::KeyBox{v3(0, 0, 0), v3(0, 0, 0)};
+    s->q_box_gen = s->inst_gen;
+}
+
+// The sorted mode's scratch for a batch of n rays (query_order_plan's layout at the capacity,
+// then hipCUB's temporary storage, whose size is asked once per capacity).  A failed allocation
+// leaves the scene without scratch, otherwise as it was.
+int ensure_order_scratch(rt_scene* s, long long n) {
+    if (n <= s->qo_rays) return RT_OK;
+    const long long cap = std::min<long long>(std::max(n, 2 * s->qo_rays), INT32_MAX);
+    const QueryOrderPlan P = query_order_plan(cap, QUERY_ORDER_SORTED, false);
+    const size_t temp = (ray_sort_temp_bytes(cap, P.key_bits) + 255) & ~(size_t)255;
+    dfree(s->qo_dev); s->qo_rays = 0; s->qo_temp = 0;
+    s->last_query_order = nullptr;                             // (rt_query_last: the last order went with the buffer)
+    if (hipMalloc((void**)&s->qo_dev, P.scratch_bytes + temp) != hipSuccess) {
+        s->qo_dev = nullptr;
+        return fail(RT_ERR_HIP, std::string("rt_query: no memory for the sort of ") + std::to_string(n) + " rays: " +
+                                    hipGetErrorString(hipGetLastError()));
+    }
+    s->qo_rays = cap; s->qo_temp = temp;
+    return RT_OK;
+}
+
 // Zero the counters; the two minima (slots 15 and 19: the waves' earliest start and earliest end,
 // trace_kernel) start at all ones.
 int clear_stats(rt_scene* s, hipStream_t st) {
@@ -720,7 +759,7 @@ rt_scene::~rt_scene() {
     dfree(d_tris); dfree(d_meshes); dfree(d_mats); dfree(d_lights); dfree(d_tri_ax);
     dfree(d_mesh_box); dfree(d_spp); dfree(d_stats); dfree(d_canvas); dfree(d_dbg);
     for (auto& p : d_out) dfree(p);
-    dfree(q_dev); hfree(q_host);
+    dfree(q_dev); hfree(q_host); dfree(qo_dev);
     for (auto& e : ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : tev) (void)hipEventDestroy(e);
     for (auto& f : slots) f.release();
@@ -1318,6 +1357,8 @@ int rt_query(rt_scene* s, const rt_query_opts* o, rt_stats* stats) {
     if (any ? !o->hit : !(o->t || o->inst || o->tri || o->uv || o->normal || o->hit || o->rays_out))
         return fail(RT_ERR_ARG, any ? "rt_query: an occlusion query writes `hit`" : "rt_query: no output requested");
     const size_t n = (size_t)o->n;
+    if (s->query_order == RT_QUERY_ORDER_SORTED && o->n > (int64_t)INT32_MAX)
+        return fail(RT_ERR_LIMIT, "rt_query: RT_QUERY_ORDER_SORTED takes at most 2^31 - 1 rays (32-bit ray indices)");
     if (o->host && by_pixel)
         for (size_t i = 0; i < n; i++) {
             const int x = o->pixel[2 * i], y = o->pixel[2 * i + 1];
@@ -1328,6 +1369,9 @@ int rt_query(rt_scene* s, const rt_query_opts* o, rt_stats* stats) {
     if ((r = begin_side_entry(s, 1, false)) != RT_OK) return r;   // upload, frames in flight, current poses
     hipStream_t st = sstream(s);
     const bool counted = stats != nullptr;
+    // the sorted mode's scratch, before anything of this call is in flight
+    const QueryOrderPlan OP = query_order_plan(o->n, s->query_order, counted);
+    if (OP.sort && (r = ensure_order_scratch(s, o->n)) != RT_OK) return r;
     if (counted) { HIPCHK(hipMemsetAsync(s->d_stats, 0, STATS_N * sizeof(unsigned long long), st)); HIPCHK(hipEventRecord(s->ev[0], st)); }
     if (o->use_bvh && (o->rebuild_bvh || !s->cur().bvh_valid) && (r = build_bvh(s, st)) != RT_OK) return r;
     if (counted) HIPCHK(hipEventRecord(s->ev[1], st));
@@ -1381,12 +1425,32 @@ int rt_query(rt_scene* s, const rt_query_opts* o, rt_stats* stats) {
     Q.any_margin = margin <= 0.125f ? margin : -1.0f;
     int form = -1;                                             // RT_QUERY_FORM (measurements): small / persistent
     if (const char* e = getenv("RT_QUERY_FORM")) form = !strcmp(e, "small") ? 0 : !strcmp(e, "persistent") ? 1 : -1;
-    const QueryVariant V = choose_query_variant(o->n, S, any, counted, s->n_cu, form);
+    const QueryVariant V = choose_query_variant(o->n, S, any, counted, s->n_cu, form, OP.sort);
     if (!V.fn)
         return fail(RT_ERR_STATE, "no query kernel <" + std::to_string(V.tree) + ", " + std::to_string((int)V.lds) + ", " +
-                                      std::to_string((int)V.any_hit) + ", " + std::to_string((int)V.counted) + ">");
-    HIPCHK(launch_query_kernel(V, Q, S, st));
+                                      std::to_string((int)V.any_hit) + ", " + std::to_string((int)V.counted) + ", " +
+                                      std::to_string((int)V.ordered) + ">");
+    bool trace = true;
+    if (OP.sort) {
+        // key, sort, trace: stream-ordered, no host synchronisation between them.  The buffers
+        // are laid out for the scratch's capacity; the sort looks at the key bits in use only.
+        refresh_query_box(s);
+        const QueryOrderPlan CP = query_order_plan(s->qo_rays, QUERY_ORDER_SORTED, false);
+        unsigned char* p = s->qo_dev;
+        unsigned long long* k_in = (unsigned long long*)p; p += CP.keys_bytes;
+        unsigned long long* k_out = (unsigned long long*)p; p += CP.keys_bytes;
+        uint32_t* v_in = (uint32_t*)p; p += CP.idx_bytes;
+        uint32_t* v_out = (uint32_t*)p; p += CP.idx_bytes;
+        HIPCHK(launch_ray_keys(Q, s->q_box, k_in, v_in, st));
+        HIPCHK(ray_sort_pairs(p, s->qo_temp, k_in, k_out, v_in, v_out, o->n, OP.key_bits, st));
+        Q.order = v_out;
+        // RT_QUERY_SORT_ONLY (measurements, tools/query_bench.py): stop after the sort; no output is written
+        if (const char* e = getenv("RT_QUERY_SORT_ONLY")) trace = atoi(e) == 0;
+    }
+    if (trace) HIPCHK(launch_query_kernel(V, Q, S, st));
     HIPCHK(hipGetLastError());
+    s->last_query = V; s->has_last_query = true;               // rt_query_last
+    s->last_query_sorted = OP.sort; s->last_query_n = o->n; s->last_query_order = Q.order;
     if (counted) HIPCHK(hipEventRecord(s->ev[2], st));
     if (o->host && total > in_bytes)
         HIPCHK(hipMemcpyAsync(s->q_host + in_bytes, s->q_dev + in_bytes, total - in_bytes, hipMemcpyDeviceToHost, st));
@@ -1402,6 +1466,38 @@ int rt_query(rt_scene* s, const rt_query_opts* o, rt_stats* stats) {
         HIPCHK(hipEventElapsedTime(&a, s->ev[0], s->ev[1]));
         HIPCHK(hipEventElapsedTime(&b, s->ev[1], s->ev[2]));
         stats->bvh_ms = a; stats->trace_ms = b;
+    }
+    return RT_OK;
+}
+
+int rt_query_set_order(rt_scene* s, int mode) {
+    CHECK_SCENE(s);
+    if (mode != RT_QUERY_ORDER_CALLER && mode != RT_QUERY_ORDER_SORTED)
+        return fail(RT_ERR_ARG, "query order: RT_QUERY_ORDER_CALLER or RT_QUERY_ORDER_SORTED");
+    s->query_order = mode;
+    return RT_OK;
+}
+
+int rt_query_last(const rt_scene* s, int32_t* out8, float* bounds6, uint32_t* order, int64_t order_cap) {
+    CHECK_FINISHED(s);
+    if (!s->has_last_query) return fail(RT_ERR_STATE, "no rt_query yet");
+    const QueryVariant& k = s->last_query;
+    const bool sorted = s->last_query_sorted;
+    if (order && sorted && order_cap < s->last_query_n) return fail(RT_ERR_ARG, "rt_query_last: order_cap is below the batch's n");
+    if (out8) {
+        const int32_t v[8] = {k.tree, (int32_t)k.lds, (int32_t)k.any_hit, (int32_t)k.counted, (int32_t)k.ordered,
+                              (int32_t)k.persistent, k.blocks, (int32_t)sorted};
+        std::copy(v, v + 8, out8);
+    }
+    if (bounds6) {
+        const rtk::KeyBox b = sorted ? s->q_box : rtk::KeyBox{v3(0, 0, 0), v3(0, 0, 0)};
+        const float v[6] = {b.mn.x, b.mn.y, b.mn.z, b.mx.x, b.mx.y, b.mx.z};
+        std::copy(v, v + 6, bounds6);
+    }
+    if (order && sorted) {
+        if (!s->last_query_order) return fail(RT_ERR_STATE, "rt_query_last: the last order's buffer was released");
+        HIPCHK(hipSetDevice(s->device));
+        HIPCHK(hipMemcpy(order, s->last_query_order, (size_t)s->last_query_n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     }
     return RT_OK;
 }
@@ -1468,14 +1564,14 @@ int rt_kat_device(const char* op, int n, const float* in0, const float* in1, con
                   uint64_t* ou) {
     static const char* ops[] = {"normalize3", "cross", "reflect", "refract", "quat_rotate", "quat_inverse", "quat_mul",
                                 "tri_hit", "ray_ctor", "zorder", "to_mat3", "box_hit", "pow", "tri_hit_f", "box_hit_f",
-                                "box_pair", "rcp_cr", "sqrt_cr", "box_from_local", "box_merge", "entity"};
+                                "box_pair", "rcp_cr", "sqrt_cr", "box_from_local", "box_merge", "entity", "ray_key"};
     // per-op sizes (floats): in0, in1, in2, out_f, out_i, out_u per element
     static const int sz[][6] = {{3, 0, 0, 3, 0, 0}, {3, 3, 0, 3, 0, 0}, {3, 3, 0, 3, 0, 0}, {3, 3, 2, 3, 1, 0},
                                 {4, 3, 0, 3, 0, 0}, {4, 0, 0, 4, 0, 0}, {4, 4, 0, 4, 0, 0}, {9, 6, 0, 3, 1, 0},
                                 {6, 0, 0, 6, 0, 0}, {3, 0, 0, 0, 0, 1}, {4, 0, 0, 9, 0, 0}, {7, 6, 0, 0, 1, 0},
                                 {1, 1, 0, 1, 0, 0}, {9, 6, 0, 3, 1, 0}, {7, 6, 0, 0, 1, 0}, {14, 6, 0, 0, 2, 0},
                                 {1, 0, 0, 1, 0, 0}, {1, 0, 0, 1, 0, 0}, {7, 7, 0, 6, 1, 0}, {7, 7, 0, 6, 1, 0},
-                                {7, 3, 0, 12, 0, 0}};
+                                {7, 3, 0, 12, 0, 0}, {6, 6, 0, 0, 0, 1}};
     if (!op || n <= 0) return fail(RT_ERR_ARG, "bad arguments");
     int k = -1;
     for (int i = 0; i < (int)(sizeof ops / sizeof *ops); i++) if (!strcmp(op, ops[i])) k = i;

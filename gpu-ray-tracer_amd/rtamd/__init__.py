@@ -40,7 +40,9 @@ SYMBOLS = [
     "rt_scene_atlas_info", "rt_scene_set_frame_slots", "rt_scene_set_overlap", "rt_frame_work",
     "rt_scene_set_devices", "rt_profile_marker", "rt_host_alloc", "rt_host_free", "rt_copy_to_host_async",
     "rt_copy_engines_warm", "rt_scene_last_trace", "rt_query_opts_default", "rt_query",
+    "rt_query_set_order", "rt_query_last",
 ]
+RT_QUERY_ORDER_CALLER, RT_QUERY_ORDER_SORTED = 0, 1
 
 
 class RtError(RuntimeError):
@@ -159,6 +161,9 @@ def lib():
     L.rt_query_opts_default.argtypes = [ctypes.POINTER(QueryOpts)]
     L.rt_query_opts_default.restype = None
     L.rt_query.argtypes = [vp, ctypes.POINTER(QueryOpts), ctypes.POINTER(Stats)]
+    if hasattr(L, "rt_query_set_order"):        # (absent from libraries before the coherence sort: A/B runs)
+        L.rt_query_set_order.argtypes = [vp, ip]
+        L.rt_query_last.argtypes = [vp, vp, vp, vp, ctypes.c_int64]
     if hasattr(L, "rt_profile_marker"):         # (absent from libraries older than ABI 3's round 5: A/B runs)
         L.rt_profile_marker.argtypes = [ip, vp]
     if hasattr(L, "rt_copy_to_host_async"):     # ABI 4
@@ -477,11 +482,50 @@ class Scene:
         return (w.as_dict(), rgba) if want_rgba else w.as_dict()
 
     # ---- ray queries (rt_query) ----
+    def set_query_order(self, mode):
+        """RT_QUERY_ORDER_CALLER (0, default) or RT_QUERY_ORDER_SORTED (1): whether query / query_device
+        sort a batch into coherent waves on the device before tracing it (rt_query_set_order).  The
+        results are the same arrays either way; sorting pays for itself on incoherent batches."""
+        _check(lib().rt_query_set_order(self._h, int(mode)))
+        self._query_order = int(mode)
+
+    def _query(self, o, st, reorder):
+        """rt_query; reorder=True: in RT_QUERY_ORDER_SORTED for this call, the scene's mode restored after it."""
+        before = getattr(self, "_query_order", RT_QUERY_ORDER_CALLER)
+        if reorder:
+            self.set_query_order(RT_QUERY_ORDER_SORTED)
+        try:
+            _check(lib().rt_query(self._h, ctypes.byref(o), ctypes.byref(st) if st is not None else None))
+            if o.n > 0:                                        # (n = 0 returns before any launch)
+                self._last_query_n = int(o.n)
+        finally:
+            if reorder:
+                self.set_query_order(before)
+
+    def query_last(self, want_order=False):
+        """The scene's most recent rt_query (rt_query_last): its kernel's TREE / LDS / ANY / STATS, whether
+        the ordered kernel ran, the form, the grid, whether the batch was sorted, and the keys' box;
+        want_order: also "order", the sorted batch's ray order (None if it was not sorted)."""
+        v, b = np.zeros(8, np.int32), np.zeros(6, np.float32)
+        _check(lib().rt_query_last(self._h, _ptr(v), _ptr(b), None, 0))
+        keys = ["tree", "lds", "any_hit", "counted", "ordered", "persistent", "blocks", "sorted"]
+        d = dict(zip(keys, [int(x) for x in v]))
+        d["bounds"] = b
+        if want_order:
+            d["order"] = None
+            if d["sorted"]:
+                n = getattr(self, "_last_query_n", 0)          # (the batch size of this object's last query)
+                order = np.zeros(max(1, n), np.uint32)
+                _check(lib().rt_query_last(self._h, None, None, _ptr(order), n))
+                d["order"] = order[:n]
+        return d
+
     def query(self, origins=None, dirs=None, pixels=None, tmax=None, any_hit=False, use_bvh=True, rebuild_bvh=True,
-              want=("t", "inst", "tri"), stats=False):
+              want=("t", "inst", "tri"), stats=False, reorder=False):
         """Closest hit (or, any_hit, occlusion) of caller-supplied rays: origins / dirs (n, 3), or
         pixels (n, 2) for the camera's sample-0 rays.  Returns a dict of numpy arrays, one per
-        name in `want` (QUERY_OUTPUTS; any_hit: "hit" and "rays_out" only), plus "stats" on request."""
+        name in `want` (QUERY_OUTPUTS; any_hit: "hit" and "rays_out" only), plus "stats" on request.
+        reorder=True: this call runs in RT_QUERY_ORDER_SORTED (set_query_order), whatever the scene's mode."""
         o = QueryOpts()
         lib().rt_query_opts_default(ctypes.byref(o))
         keep = []
@@ -507,23 +551,24 @@ class Scene:
             out[k] = np.zeros((n, c) if c > 1 else (n,), dt)
             setattr(o, k, _ptr(out[k]))
         st = Stats()
-        _check(lib().rt_query(self._h, ctypes.byref(o), ctypes.byref(st) if stats else None))
+        self._query(o, st if stats else None, reorder)
         if stats:
             out["stats"] = st.as_dict()
         return out
 
     def query_device(self, n, origin_ptr=None, dir_ptr=None, pixel_ptr=None, tmax_ptr=None, any_hit=False, use_bvh=True,
                      rebuild_bvh=True, t_ptr=None, inst_ptr=None, tri_ptr=None, uv_ptr=None, normal_ptr=None,
-                     hit_ptr=None, rays_out_ptr=None, stats=False):
+                     hit_ptr=None, rays_out_ptr=None, stats=False, reorder=False):
         """rt_query on caller-owned DEVICE buffers (e.g. torch tensors' data_ptr()): float32
-        origins / dirs / tmax, int32 pixels and ids, uint8 hit.  Returns when the results are written."""
+        origins / dirs / tmax, int32 pixels and ids, uint8 hit.  Returns when the results are written.
+        reorder: as query's."""
         o = QueryOpts()
         lib().rt_query_opts_default(ctypes.byref(o))
         o.n, o.origin, o.dir, o.pixel, o.tmax = int(n), origin_ptr, dir_ptr, pixel_ptr, tmax_ptr
         o.use_bvh, o.rebuild_bvh, o.any_hit, o.host = int(use_bvh), int(rebuild_bvh), int(any_hit), 0
         o.t, o.inst, o.tri, o.uv, o.normal, o.hit, o.rays_out = t_ptr, inst_ptr, tri_ptr, uv_ptr, normal_ptr, hit_ptr, rays_out_ptr
         st = Stats()
-        _check(lib().rt_query(self._h, ctypes.byref(o), ctypes.byref(st) if stats else None))
+        self._query(o, st if stats else None, reorder)
         return st.as_dict() if stats else None
 
     def pick(self, x, y):
@@ -589,7 +634,7 @@ def kat_device(op, *inputs):
              "ray_ctor": (6, 0, 0), "zorder": (0, 0, 1), "to_mat3": (9, 0, 0), "box_hit": (0, 1, 0), "pow": (1, 0, 0),
              "tri_hit_f": (3, 1, 0), "box_hit_f": (0, 1, 0), "box_pair": (0, 2, 0),
              "rcp_cr": (1, 0, 0), "sqrt_cr": (1, 0, 0), "box_from_local": (6, 1, 0), "box_merge": (6, 1, 0),
-             "entity": (12, 0, 0)}
+             "entity": (12, 0, 0), "ray_key": (0, 0, 1)}
     nf, ni, nu = sizes[op]
     ins = [_f(a) for a in inputs] + [None] * (3 - len(inputs))
     n = inputs[0].shape[0]

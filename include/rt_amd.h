@@ -29,7 +29,9 @@ extern "C" {
  * 5: rt_scene_last_trace (test hook: the trace kernel a launch used); rt_frame_work keeps its
  *    frame when rt_render_opts.rgba is set
  *    (still 5: rt_query / rt_query_opts_default were added later; the change is additive, no
- *    existing entry or struct changed, so the version callers compare against stays) */
+ *    existing entry or struct changed, so the version callers compare against stays)
+ *    (still 5: additive -- rt_query_set_order / rt_query_last and the RT_QUERY_ORDER_* modes;
+ *    rt_query_opts keeps its layout, the switch is scene state) */
 #define RT_ABI_VERSION 5
 
 enum {
@@ -228,6 +230,32 @@ void rt_query_opts_default(rt_query_opts* o);
  * RT_ERR_NODEV: no usable device. */
 int rt_query(rt_scene* s, const rt_query_opts* opts, rt_stats* stats);
 
+/* The order rt_query traces a batch in.  RT_QUERY_ORDER_CALLER (default): 64 consecutive rays
+ * to a wave, as given.  RT_QUERY_ORDER_SORTED: for batches whose order is not a frame's
+ * (occlusion rays from hit points, bounce rays, picks from many views) -- on the scene's stream
+ * the call forms a 64-bit key per ray (origin cell in the scene's box, then direction; rejected
+ * rays last), sorts (key, ray index) on the device (stable) and traces wave c's lane l as ray
+ * order[64 c + l].  Every output is written at the ray's own index: the caller sees the arrays of
+ * RT_QUERY_ORDER_CALLER, bit for bit.  A counted query (stats non-NULL) and a batch of n <= 64
+ * rays run in caller order whatever the mode.  Ray indices are 32-bit: rt_query with n > 2^31 - 1
+ * in sorted mode returns RT_ERR_LIMIT (checked with the arguments, before any device work).  The
+ * sort's scratch (12 bytes a ray, double-buffered, plus the sort's temporary storage) belongs to
+ * the scene, grows on demand and is freed with it; if it cannot be allocated the call returns
+ * RT_ERR_HIP and the scene stays usable.  Sorting pays for itself on incoherent batches only: a
+ * batch already in pixel order loses the sort's time.  Host-side state, no device needed; it
+ * reaches nothing but rt_query.  RT_ERR_ARG: any other mode. */
+enum { RT_QUERY_ORDER_CALLER = 0, RT_QUERY_ORDER_SORTED = 1 };
+int rt_query_set_order(rt_scene* s, int mode);
+
+/* The scene's most recent rt_query that reached its launch (test hook, as rt_scene_last_trace).
+ * out8 = {TREE, LDS, ANY, STATS of the query kernel used, ordered kernel 0/1, persistent form
+ * 0/1, blocks, batch was sorted 0/1}; bounds6 = the box (min3, max3) the keys were quantised in
+ * (the instances' world boxes merged; zeros if the batch was not sorted); `order`, if non-NULL, is
+ * a host array of order_cap entries that receives the last sorted batch's order, n entries
+ * (copied from the device; nothing is written if the batch was not sorted).  Each may be NULL.
+ * RT_ERR_STATE before the first rt_query; RT_ERR_ARG if order_cap < n. */
+int rt_query_last(const rt_scene* s, int32_t out8[8], float bounds6[6], uint32_t* order, int64_t order_cap);
+
 /* Frame slots (1 = default, up to 8).  The reference rebuilds its BVH inside every
  * update_scene call (raytracer.cu:103-119), so a frame owns per-frame state: BVH, work
  * counters and scheduling history.  With n slots, consecutive rt_render calls rotate
@@ -303,7 +331,9 @@ int rt_debug_cast(rt_scene* s, int x, int y, char* buf, int64_t cap);
  * the GPU.  op names as in oracle/rt_oracle.h's orc_kat_*, plus the filtered variants
  * tri_hit_f, box_hit_f and box_pair (two boxes per element, two int results), and
  * box_from_local / box_merge (box7 = min3 max3 nondegenerate; entity7 = quat4 pos3 -> box6 +
- * int) and entity (entity7, v3 -> point/vec to/from local, 12 floats). 
+ * int) and entity (entity7, v3 -> point/vec to/from local, 12 floats), and ray_key (in0 = n*6
+ * rays as traced: origin, unit direction; in1 = n*6 boxes: min3, max3; out_u = the coherence
+ * keys of RT_QUERY_ORDER_SORTED).
  * Host pointers in/out. */
 int rt_kat_device(const char* op, int n, const float* in0, const float* in1, const float* in2,
                   float* out_f, int32_t* out_i, uint64_t* out_u);

@@ -3,7 +3,10 @@ by default, with device buffers, median of `calls` synchronous calls after warm-
   a  the frame's rays in pixel order (origin / dir mode; also the pixel mode itself)
   b  the same rays under a fixed permutation (incoherent packets)
   c  occlusion (any_hit): from every primary hit point towards the point light, tmax = its distance
-each with the BVH kept (rebuild_bvh = 0: the query alone) and rebuilt per call (the default).  Then
+  d  ambient-occlusion fans (any_hit): 4 seeded directions in the normal's hemisphere per hit point, tmax = 2
+each with the BVH kept (rebuild_bvh = 0: the query alone) and rebuilt per call (the default), and each
+in caller order and sorted (RT_QUERY_ORDER_SORTED, reorder=True), the two modes alternated call by call
+in one run, plus the sorted call stopped after its sort (key kernel + radix sort alone).  Then
 the latency of Scene.pick, the small / persistent crossover (both forms forced through
 RT_QUERY_FORM over a ladder of batch sizes: the frame's last m rays in pixel order, then m
 permuted rays; BVH kept) and, as context, the trace
@@ -72,25 +75,88 @@ torch.cuda.synchronize()
 
 
 def closest(o_t, d_t, m, rebuild):
-    return lambda: s.query_device(m, origin_ptr=o_t.data_ptr(), dir_ptr=d_t.data_ptr(), t_ptr=t_d.data_ptr(),
-                                  inst_ptr=inst_d.data_ptr(), tri_ptr=tri_d.data_ptr(), rebuild_bvh=rebuild)
+    return lambda **kw: s.query_device(m, origin_ptr=o_t.data_ptr(), dir_ptr=d_t.data_ptr(), t_ptr=t_d.data_ptr(),
+                                       inst_ptr=inst_d.data_ptr(), tri_ptr=tri_d.data_ptr(), rebuild_bvh=rebuild, **kw)
+
+
+# d: ambient-occlusion fans -- from every primary hit point (lifted 1e-3 along the hit normal, off
+# its own triangle) FAN directions in the hemisphere of the normal, from a seeded generator;
+# any_hit with tmax = 2 units; a hit point's FAN rays are consecutive, as a caller generates them
+FAN, FAN_SEED, FAN_TMAX = 4, 20240608, 2.0
+n_d = 0
+if n_c:
+    nrm_d = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    s.query_device(n, origin_ptr=o_a.data_ptr(), dir_ptr=d_a.data_ptr(), t_ptr=t_d.data_ptr(), inst_ptr=inst_d.data_ptr(),
+                   normal_ptr=nrm_d.data_ptr())
+    nh = nrm_d[hitm]
+    ph = ((o_a + t_d[:, None] * d_a)[hitm] + 1e-3 * nh)
+    g = torch.Generator(device="cpu")
+    g.manual_seed(FAN_SEED)
+    v = torch.randn((n_c, FAN, 3), generator=g, dtype=torch.float32).to(dev)
+    v = v / torch.linalg.norm(v, dim=2, keepdim=True)
+    v = torch.where(((v * nh[:, None, :]).sum(dim=2, keepdim=True) < 0), -v, v)
+    o_d = ph[:, None, :].expand(n_c, FAN, 3).reshape(-1, 3).contiguous()
+    d_d = v.reshape(-1, 3).contiguous()
+    n_d = n_c * FAN
+    tmax_d = torch.full((n_d,), FAN_TMAX, dtype=torch.float32, device=dev)
+    hit_dd = torch.empty(n_d, dtype=torch.uint8, device=dev)
+    del v, nh, ph, nrm_d
+torch.cuda.synchronize()
+
+caller_only = bool(os.environ.get("QUERY_BENCH_CALLER_ONLY"))        # (a library without rt_query_set_order: A/B runs)
+
+
+def paired_ms(fn, reps=calls, warm=3):
+    """Median ms of fn() in caller order and of fn(reorder=True), the two alternated call by call in
+    one run; then of the sorted call stopped after its sort (RT_QUERY_SORT_ONLY: key kernel + radix
+    sort + the call's host path, no trace)."""
+    if caller_only:
+        return median_ms(fn, reps, warm), None, None
+    ts = {False: [], True: []}
+    for k in range(warm + reps):
+        for reorder in (False, True):
+            t = time.perf_counter()
+            fn(reorder=reorder)
+            if k >= warm:
+                ts[reorder].append(time.perf_counter() - t)
+    med = {r: sorted(v)[len(v) // 2] * 1e3 for r, v in ts.items()}
+    os.environ["RT_QUERY_SORT_ONLY"] = "1"
+    try:
+        sort_only = median_ms(lambda: fn(reorder=True), reps, warm)
+    finally:
+        del os.environ["RT_QUERY_SORT_ONLY"]
+    return med[False], med[True], sort_only
+
+
+def report(case, rays, fn, rebuild, **extra):
+    a, b, k = paired_ms(fn)
+    row = dict(case=case, rays=rays, median_ms=round(a, 4), mrays_per_s=round(rays / a / 1e3, 1))
+    if b is not None:
+        row.update(sorted_median_ms=round(b, 4), sorted_mrays_per_s=round(rays / b / 1e3, 1), key_sort_only_ms=round(k, 4),
+                   sorted_over_caller=round(b / a, 3))
+    out(**row, rebuild_bvh=int(rebuild), calls=calls, **extra)
 
 
 for rebuild in (False, True):
-    tag = dict(rebuild_bvh=int(rebuild), calls=calls)
-    ms = median_ms(lambda: s.query_device(n, pixel_ptr=pix.data_ptr(), t_ptr=t_d.data_ptr(), inst_ptr=inst_d.data_ptr(),
-                                          tri_ptr=tri_d.data_ptr(), rebuild_bvh=rebuild))
-    out(case="a_pixel_mode", rays=n, median_ms=round(ms, 4), mrays_per_s=round(n / ms / 1e3, 1), **tag)
-    ms = median_ms(closest(o_a, d_a, n, rebuild))
-    out(case="a_pixel_order", rays=n, median_ms=round(ms, 4), mrays_per_s=round(n / ms / 1e3, 1), **tag)
-    ms = median_ms(closest(o_b, d_b, n, rebuild))
-    out(case="b_permuted", rays=n, median_ms=round(ms, 4), mrays_per_s=round(n / ms / 1e3, 1), **tag)
+    report("a_pixel_mode", n, lambda **kw: s.query_device(n, pixel_ptr=pix.data_ptr(), t_ptr=t_d.data_ptr(), inst_ptr=inst_d.data_ptr(),
+                                                          tri_ptr=tri_d.data_ptr(), rebuild_bvh=rebuild, **kw), rebuild)
+    report("a_pixel_order", n, closest(o_a, d_a, n, rebuild), rebuild)
+    report("b_permuted", n, closest(o_b, d_b, n, rebuild), rebuild)
     if len(point) and n_c:
-        ms = median_ms(lambda: s.query_device(n_c, origin_ptr=p.data_ptr(), dir_ptr=d_c.data_ptr(), tmax_ptr=tmax_c.data_ptr(),
-                                              any_hit=True, hit_ptr=hit_d.data_ptr(), rebuild_bvh=rebuild))
+        report("c_any_hit_to_light", n_c,
+               lambda **kw: s.query_device(n_c, origin_ptr=p.data_ptr(), dir_ptr=d_c.data_ptr(), tmax_ptr=tmax_c.data_ptr(),
+                                           any_hit=True, hit_ptr=hit_d.data_ptr(), rebuild_bvh=rebuild, **kw), rebuild)
         torch.cuda.synchronize()
-        out(case="c_any_hit_to_light", rays=n_c, median_ms=round(ms, 4), mrays_per_s=round(n_c / ms / 1e3, 1),
-            occluded=round(float(hit_d[:n_c].float().mean()), 4), **tag)
+        out(case="c_occluded", occluded=round(float(hit_d[:n_c].float().mean()), 4))
+    if n_d:
+        report("d_ao_fans", n_d,
+               lambda **kw: s.query_device(n_d, origin_ptr=o_d.data_ptr(), dir_ptr=d_d.data_ptr(), tmax_ptr=tmax_d.data_ptr(),
+                                           any_hit=True, hit_ptr=hit_dd.data_ptr(), rebuild_bvh=rebuild, **kw), rebuild,
+               fan=FAN, tmax=FAN_TMAX)
+        torch.cuda.synchronize()
+        out(case="d_occluded", occluded=round(float(hit_dd.float().mean()), 4))
+if os.environ.get("QUERY_BENCH_CASES_ONLY"):                          # (the RAYKEY_ORIGIN_BITS ladder: cases a-d alone)
+    sys.exit(0)
 
 # pick: one ray through the host path (pinned staging, one copy each way)
 for rebuild in (False, True):
