@@ -55,6 +55,23 @@ __host__ __device__ inline size_t bvh_lds_bytes(int n, bool lds_tree) {
     return 12 * (size_t)n + (lds_tree ? 28 * (size_t)(2 * n - 1) : 0);
 }
 
+// The sort of bvh_build_kernel<true> with `threads` threads: the chunked rank sort when whole
+// waves cover the instances (one entry per thread) and the padded count fills a wave, the
+// bitonic network otherwise.  bvh_build_kernel<false> always takes the bitonic network.
+__host__ __device__ inline bool bvh_rank_sort(int n, int n_inst, int threads) {
+    return n >= 64 && 64 * ((n_inst + 63) >> 6) <= threads;
+}
+// Which build runs for n padded leaves (RT_EXPORT_BVH_INFO's `form`): the conditions build_bvh
+// and bvh_build_kernel branch on.
+enum { BVH_FORM_NONE = 0, BVH_FORM_LDS_RANK = 1, BVH_FORM_LDS_BITONIC = 2, BVH_FORM_HBM = 3, BVH_FORM_GRID = 4 };
+constexpr int BVH_WG_THREADS = 1024;             // bvh_build_kernel's workgroup
+constexpr size_t BVH_LDS_MAX = 160 * 1024;       // LDS of one CU
+inline int bvh_form(int n, int n_inst, int wg_leaves) {
+    if (n > wg_leaves) return BVH_FORM_GRID;
+    if (bvh_lds_bytes(n, true) > BVH_LDS_MAX) return BVH_FORM_HBM;
+    return bvh_rank_sort(n, n_inst, BVH_WG_THREADS) ? BVH_FORM_LDS_RANK : BVH_FORM_LDS_BITONIC;
+}
+
 // Karras radix-tree node i over sorted 64-bit keys k[0, nr): range [first, last] and
 // split gamma (left = [first, gamma], right = [gamma+1, last]); equal keys are told
 // apart by their index (delta = 64 + clz(i ^ j)).

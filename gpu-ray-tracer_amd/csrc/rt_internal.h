@@ -173,6 +173,9 @@ struct rt_scene {
     rtd::TraceKey last_key{};
     int last_ftree = 0;
     bool has_last_trace = false;
+    // the most recent BVH build (RT_EXPORT_BVH_*): its frame slot (-1: none yet), the ordered
+    // tree's shape it was launched with and which build ran (rtb::bvh_form); host state only
+    struct Built { int slot = -1, n_real = 0, fdepth = 0, form = 0; } built;
     rti::FrameSlot& cur() { return slots[cur_slot]; }
     const rti::FrameSlot& cur() const { return slots[cur_slot]; }
     ~rt_scene();

@@ -2149,7 +2149,7 @@ __global__ __launch_bounds__(1024) void bvh_build_kernel(BvhArgs A) {
     const int m = A.n_inst, nch = (m + 63) >> 6;
     bool sorted = false;
     if constexpr (LDS_TREE) {
-        if (n >= 64 && nch * 64 <= nt) {
+        if (bvh_rank_sort(n, m, nt)) {
             // Chunked rank sort: wave w sorts entries [64w, 64w + 64) in registers (bitonic
             // network over lanes), then each entry's rank = its lane + its rank in every other
             // sorted chunk (branchless binary search in LDS).  Earlier chunks hold smaller
@@ -2528,7 +2528,7 @@ hipError_t launch_bvh_build(BvhArgs& A, bool lds_tree, size_t lds, hipStream_t s
     const void* fn = lds_tree ? (const void*)bvh_build_kernel<true> : (const void*)bvh_build_kernel<false>;
     if (lds > 64 * 1024) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     void* args[] = {&A};
-    return hipExtLaunchKernel(fn, dim3(1), dim3(1024), args, lds, st, e0, e1, 0);
+    return hipExtLaunchKernel(fn, dim3(1), dim3(BVH_WG_THREADS), args, lds, st, e0, e1, 0);
 }
 
 void launch_unpermute(const uint32_t* g, uint32_t* out, int W, int H, int N, int rows_max, hipStream_t st) {

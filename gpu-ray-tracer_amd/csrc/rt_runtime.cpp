@@ -498,18 +498,21 @@ int build_bvh(rt_scene* s, hipStream_t st, hipEvent_t e0 = nullptr, hipEvent_t e
     // the slot the next fast frame records its heavy list into (launch_trace skips its memset)
     A.hctl = f.d_hctl ? f.d_hctl + 2 * (1 - f.hist_parity) : nullptr;
     f.hctl_zeroed = f.d_hctl ? 1 - f.hist_parity : -1;
-    if (A.n > BVH_WG_LEAVES) {                                // above one workgroup's LDS: the grid-wide build
+    const int form = bvh_form(A.n, A.n_inst, BVH_WG_LEAVES);
+    if (form == BVH_FORM_GRID) {                              // above one workgroup's LDS: the grid-wide build
         if (!f.d_bscratch) HIPCHK(hipMalloc(&f.d_bscratch, bvh_large_scratch_bytes(A.n)));
         HIPCHK(bvh_build_large(A, f.d_bscratch, st, e0, e1));
     } else {
-        const bool lds_tree = bvh_lds_bytes(A.n, true) <= 160 * 1024;       // n <= 2048
+        const bool lds_tree = form != BVH_FORM_HBM;                         // n <= 2048
         const size_t lds = bvh_lds_bytes(A.n, lds_tree);
-        if (lds > 160 * 1024) return fail(RT_ERR_LIMIT, "BVH build needs more LDS than one CU has");
+        if (lds > BVH_LDS_MAX) return fail(RT_ERR_LIMIT, "BVH build needs more LDS than one CU has");
         HIPCHK(launch_bvh_build(A, lds_tree, lds, st, e0, e1));
         HIPCHK(hipGetLastError());
     }
     f.bvh_valid = true;
     f.work_zeroed = true;
+    // what RT_EXPORT_BVH_* reads back (host state): the slot, and the shape this build was given
+    s->built = {s->cur_slot, s->n_real, s->fdepth, form};
     return RT_OK;
 }
 
@@ -940,8 +943,35 @@ static bool meshes_cover_tris_once(const rt::Scene& h) {
     return n == h.tris.size();
 }
 
+// RT_EXPORT_BVH_* (test hook): the arrays the most recent BVH build wrote into its frame slot,
+// copied to the host once that slot's work is done.  Copies only: no launch, no state change.
+static int export_built_bvh(const rt_scene* s, int what, void* dst, int64_t cap) {
+    const rt_scene::Built& b = s->built;
+    if (!s->uploaded || b.slot < 0) return fail(RT_ERR_STATE, "no BVH built yet (render a frame first)");
+    const FrameSlot& f = s->slots[b.slot];
+    const size_t n = (size_t)s->n_leaf;
+    const int32_t info[8] = {s->n_leaf, (int32_t)s->h.d_insts.size(), b.n_real, b.fdepth,
+                             ordered_tree_usable(b.n_real, b.fdepth) ? 1 : 0, b.form, b.slot, 0};
+    const void* src = nullptr;
+    size_t bytes = 0;
+    switch (what) {
+        case RT_EXPORT_BVH_INFO: bytes = sizeof info; break;
+        case RT_EXPORT_BVH_PAIRS: src = f.d_node_pair; bytes = 12 * n * sizeof(float); break;
+        case RT_EXPORT_BVH_LEAF_INST: src = f.d_leaf; bytes = n * sizeof(int32_t); break;
+        default: src = f.d_fnode; bytes = 16 * (size_t)std::max(b.n_real - 1, 0) * sizeof(float); break;
+    }
+    if ((bytes && !dst) || cap < (int64_t)bytes) return fail(RT_ERR_ARG, "destination too small");
+    if (what == RT_EXPORT_BVH_INFO) { memcpy(dst, info, sizeof info); return RT_OK; }
+    if (!bytes) return RT_OK;
+    HIPCHK(hipSetDevice(s->device));
+    if (f.pending) HIPCHK(hipEventSynchronize(f.done));
+    HIPCHK(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
 int rt_scene_export(const rt_scene* s, int what, void* dst, int64_t cap) {
     CHECK_FINISHED(s);
+    if (what >= RT_EXPORT_BVH_INFO && what <= RT_EXPORT_BVH_FNODE) return export_built_bvh(s, what, dst, cap);
     const rt::Scene& h = s->h;
     if ((what == RT_EXPORT_TRIS || what == RT_EXPORT_TEXCOORDS) && !meshes_cover_tris_once(h))
         return fail(RT_ERR_STATE, "meshes do not cover every triangle once");

@@ -26,6 +26,9 @@ LIB_PATH = os.environ.get("RTAMD_LIB", os.path.join(PKG, "librt_amd.so"))
 RT_OK, RT_ERR_ARG, RT_ERR_IO, RT_ERR_PARSE, RT_ERR_HIP, RT_ERR_STATE, RT_ERR_NODEV, RT_ERR_LIMIT = 0, -1, -2, -3, -4, -5, -6, -7
 EXPORTS = {"vertices": 0, "normals": 1, "tris": 2, "materials": 3, "instances": 4, "inst_mesh": 5,
            "lights": 6, "camera": 7, "env": 8, "texcoords": 9}
+# RT_EXPORT_BVH_* (test hook): the tree the most recent frame's BVH build left on the device
+BVH_EXPORTS = {"bvh_info": 11, "bvh_pairs": 12, "bvh_leaf_inst": 13, "bvh_fnode": 14}
+BVH_INFO_KEYS = ("n_leaf", "n_inst", "n_real", "fdepth", "ftree", "form", "slot")
 
 # Every symbol include/rt_amd.h declares (checked by tests/test_abi.py).
 SYMBOLS = [
@@ -382,6 +385,21 @@ class Scene:
         return self.info()["H"]
 
     def export(self, what):
+        """Host copies of the scene arrays.  "bvh_info" (a dict of BVH_INFO_KEYS), "bvh_pairs"
+        ([n_leaf, 12] float32), "bvh_leaf_inst" ([n_leaf] int32) and "bvh_fnode" ([n_real - 1, 16]
+        float32; words 12..15 are int32 refs) read the tree the most recent frame's BVH build left
+        on the device (RT_EXPORT_BVH_*, a test hook); RT_ERR_STATE before any build."""
+        if what in BVH_EXPORTS:
+            v = np.zeros(8, np.int32)
+            _check(lib().rt_scene_export(self._h, BVH_EXPORTS["bvh_info"], _ptr(v), v.nbytes))
+            b = dict(zip(BVH_INFO_KEYS, (int(x) for x in v)))
+            if what == "bvh_info":
+                return b
+            shp, dt = {"bvh_pairs": ((b["n_leaf"], 12), np.float32), "bvh_leaf_inst": ((b["n_leaf"],), np.int32),
+                       "bvh_fnode": ((max(b["n_real"] - 1, 0), 16), np.float32)}[what]
+            a = np.zeros(shp, dt)
+            _check(lib().rt_scene_export(self._h, BVH_EXPORTS[what], _ptr(a), a.nbytes))
+            return a
         i = self.info()
         shapes = {"vertices": ((i["n_vertices"], 3), np.float32), "normals": ((i["n_vertices"], 3), np.float32),
                   "tris": ((i["n_tris"], 4), np.int32), "materials": ((i["n_mats"], 26), np.float32),

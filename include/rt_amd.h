@@ -31,7 +31,8 @@ extern "C" {
  *    (still 5: rt_query / rt_query_opts_default were added later; the change is additive, no
  *    existing entry or struct changed, so the version callers compare against stays)
  *    (still 5: additive -- rt_query_set_order / rt_query_last and the RT_QUERY_ORDER_* modes;
- *    rt_query_opts keeps its layout, the switch is scene state) */
+ *    rt_query_opts keeps its layout, the switch is scene state)
+ *    (still 5: additive -- the RT_EXPORT_BVH_* values of rt_scene_export, a test hook) */
 #define RT_ABI_VERSION 5
 
 enum {
@@ -108,7 +109,23 @@ int rt_scene_info(const rt_scene* s, int32_t info10[10]);
 enum { RT_EXPORT_VERTICES = 0, RT_EXPORT_NORMALS = 1, RT_EXPORT_TRIS = 2, RT_EXPORT_MATERIALS = 3,
        RT_EXPORT_INSTANCES = 4, RT_EXPORT_INST_MESH = 5, RT_EXPORT_LIGHTS = 6, RT_EXPORT_CAMERA = 7, RT_EXPORT_ENV = 8,
        RT_EXPORT_TEXCOORDS = 9,   /* per triangle float7 {has, tx, ty, ux, uy, vx, vy} */
-       RT_EXPORT_ATLAS = 10 };    /* atlas RGBA8 bytes, width*height*4 (rt_scene_atlas_info) */
+       RT_EXPORT_ATLAS = 10,      /* atlas RGBA8 bytes, width*height*4 (rt_scene_atlas_info) */
+       /* Test hook (still ABI 5: additive values of `what`): the tree the most recent frame's BVH
+        * build (rt_render, rt_update_scene, rt_frame_work) left in its frame slot, copied from the
+        * device after that slot's work is done.  No kernel is launched and no frame state changes.
+        * RT_ERR_STATE before any build (and so without a device).
+        * INFO: int32[8] = {n_leaf, n_inst, n_real, fdepth, ftree, form, slot, 0}; n_leaf: padded
+        *   leaf count; n_real: instances with a non-degenerate box; fdepth / ftree: depth of the
+        *   ordered tree and whether the fast kernels are given it; form: the build that ran --
+        *   1: one workgroup, tree in LDS, chunked rank sort; 2: one workgroup, tree in LDS, bitonic
+        *   sort; 3: one workgroup, tree in HBM; 4: grid-wide (0 never appears: no build yet fails).
+        * PAIRS: float[12 n_leaf], child-pair boxes in heap order: node k's component c of
+        *   (mn.xyz, mx.xyz) at [12 (k >> 1) + (k & 1) + 2 c]; degenerate: mn = +inf, mx = -inf.
+        * LEAF_INST: int32[n_leaf], instance of heap leaf n_leaf + i.
+        * FNODE: max(n_real - 1, 0) records of 16 words, the ordered radix tree: 12 floats (child
+        *   A / child B boxes, interleaved as PAIRS) and int32 {A, B, 0, 0} (>= 0: node, < 0:
+        *   -1 - instance). */
+       RT_EXPORT_BVH_INFO = 11, RT_EXPORT_BVH_PAIRS = 12, RT_EXPORT_BVH_LEAF_INST = 13, RT_EXPORT_BVH_FNODE = 14 };
 int rt_scene_export(const rt_scene* s, int what, void* dst, int64_t dst_bytes);
 
 /* ---- camera / environment (entity.h:49-74, environment.h:30-44) ---- */

@@ -2,9 +2,10 @@
 1024): per-64-entry chunk sort, then rank = lane + the entry's rank in every other sorted
 chunk by a 6-step branchless binary search (<= against earlier chunks, < against later
 ones).  It must give thrust's stable sort_by_key order (bvh.cu:86), i.e. (key, index)
-order, with ties and ~0 (degenerate-box) keys.  The device kernel itself is checked by
-the GPU parity tests (hit ids and BVH counters equal the oracle's); their scenes have no
-tied Morton keys, hence this model test of the tie rules."""
+order, with ties and ~0 (degenerate-box) keys.  The device sort's ties are checked on the
+device too: tests/test_gpu_bvh_build.py reads the built tree back and compares it with the
+oracle's for scenes with tied and degenerate keys at every size where the sort changes.  This
+model states the tie rules of the rank sort on their own, over random key sets."""
 import random
 
 ONES = 2 ** 64 - 1
