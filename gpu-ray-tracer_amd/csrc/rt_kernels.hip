@@ -309,15 +309,31 @@ __device__ __forceinline__ Pose inst_pose(const SceneView& S, const BvhRefs& bv,
 // `inv` (axis-plane triangles, axis_plane_t): fl(1/mrd_a), NaN where |mrd_a| < 1e-5.
 struct DirPre { V3 mrd, inv; float scale, dir_len; };
 __device__ __forceinline__ float axis_inv(float d) { return fabsf(d) < THRESH ? __builtin_nanf("") : rcp_cr(d); }
+// keep_arm: passes an arm's operand through an empty asm statement, so that the arm stays an arm.
+// Both arms of a vote are plain arithmetic, which the compiler otherwise hoists out of the branch
+// (and out of the traversal loop) and runs one after the other with selects on the vote -- the
+// generic chain on every query again.
+__device__ __forceinline__ V3 keep_arm(V3 v) { asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z)); return v; }
+// A traced direction is unit to a few ulps and every stage maps unit to unit, so the four
+// length / reciprocal pairs take their closed forms (rt_math.h, unit_len_rcp: the same bits).
+// One wave vote on the chain's head (unit_head): when a lane with a query (`active`) fails it,
+// the whole wave runs the generic chain.
 template <bool AXIS = false>
-__device__ __forceinline__ DirPre dir_pre(V3 d) {
+__device__ __forceinline__ DirPre dir_pre(V3 d, bool active) {
     DirPre p;
-    const V3 ld = qrot_identity(d);                          // Entity::vec_to_local, identity pose
-    p.dir_len = len(ld);
-    const V3 lrd = normalized(ld);                           // Ray ctor (geometry.h:216)
-    const V3 md = qrot_identity(lrd);                        // HitHandle::get_local_ray, identity mesh pose
-    p.scale = len(md);
-    p.mrd = normalized(md);
+    if (!__ballot(active && !unit_head(dot(d, d)))) {
+        d = keep_arm(d);
+        const V3 lrd = normalized_unit(qrot_identity_unit(d), p.dir_len);
+        p.mrd = normalized_unit(qrot_identity_unit(lrd), p.scale);
+    } else {
+        d = keep_arm(d);
+        const V3 ld = qrot_identity(d);                      // Entity::vec_to_local, identity pose
+        p.dir_len = len(ld);
+        const V3 lrd = normalized(ld);                       // Ray ctor (geometry.h:216)
+        const V3 md = qrot_identity(lrd);                    // HitHandle::get_local_ray, identity mesh pose
+        p.scale = len(md);
+        p.mrd = normalized(md);
+    }
     if (AXIS) p.inv = v3(axis_inv(p.mrd.x), axis_inv(p.mrd.y), axis_inv(p.mrd.z));
     return p;
 }
@@ -426,7 +442,17 @@ __device__ __forceinline__ V3 hit_normal(const SceneView& S, const BvhRefs& bv, 
     const DTri& T = bv.tris[b.tri];
     mat = T.mat;
     float b0 = 1.0f - b.u - b.v;
-    V3 n = normalized((b0 * T.n0 + b.u * T.n1) + b.v * T.n2);
+    V3 ni = (b0 * T.n0 + b.u * T.n1) + b.v * T.n2;
+    // Equal unit vertex normals (every cube face) under identity poses: four unit-length stages
+    // (unit_len_rcp).  One vote of the lanes that hit, on the chain's head: an interpolated normal
+    // off unit length, or a general pose, sends the wave to the generic chain.
+    if (!__ballot(!(mp.identity && ip.identity && unit_head(dot(ni, ni))))) {
+        float l;
+        const V3 un = normalized_unit(qrot_identity_unit(normalized_unit(ni, l)), l);
+        return qrot_identity_unit(un);
+    }
+    ni = keep_arm(ni);
+    V3 n = normalized(ni);
     n = normalized(vec_from_local(mp, n));
     return vec_from_local(ip, n);
 }
@@ -524,8 +550,8 @@ __device__ __forceinline__ bool closest_hit(const SceneView& S, const BvhRefs& b
         // triangles take the axis-plane path (AXIS: identity rotations) with no entry bound;
         // a lane that found an occluding hit (occl_t, all-opaque scenes) stops.
         DirPre pre{};
-        if (AXIS) pre = dir_pre<true>(r.d);
-        else if (S.ident_all) pre = dir_pre(r.d);
+        if (AXIS) pre = dir_pre<true>(r.d, active);
+        else if (S.ident_all) pre = dir_pre(r.d, active);
         bool live = active;
         for (int i = 0; i < S.n_inst; i++) {
             if (!__ballot(live)) break;
@@ -538,7 +564,7 @@ __device__ __forceinline__ bool closest_hit(const SceneView& S, const BvhRefs& b
     }
     if (!FT && (!S.use_bvh || S.n_leaf == 0)) {               // brute force (scene.cu:48-52)
         DirPre pre{};
-        if (S.ident_all) pre = dir_pre(r.d);
+        if (S.ident_all) pre = dir_pre(r.d, active);
         for (int i = 0; i < S.n_inst; i++) {
             if (STATS) {
                 wc.leaves += __popcll(am);
@@ -619,8 +645,8 @@ __device__ __forceinline__ bool closest_hit(const SceneView& S, const BvhRefs& b
                     const bool lh = lt <= ct;                  // (ct only decreases: fresh for the second leaf)
                     if (__ballot(lh)) {
                         if (!pre_ok) {
-                            if (AXIS) pre = dir_pre<true>(r.d);    // S.tri_ax set: identity rotations
-                            else if (S.ident_all) pre = dir_pre(r.d);
+                            if (AXIS) pre = dir_pre<true>(r.d, active_in);    // S.tri_ax set: identity rotations
+                            else if (S.ident_all) pre = dir_pre(r.d, active_in);
                             pre_ok = true;
                         }
                         const unsigned long long cl0 = PROF ? __builtin_amdgcn_s_memtime() : 0;
@@ -651,7 +677,7 @@ __device__ __forceinline__ bool closest_hit(const SceneView& S, const BvhRefs& b
     const unsigned long long br = __ballot(hr);
     if (!br) return false;
     DirPre pre{};
-    if (S.ident_all) pre = dir_pre(r.d);
+    if (S.ident_all) pre = dir_pre(r.d, active);
     // lower bound of acceptable local times in a leaf entered at >= tl (see distance pruning)
     const bool box_bound = !STATS && S.prune_abs >= 0.0f;   // counted kernel: plain reference path
     auto t_low = [&](float tl) { return box_bound ? tl - slack(tl) : -INFINITY; };
@@ -1014,7 +1040,14 @@ __device__ __forceinline__ V4 trace_sample(const SceneView& S, const BvhRefs& bv
                     cur.type = F_NORMAL;                           // the child: last_mat, in_obj inherited
                     cur.atten = cur.atten * m.Kr;
                     cur.depth = cur.depth - 1;
-                    cur.ray = make_ray(hp, reflect(cur.ray.d, NN ? is_nn : normalized(is_norm)));
+                    // (reflect of unit vectors is unit: the Ray ctor's normalisation by unit_len_rcp,
+                    // on one vote of the reflecting lanes)
+                    const V3 rd = reflect(cur.ray.d, NN ? is_nn : normalized(is_norm));
+                    float rl;
+                    V3 rn;
+                    if (!__ballot(!unit_head(dot(rd, rd)))) rn = normalized_unit(rd, rl);
+                    else rn = normalized(keep_arm(rd));
+                    cur.ray = Ray{hp, rn};
                 }
             } else if (!OPQ && m.refractive) {                    // F_REFRACT (scene.cu:149-184)
                 dbg(P, me, 3);
@@ -1379,6 +1412,9 @@ __global__ __launch_bounds__(TRACE_BLOCK_P) void trace_kernel(TraceParams P_arg,
         // The scheduling history is read with scalar loads: a vector load here would wait
         // (vmcnt is in order) for the previous group's output stores to be acknowledged.
         auto umod = [&](unsigned n) { return n - udiv(n, kld(P.div_perq)) * (unsigned)per_q; };
+        // (the long modulo below is the rare arm: per_q made opaque there, so that the division's
+        // float reciprocal of it -- a VGPR -- is formed in that arm, not held across the group loop)
+        auto per_q_cold = [&]() { int v = per_q; asm volatile("" : "+s"(v)); return v; };
         auto live_g = [&]() {
             const int n = live_n(qi);
             int i;
@@ -1402,7 +1438,7 @@ __global__ __launch_bounds__(TRACE_BLOCK_P) void trace_kernel(TraceParams P_arg,
         const int g = qi < 0 ? (P.hist == 2 ? heavy_g() : ldc(P.hl_prev, ticket))
                              : P.live ? live_g()
                              : ((q0 + qi) % NQ) + NQ * (P.scramble_small ? (int)umod((unsigned)ticket * (unsigned)P.scramble)
-                                                                         : (int)(((long long)ticket * P.scramble) % per_q));
+                                                                         : (int)(((long long)ticket * P.scramble) % per_q_cold()));
         auto flag = [&](const unsigned char* f) { return (ldc(reinterpret_cast<const uint32_t*>(f), g >> 2) >> (8 * (g & 3))) & 0xffu; };
         if (g >= P.n_groups || (qi < 0 && P.hist == 1 && P.gsky && flag(P.gsky)) ||    // sky group: done by sky_kernel
             (qi >= 0 && P.hist == 1 && flag(P.hf_prev)))
@@ -1437,7 +1473,9 @@ __global__ __launch_bounds__(TRACE_BLOCK_P) void trace_kernel(TraceParams P_arg,
             // outputs are zeros (and -1 hit ids).  Most groups of the reference scenes are sky.
             if (FT && !STATS && !PROF && !MULTI && SV().use_bvh && SV().n_leaf > 0 && !kparams().gsky && !__ballot(ft_root_hit(SV(), bv, act, r0))) {
                 if (act && k == 0) {
-                    const int op = gl.pix;
+                    int gq = g;                                // (the pixel recomputed here: its two store
+                    asm volatile("" : "+s"(gq));               // addresses are not held in VGPRs over the group)
+                    const int op = group_lane(gq).pix;
                     if (P.hit_inst) P.hit_inst[op] = -1;
                     if (P.hit_tri) P.hit_tri[op] = -1;
                 }

@@ -43,6 +43,47 @@ RT_HD float dot(V3 a, V3 b) {                                       // linear.h:
 RT_HD float rcp_cr(float x) { return 1.0f / x; }
 RT_HD float sqrt_cr(float x) { return sqrtf(x); }
 
+// Unit-length fast path.  A squared length s of a (nearly) unit vector lies a few ulps from 1,
+// and there L = sqrt_cr(s) and r = rcp_cr(L) are closed-form in s's bit pattern.  With
+// d = bits(s) - bits(1) (ulps of s above 1: 2^-23 each; below 1: 2^-24 each, d < 0):
+//   sqrt(1 + x) = 1 + x/2 - x^2/8 + ...: bits(L) = bits(1) + floor(d / 2) on both sides (an odd d
+//   is a half-way case of x/2 pushed down by the x^2 term, an even d is x/2 exactly, and
+//   x^2/8 stays far below half an ulp);
+//   1/(1 + y) = 1 - y + y^2 - ...: with e = bits(L) - bits(1), r = 1 - 2e ulps-below-1 for e >= 0
+//   (bits(1) - 2e), and for e < 0 r = 1 + ceil(|e| / 2) ulps-above-1 (bits(1) - floor(e / 2)): an
+//   odd |e| is a half-way case pushed up by the y^2 term.
+// The window is |s - 1| <= 2^-14 (d in [-1024, 512]); tests/unitlen_host.cpp checks every float
+// of it against sqrtf and 1.0f / sqrtf.  Integer arithmetic only: host and device agree.
+RT_HD int32_t unit_ulps(float s) {
+    union { float f; int32_t i; } b{s};
+    return (int32_t)((uint32_t)b.i - 0x3f800000u);
+}
+RT_HD bool unit_window(float s) { return (uint32_t)unit_ulps(s) + 1024u <= 1536u; }
+RT_HD void unit_len_rcp(float s, float& L, float& r) {
+    const int32_t e = unit_ulps(s) >> 1;                              // floor (arithmetic shift)
+    union { int32_t i; float f; } l{0x3f800000 + e}, q{0x3f800000 - (e >= 0 ? 2 * e : e >> 1)};
+    L = l.f; r = q.f;
+}
+// Chain head: |s - 1| <= 2^-16.  A chain of normalisations and identity rotations whose first
+// squared length passes this test keeps every later one inside unit_window: a stage changes the
+// squared length by at most a few ulps (three roundings of the products and one of L r, each
+// 2^-24 relative, twice over for the square), or brings it to 1 within as many, and the head
+// leaves 2^-14 - 2^-16 = 384 ulps of room.  So a chain is guarded once, by one wave vote on its
+// head (tests/unitlen_host.cpp sweeps heads up to both edges through the chains).
+RT_HD bool unit_head(float s) { return (uint32_t)unit_ulps(s) + 256u <= 384u; }
+// normalized(v) and qrot_identity(v) (below) for |v|^2 inside unit_window: L ~ 1 > THRESH, so
+// the zero-length branch is not taken.
+RT_HD V3 normalized_unit(V3 v, float& L) {                           // L = len(v)
+    float r;
+    unit_len_rcp(dot(v, v), L, r);
+    return r * v;
+}
+RT_HD V3 qrot_identity_unit(V3 v) {
+    float L;
+    const V3 nc = normalized_unit(v3(v.x + 0.0f, v.y + 0.0f, v.z + 0.0f), L);
+    return L * nc;
+}
+
 RT_HD float len(V3 v) { return sqrt_cr(dot(v, v)); }
 RT_HD V3 normalized(V3 v) {                                         // linear.h:159-167
     float l = len(v);
