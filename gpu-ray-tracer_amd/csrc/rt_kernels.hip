@@ -314,6 +314,7 @@ __device__ __forceinline__ float axis_inv(float d) { return fabsf(d) < THRESH ? 
 // (and out of the traversal loop) and runs one after the other with selects on the vote -- the
 // generic chain on every query again.
 __device__ __forceinline__ V3 keep_arm(V3 v) { asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z)); return v; }
+__device__ __forceinline__ float keep_arm(float s) { asm volatile("" : "+v"(s)); return s; }
 // A traced direction is unit to a few ulps and every stage maps unit to unit, so the four
 // length / reciprocal pairs take their closed forms (rt_math.h, unit_len_rcp: the same bits).
 // One wave vote on the chain's head (unit_head): when a lane with a query (`active`) fails it,
@@ -338,6 +339,37 @@ __device__ __forceinline__ DirPre dir_pre(V3 d, bool active) {
     return p;
 }
 
+// The shading steps' chains (trace_sample: the hit's unit normal, the light step, the reflection
+// step) in the same manner: one vote per chain of the lanes in that step, on the chain's first
+// squared length(s); a failing lane sends the wave to the generic chain, unchanged.
+// (len, 1 / len) of a vector from its squared length s
+__device__ __forceinline__ void len_rcp_vote(float s, float& l, float& r) {
+    if (!__ballot(!unit_head(s))) {
+        unit_len_rcp(keep_arm(s), l, r);
+    } else {
+        l = sqrt_cr(keep_arm(s));
+        r = rcp_cr(l);
+    }
+}
+// normalized(v)
+__device__ __forceinline__ V3 normalized_vote(V3 v) {
+    const float s = dot(v, v);
+    if (!__ballot(!unit_head(s))) {
+        float l, r;
+        unit_len_rcp(keep_arm(s), l, r);
+        return r * v;
+    }
+    const float l = sqrt_cr(keep_arm(s));
+    if (l > THRESH) return rcp_cr(l) * v;
+    return v3(0.0f, 0.0f, 0.0f);
+}
+// reflect(dir, nrm): both heads vote, the mirrored direction's length follows them (rt_math.h)
+__device__ __forceinline__ V3 reflect_vote(V3 dir, V3 nrm) {
+    if (!__ballot(!(unit_head(dot(dir, dir)) && unit_head(dot(nrm, nrm)))))
+        return reflect_unit(keep_arm(dir), keep_arm(nrm));
+    return reflect(keep_arm(dir), keep_arm(nrm));
+}
+
 // Component `a` of a vector (a wave-uniform axis index: the selects fold into branches).
 __device__ __forceinline__ float comp(V3 v, int a) { return a == 0 ? v.x : a == 1 ? v.y : v.z; }
 
@@ -354,12 +386,16 @@ __device__ __forceinline__ bool cast_local(const SceneView& S, const BvhRefs& bv
     const DMesh mesh = ldc(S.meshes, mesh_id);
     float dir_len, scale;
     Ray mr;
-    if (S.ident_all) {
+    // AXIS kernels run only with identity rotations everywhere (choose_trace_variant checks it), so
+    // the general-pose arm is not compiled into them.  Elsewhere its direction chain is plain
+    // arithmetic on the query's ray, which the compiler would hoist out of the leaf and traversal
+    // loops and run on every query whatever S.ident_all says: keep_arm holds it in its arm.
+    if (AXIS || S.ident_all) {
         dir_len = pre.dir_len; scale = pre.scale;
         mr.o = qrot_identity(qrot_identity(r.o - ip.p) - mesh.pose.p);
         mr.d = pre.mrd;
     } else {
-        V3 ld = vec_to_local(ip, r.d);
+        V3 ld = vec_to_local(ip, keep_arm(r.d));
         dir_len = len(ld);
         Ray lr = make_ray(point_to_local(ip, r.o), ld);
         V3 md = vec_to_local(mesh.pose, lr.d);               // HitHandle::get_local_ray
@@ -749,7 +785,8 @@ __device__ __forceinline__ V4 phong_factor(const DMat& m, V4 kd, V3 nrm, V3 nrm_
                                            float tl_len, V3 tl_neg_unit) {
     float nd = max_std(dot(to_light, nrm), 0.0f);
     V4 diffuse = nd * kd;
-    V3 reflected = reflect_pre(tl_len, tl_neg_unit, nrm_unit);         // reflect(neg(to_light), nrm)
+    // reflect(neg(to_light), nrm) = reflect_pre(tl_len, tl_neg_unit, nrm_unit), its one normalisation voted
+    V3 reflected = tl_len * normalized_vote(reflect_w(tl_neg_unit, nrm_unit));
     float rd = dot(neg(reflected), ray_dir);
     V4 specular = pow_fast(max_std(rd, 0.0f), m.alpha) * m.Ks;
     return diffuse + specular;
@@ -960,95 +997,115 @@ __device__ __forceinline__ V4 trace_sample(const SceneView& S, const BvhRefs& bv
         KTP& P = kparams();
         if ((STATS || PROF) && c_post) { wc.cyc_post += __builtin_amdgcn_s_memtime() - c_post; c_post = 0; }
         // ---- local transitions until this lane waits for a query or is done ----
-        while (st == ST_ADVANCE || st == ST_LIGHT) {
+        // ST_LIGHT
+        auto light_step = [&]() {
             const unsigned long long cl = PROF ? __builtin_amdgcn_s_memtime() : 0;
-            if (st == ST_LIGHT) {
-                if (li < SV().n_lights) {
-                    const DLight L = bv.lights[li];
-                    const V3 hpos = at(cur.ray, is_time);          // org_ray.at(isect.time) (phong.cu:48)
-                    V3 dtl;
-                    if (L.type == 0) {                             // PointLight::shine (light.cu:63-70)
-                        V3 disp = L.v - hpos;
-                        float dist = len(disp);
-                        float quad = P.dist_atten.x + P.dist_atten.y * dist + P.dist_atten.z * dist * dist;
-                        da = quad < 1.0f ? 1.0f : 1.0f / quad;
-                        dtl = normalized(disp);
-                        max_t = dist;
-                    } else {                                       // DirLight::shine (light.cu:72-77)
-                        dtl = neg(L.v);
-                        max_t = INFINITY;
-                    }
-                    // to = make_ray(hpos, dtl): normalized(dtl) formed here once; phong's
-                    // reflect(neg(dtl), n) takes |neg(dtl)| = |dtl| (the same squares) and
-                    // normalized(neg(dtl)) = neg(normalized(dtl)) (the same magnitudes, RNE is
-                    // sign-symmetric; +0s below THRESH in both)
-                    const float tl = len(dtl);
-                    const bool tl_ok = tl > THRESH;
-                    const float tr = rcp_cr(tl);
-                    const Ray to{hpos, tl_ok ? tr * dtl : v3(0.0f, 0.0f, 0.0f)};
-                    const V3 tn = tl_ok ? tr * neg(dtl) : v3(0.0f, 0.0f, 0.0f);
-                    rv = L.col;                                    // Light::attenuate (light.cu:30-31)
-                    // Unlit skip: when phong's factor (diffuse + specular) is zero in every
-                    // channel -- the light behind the surface, no specular lobe -- the light's
-                    // term (factor x incoming) is that signed zero for every incoming light
-                    // >= +0, which the host guarantees (unlit_skip: light colours >= +0 and
-                    // finite, transmission Kt in [+0, 1], so every attenuation is >= +0 and
-                    // finite).  The shadow segments cannot change the sum: none is traced.
-                    // The lane still takes the wait-for-shadow step, with no query (max_t = -inf
-                    // marks it): no hit, so the light's term is phong's with the unshadowed
-                    // light, the same signed zeros.
-                    const DMat& mm = bv.mats[is_mat];
-                    fct = phong_factor(mm, TEX ? is_kd : mm.Kd, is_norm, NN ? is_nn : normalized(is_norm), cur.ray.d,
-                                       dtl, tl, tn);
-                    if (P.unlit_skip && fct.x == 0.0f && fct.y == 0.0f && fct.z == 0.0f && fct.w == 0.0f)
-                        max_t = -INFINITY;
-                    q = make_ray(at(to, THRESH), to.d);
-                    dbg(P, me, 4);
-                    st = ST_WAIT_SHADOW;
-                } else {
-                    acc = acc + cur.atten * summed;                 // scene.cu:127
-                    if (fl & 2) { fl &= ~2; pop(); }
-                    st = top < 0 ? ST_DONE : ST_ADVANCE;
+            if (li < SV().n_lights) {
+                const DLight L = bv.lights[li];
+                const V3 hpos = at(cur.ray, is_time);          // org_ray.at(isect.time) (phong.cu:48)
+                V3 dtl;
+                if (L.type == 0) {                             // PointLight::shine (light.cu:63-70)
+                    V3 disp = L.v - hpos;
+                    float dist = len(disp);
+                    float quad = P.dist_atten.x + P.dist_atten.y * dist + P.dist_atten.z * dist * dist;
+                    da = quad < 1.0f ? 1.0f : 1.0f / quad;
+                    dtl = normalized(disp);
+                    max_t = dist;
+                } else {                                       // DirLight::shine (light.cu:72-77)
+                    dtl = neg(L.v);
+                    max_t = INFINITY;
                 }
-                if (PROF) wc.cyc_light += __builtin_amdgcn_s_memtime() - cl;
-                continue;
+                // to = make_ray(hpos, dtl): normalized(dtl) formed here once; phong's
+                // reflect(neg(dtl), n) takes |neg(dtl)| = |dtl| (the same squares) and
+                // normalized(neg(dtl)) = neg(normalized(dtl)) (the same magnitudes, RNE is
+                // sign-symmetric; +0s below THRESH in both)
+                // (a point light's dtl is unit: closed forms on one vote of the lanes in this
+                // step; a directional light's |dtl|^2 is the light's own, and fails it)
+                float tl, tr;
+                len_rcp_vote(dot(dtl, dtl), tl, tr);
+                const bool tl_ok = tl > THRESH;
+                const Ray to{hpos, tl_ok ? tr * dtl : v3(0.0f, 0.0f, 0.0f)};
+                const V3 tn = tl_ok ? tr * neg(dtl) : v3(0.0f, 0.0f, 0.0f);
+                rv = L.col;                                    // Light::attenuate (light.cu:30-31)
+                // Unlit skip: when phong's factor (diffuse + specular) is zero in every
+                // channel -- the light behind the surface, no specular lobe -- the light's
+                // term (factor x incoming) is that signed zero for every incoming light
+                // >= +0, which the host guarantees (unlit_skip: light colours >= +0 and
+                // finite, transmission Kt in [+0, 1], so every attenuation is >= +0 and
+                // finite).  The shadow segments cannot change the sum: none is traced.
+                // The lane still takes the wait-for-shadow step, with no query (max_t = -inf
+                // marks it): no hit, so the light's term is phong's with the unshadowed
+                // light, the same signed zeros.
+                const DMat& mm = bv.mats[is_mat];
+                fct = phong_factor(mm, TEX ? is_kd : mm.Kd, is_norm, NN ? is_nn : normalized(is_norm), cur.ray.d,
+                                   dtl, tl, tn);
+                if (P.unlit_skip && fct.x == 0.0f && fct.y == 0.0f && fct.z == 0.0f && fct.w == 0.0f)
+                    max_t = -INFINITY;
+                q = Ray{at(to, THRESH), normalized_vote(to.d)};  // make_ray: to.d is unit already
+                dbg(P, me, 4);
+                st = ST_WAIT_SHADOW;
+            } else {
+                acc = acc + cur.atten * summed;                 // scene.cu:127
+                if (fl & 2) { fl &= ~2; pop(); }
+                st = top < 0 ? ST_DONE : ST_ADVANCE;
             }
-            // ST_ADVANCE
-            if (cur.type == F_NORMAL) {                            // scene.cu:100-103
-                is_time = INFINITY;
-                dbg(P, me, 1);
-                q = cur.ray;
-                st = ST_WAIT_NORMAL;
-                continue;
+            if (PROF) wc.cyc_light += __builtin_amdgcn_s_memtime() - cl;
+        };
+        // ST_ADVANCE, a NORMAL frame (scene.cu:100-103)
+        auto normal_step = [&]() {
+            is_time = INFINITY;
+            dbg(P, me, 1);
+            q = cur.ray;
+            st = ST_WAIT_NORMAL;
+        };
+        // ST_ADVANCE, a REFLECT frame (scene.cu:129-148: the frame's own hit)
+        auto reflect_step = [&]() {
+            const DMat& m = bv.mats[is_mat];
+            cur.type = F_REFRACT;
+            if (m.reflective) {
+                dbg(P, me, 2);
+                const V3 hp = at(cur.ray, is_time);
+                // NS = 0 with depth > 0: the host picks it only when no material is refractive.
+                // The suspended frame would then only be popped when resumed (its REFRACT step
+                // pops: the material of the shared Isect is never refractive, scene.cu:149-184),
+                // and so would every frame under it, so the child replaces it (a tail call):
+                // no stack, no scratch writes.
+                if (NS > 0) {
+                    stk[top].f = cur; stk[top].hit_pt = hp; stk[top].norm = is_norm;
+                    top++;
+                }
+                cur.type = F_NORMAL;                           // the child: last_mat, in_obj inherited
+                cur.atten = cur.atten * m.Kr;
+                cur.depth = cur.depth - 1;
+                // reflect's three lengths (the ray's, the normal's, the mirrored direction's) on one
+                // vote of the reflecting lanes; the normal is taken inside this arm (reflect
+                // re-normalises it: formed outside, that chain ran on every query).  Reflect of
+                // unit vectors is unit: the Ray ctor's normalisation by unit_len_rcp, on a second vote.
+                const V3 rd = reflect_vote(cur.ray.d, NN ? is_nn : normalized(is_norm));
+                float rl;
+                V3 rn;
+                if (!__ballot(!unit_head(dot(rd, rd)))) rn = normalized_unit(rd, rl);
+                else rn = normalized(keep_arm(rd));
+                cur.ray = Ray{hp, rn};
             }
+        };
+        // Without a frame stack (NS = 0: no refractive material) a lane makes at most one pass of
+        // LIGHT (the light step, or the frame's end), REFLECT, REFRACT (a pop: the sample is done),
+        // NORMAL between two queries: the same steps in the same order as the loop below, as
+        // predicated blocks, so that the integrator's state is not copied around a loop's back edge.
+        if (NS == 0) {
+            if (st == ST_LIGHT) light_step();
+            if (st == ST_ADVANCE && cur.type == F_REFLECT) reflect_step();
+            if (st == ST_ADVANCE && cur.type == F_REFRACT) { pop(); if (top < 0) st = ST_DONE; }
+            if (st == ST_ADVANCE && cur.type == F_NORMAL) normal_step();
+        } else
+        while (st == ST_ADVANCE || st == ST_LIGHT) {
+            if (st == ST_LIGHT) { light_step(); continue; }
+            if (cur.type == F_NORMAL) { normal_step(); continue; }
             const DMat& m = bv.mats[is_mat];
             bool do_pop = false;
-            if (cur.type == F_REFLECT) {                           // scene.cu:129-148 (frame's own hit)
-                cur.type = F_REFRACT;
-                if (m.reflective) {
-                    dbg(P, me, 2);
-                    const V3 hp = at(cur.ray, is_time);
-                    // NS = 0 with depth > 0: the host picks it only when no material is refractive.
-                    // The suspended frame would then only be popped when resumed (its REFRACT step
-                    // pops: the material of the shared Isect is never refractive, scene.cu:149-184),
-                    // and so would every frame under it, so the child replaces it (a tail call):
-                    // no stack, no scratch writes.
-                    if (NS > 0) {
-                        stk[top].f = cur; stk[top].hit_pt = hp; stk[top].norm = is_norm;
-                        top++;
-                    }
-                    cur.type = F_NORMAL;                           // the child: last_mat, in_obj inherited
-                    cur.atten = cur.atten * m.Kr;
-                    cur.depth = cur.depth - 1;
-                    // (reflect of unit vectors is unit: the Ray ctor's normalisation by unit_len_rcp,
-                    // on one vote of the reflecting lanes)
-                    const V3 rd = reflect(cur.ray.d, NN ? is_nn : normalized(is_norm));
-                    float rl;
-                    V3 rn;
-                    if (!__ballot(!unit_head(dot(rd, rd)))) rn = normalized_unit(rd, rl);
-                    else rn = normalized(keep_arm(rd));
-                    cur.ray = Ray{hp, rn};
-                }
+            if (cur.type == F_REFLECT) {
+                reflect_step();
             } else if (!OPQ && m.refractive) {                    // F_REFRACT (scene.cu:149-184)
                 dbg(P, me, 3);
                 cur.type = F_NORMAL;
@@ -1160,7 +1217,7 @@ __device__ __forceinline__ V4 trace_sample(const SceneView& S, const BvhRefs& bv
                 continue;
             }
             is_time = b.time; is_norm = hn; is_mat = hmat;
-            if (NN) is_nn = normalized(hn);
+            if (NN) is_nn = normalized_vote(hn);                   // hit_normal's fast arm returns a unit vector
             if (TEX) is_kd = hit_kd(P, bv, b, hmat);
             fl &= ~4;                                              // hit point / normal = at(ray, is_time), is_norm
             if (cur.depth > 0) {                                   // scene.cu:109-121
@@ -2425,6 +2482,12 @@ __global__ void kat_kernel(int op, int n, const float* a, const float* b, const 
             ou[i] = rtk::ray_key(r, rtk::KeyBox{L3(b + 6 * i), L3(b + 6 * i + 3)});
             break;
         }
+        // the shading chains' voted forms (one vote per wave of 64 consecutive elements): the
+        // generic functions' bits, whichever arm the wave takes
+        case 22: S3(of + 3 * i, normalized_vote(L3(a + 3 * i))); break;
+        case 23: { const V3 v = L3(a + 3 * i); len_rcp_vote(dot(v, v), of[2 * i], of[2 * i + 1]); break; }
+        case 24: S3(of + 3 * i, reflect_vote(L3(a + 3 * i), L3(b + 3 * i))); break;
+        case 25: S3(of + 3 * i, c[i] * normalized_vote(reflect_w(L3(a + 3 * i), L3(b + 3 * i)))); break;   // phong_factor's
         default: break;
     }
 }
@@ -2499,6 +2562,9 @@ TraceVariant choose_trace_variant(const SceneView& S, int spp, bool tex, bool wa
     static_cast<TraceKey&>(v) = trace_variant_key(S, spp, tex, want_stats, prof, ns, getenv("RT_NO_PART") != nullptr,
                                                   getenv("RT_NO_BRUTE_SKY") != nullptr);
     v.per_cu = 1;
+    // AXIS kernels hold no general-pose arm (cast_local): the key asks for one only through
+    // S.tri_ax, which view_of sets only when every rotation is the identity
+    if ((v.mode & M_AXIS) && !S.ident_all) return v;            // no kernel: the caller reports the key
     for (const TraceEntry& e : trace_kernels)
         if (e.ns == v.ns_bucket && e.lds == v.lds && e.mode == v.mode) v.fn = e.fn;
     if (!v.fn) return v;                                       // no such kernel: the caller reports the key

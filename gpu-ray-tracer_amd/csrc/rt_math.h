@@ -102,12 +102,26 @@ RT_HD float dot4(V4 a, V4 b) {
 }
 
 // reflect's tail with |dir| and normalized(dir), normalized(nrm) given
-RT_HD V3 reflect_pre(float d_len, V3 dn, V3 nn) {
+RT_HD V3 reflect_w(V3 dn, V3 nn) {                                   // the mirrored direction before its normalisation
     V3 proj = dot(dn, nn) * nn;
-    return d_len * normalized(dn - 2.0f * proj);
+    return dn - 2.0f * proj;
 }
+RT_HD V3 reflect_tail(float d_len, V3 w) { return d_len * normalized(w); }
+RT_HD V3 reflect_pre(float d_len, V3 dn, V3 nn) { return reflect_tail(d_len, reflect_w(dn, nn)); }
 RT_HD V3 reflect(V3 dir, V3 nrm) {                                   // linear.h:217-226
     return reflect_pre(len(dir), normalized(dir), normalized(nrm));
+}
+// The same with unit-length closed forms (unit_len_rcp): the generic functions' bits whenever every
+// squared length met -- |w|^2, and for reflect_unit |dir|^2 and |nrm|^2 before it -- lies inside
+// unit_window.  The mirror image of a unit vector in a unit normal is unit: |w|^2 = 1 - 4 c^2 +
+// 4 c^2 |nn|^2 with |c| <= 1 moves by a few roundings of magnitudes <= 3, so heads inside unit_head
+// keep |w|^2 inside the window (tests/unitlen_shade_host.cpp draws a million of them).
+RT_HD V3 reflect_tail_unit(float d_len, V3 w) { float l; return d_len * normalized_unit(w, l); }
+RT_HD V3 reflect_pre_unit(float d_len, V3 dn, V3 nn) { return reflect_tail_unit(d_len, reflect_w(dn, nn)); }
+RT_HD V3 reflect_unit(V3 dir, V3 nrm) {
+    float dl, nl;
+    const V3 dn = normalized_unit(dir, dl);
+    return reflect_pre_unit(dl, dn, normalized_unit(nrm, nl));
 }
 RT_HD V3 refract(V3 dir, V3 nrm, float from, float to, bool& tir) {  // linear.h:228-243
     float d_len = len(dir);

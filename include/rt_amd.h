@@ -350,7 +350,10 @@ int rt_debug_cast(rt_scene* s, int x, int y, char* buf, int64_t cap);
  * box_from_local / box_merge (box7 = min3 max3 nondegenerate; entity7 = quat4 pos3 -> box6 +
  * int) and entity (entity7, v3 -> point/vec to/from local, 12 floats), and ray_key (in0 = n*6
  * rays as traced: origin, unit direction; in1 = n*6 boxes: min3, max3; out_u = the coherence
- * keys of RT_QUERY_ORDER_SORTED).
+ * keys of RT_QUERY_ORDER_SORTED), and the shading chains' unit-length forms as the trace kernel
+ * runs them, one vote per wave of 64 consecutive elements between the closed and the generic
+ * form: normalized_unit (v3 -> normalized), unit_len_rcp (v3 -> len, 1 / len), reflect_unit
+ * (dir3, nrm3 -> reflect) and reflect_pre_unit (unit dir3, unit nrm3, length -> reflect's tail).
  * Host pointers in/out. */
 int rt_kat_device(const char* op, int n, const float* in0, const float* in1, const float* in2,
                   float* out_f, int32_t* out_i, uint64_t* out_u);
