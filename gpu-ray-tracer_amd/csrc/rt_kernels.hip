@@ -370,8 +370,23 @@ __device__ __forceinline__ V3 reflect_vote(V3 dir, V3 nrm) {
     return reflect(keep_arm(dir), keep_arm(nrm));
 }
 
-// Component `a` of a vector (a wave-uniform axis index: the selects fold into branches).
-__device__ __forceinline__ float comp(V3 v, int a) { return a == 0 ? v.x : a == 1 ? v.y : v.z; }
+// An axis-plane triangle's step for the wave, on the record's axis AX (cast_local dispatches on the
+// wave-uniform axis bits, so no component is picked by a select): the exact plane time tt from the
+// per-query reciprocal (axis_plane_t) and its window test, then, where some lane passed (`plane`)
+// and the record allows it, the exact in-plane reject (TriAx); `cand`: some lane is left.
+// The wave tests stay `__ballot(..) != 0`: here the compiler branches on the compare masks
+// themselves, while any_lane() made it rebuild each mask through a VGPR first (measured slower,
+// DESIGN.md §3.2 item 35).
+template <int AX>
+__device__ __forceinline__ void axis_step(const TriAx& x, const Ray& mr, V3 inv, float lo, float t_best, float& tt,
+                                          bool& pass, bool& plane, bool& cand) {
+    pass = axis_plane_pass<AX>(x, mr.o, inv, lo, t_best, tt);
+    plane = cand = __ballot(pass) != 0;
+    if (plane && (x.code & 8)) {
+        pass = pass && !axis_inplane_reject<AX>(x, mr, tt);
+        cand = __ballot(pass) != 0;
+    }
+}
 
 // t_lo: lower bound of any acceptable local time (-inf if none): the leaf box's entry
 // distance minus the pruning slack M (closest_hit).  A triangle whose plane crossing is
@@ -408,43 +423,47 @@ __device__ __forceinline__ bool cast_local(const SceneView& S, const BvhRefs& bv
         // Axis-plane path (fast kernel, identity rotations): exact plane time from the
         // per-query reciprocal (axis_plane_t), then the exact in-plane reject (TriAx);
         // general triangles take the filtered test below.  Same decisions, same order.
+        // One structured body per triangle: every path reaches the one latch, the twin skip is a
+        // scalar step there, and the accepted state (t_best, best, bu, bv_) is the loop's only
+        // vector state -- written in place by the accept and by nothing else.  (With `continue`s
+        // and `t++` inside a branch the compiler carried that state and the accept's temporaries
+        // through a second register set: 14 v_mov on an iteration that tests a plane and leaves.)
         const float lo = fmaxf(THRESH, t_lo);
-        for (int t = mesh.tri_begin; t < mesh.tri_begin + mesh.tri_count; t++) {
+        const int t_end = mesh.tri_begin + mesh.tri_count;
+        int t = mesh.tri_begin;
+        while (t < t_end) {
             const TriAx x = ldc(S.tri_ax, t);
             const int ax = x.code & 3;
-            float time, u, v;
+            int step = 1;
+            float tt;                                         // candidate lanes: the exact plane time
+            bool pass;
+            bool cand;                                        // some lane takes the inside test
             if (PROF) wc.wtri++;
-            if (ax == 3) {                                    // general triangle
+            if (ax == 3) {                                    // general triangle: filtered plane test
                 const TriHot h = ld_hot(S.tris, t);
                 float denom, num;
-                const bool pass = tri_plane_f(h.a, h.pn, mr, t_best, t_lo, denom, num);
-                if (!__ballot(pass)) continue;
+                pass = tri_plane_f(h.a, h.pn, mr, t_best, t_lo, denom, num);
+                cand = __ballot(pass) != 0;
+                if (cand) pass = pass && tri_time_f(t_best, denom, num, tt);
+            } else {
+                bool plane;                                   // some lane passed the plane time
+                if (ax == 0) axis_step<0>(x, mr, pre.inv, lo, t_best, tt, pass, plane, cand);
+                else if (ax == 1) axis_step<1>(x, mr, pre.inv, lo, t_best, tt, pass, plane, cand);
+                else axis_step<2>(x, mr, pre.inv, lo, t_best, tt, pass, plane, cand);
+                if (!plane) step += (x.code >> 2) & 1;        // same plane, same t, same best: the twin is rejected too
+                if (PROF && cand) { wc.wbary++; wc.lbary += __popcll(__ballot(pass)); }
+            }
+            if (cand) {                                       // the one inside test, for both kinds
+                const TriHot h = ld_hot(S.tris, t);
                 const TriRest q = ld_rest(S.tris, t);
-                if (pass && tri_inside_f(h.a, q.b, q.c, q.area, q.inv_area, mr, t_best, denom, num, time, u, v)) {
-                    t_best = time; best = t; bu = u; bv_ = v;
+                if (pass) {
+                    float time, u, v;
+                    if (tri_inside_t(h.a, q.b, q.c, q.area, q.inv_area, mr, tt, time, u, v)) {
+                        t_best = time; best = t; bu = u; bv_ = v;
+                    }
                 }
-                continue;
             }
-            const int au = ax == 2 ? 0 : ax + 1, av = ax == 0 ? 2 : ax - 1;
-            const float tt = axis_plane_t(x.a_ax, comp(mr.o, ax), comp(pre.inv, ax));
-            bool pass = tt >= lo && tt < t_best;
-            if (!__ballot(pass)) {
-                if (x.code & 4) t++;                          // same plane, same t, same best: rejected too
-                continue;
-            }
-            if (x.code & 8) {                                 // in-plane reject (TriAx)
-                const float pu = comp(mr.o, au) + tt * comp(mr.d, au), pv = comp(mr.o, av) + tt * comp(mr.d, av);
-                const float pa = comp(mr.o, ax) + tt * comp(mr.d, ax);
-                const float e = fmaxf(fmaxf(x.ulo - pu, pu - x.uhi), fmaxf(x.vlo - pv, pv - x.vhi));
-                pass = pass && !(e > 0.0f && e <= x.win && fabsf(pa - x.a_ax) <= x.off);
-                if (!__ballot(pass)) continue;
-            }
-            if (PROF) { wc.wbary++; wc.lbary += __popcll(__ballot(pass)); }
-            const TriHot h = ld_hot(S.tris, t);
-            const TriRest q = ld_rest(S.tris, t);
-            if (pass && tri_inside_t(h.a, q.b, q.c, q.area, q.inv_area, mr, tt, time, u, v)) {
-                t_best = time; best = t; bu = u; bv_ = v;
-            }
+            t += step;
         }
     } else
     // The plane filter needs only the 32-B head (pn, a) of each record (one batch of

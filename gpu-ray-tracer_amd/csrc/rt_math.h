@@ -402,10 +402,15 @@ RT_HD bool tri_inside_t(V3 a, V3 b, V3 c, float area, float inv_area, const Ray&
     if (fabsf(b0 + b1 + b2 - 1.0f) <= THRESH) { time = t; u = b1; v = b2; return true; }
     return false;
 }
+// The exact plane time of a triangle that passed tri_plane_f, and the reference's test of it.
+RT_HD bool tri_time_f(float best, float denom, float num, float& t) {
+    t = rcp_cr(denom) * num;                              // exact (geometry.h:259)
+    return t >= THRESH && t < best;
+}
 RT_HD bool tri_inside_f(V3 a, V3 b, V3 c, float area, float inv_area, const Ray& r, float best, float denom,
                         float num, float& time, float& u, float& v) {
-    float t = rcp_cr(denom) * num;                        // exact (geometry.h:259)
-    if (!(t >= THRESH && t < best)) return false;
+    float t;
+    if (!tri_time_f(best, denom, num, t)) return false;
     return tri_inside_t(a, b, c, area, inv_area, r, t, time, u, v);
 }
 
@@ -474,6 +479,22 @@ RT_HD bool pow_pos(float xf, float yf, float& out) {
 // (e/D)(1 - 5.6u - eta) - (5.6u + eta) - 41.8 u (D + e + off)^2 / A > 1.01e-5 at e = m and
 // e = win; the left side is concave in e, so it holds on the whole range.
 struct TriAx { int code; float a_ax, ulo, uhi, vlo, vhi, win, off; };
+// The lane's share of an axis-plane triangle's step in cast_local, for a compile-time axis AX
+// (every component pick is a register name, not a select on the record's axis bits).
+template <int A> RT_HD float pick(V3 v) { return A == 0 ? v.x : A == 1 ? v.y : v.z; }
+// The exact plane time tt and its window test, lo <= tt < t_best (a NaN time fails both).
+template <int AX> RT_HD bool axis_plane_pass(const TriAx& x, V3 o, V3 inv, float lo, float t_best, float& tt) {
+    tt = axis_plane_t(x.a_ax, pick<AX>(o), pick<AX>(inv));
+    return tt >= lo && tt < t_best;
+}
+// The in-plane reject above: true when at(r, tt) certainly fails the inside test.
+template <int AX> RT_HD bool axis_inplane_reject(const TriAx& x, const Ray& r, float tt) {
+    constexpr int AU = AX == 2 ? 0 : AX + 1, AV = AX == 0 ? 2 : AX - 1;
+    const float pu = pick<AU>(r.o) + tt * pick<AU>(r.d), pv = pick<AV>(r.o) + tt * pick<AV>(r.d);
+    const float pa = pick<AX>(r.o) + tt * pick<AX>(r.d);
+    const float e = fmaxf(fmaxf(x.ulo - pu, pu - x.uhi), fmaxf(x.vlo - pv, pv - x.vhi));
+    return e > 0.0f && e <= x.win && fabsf(pa - x.a_ax) <= x.off;
+}
 RT_HD bool tri_accept_f(V3 a, V3 b, V3 c, V3 pn, float area, float inv_area, const Ray& r, float best,
                         float& time, float& u, float& v) {
     float denom, num;
