@@ -590,9 +590,23 @@ struct Isect { float time; V3 norm; float u, v; int mat; int inst, tri; };
 thread_local std::string* g_dbg = nullptr;
 inline void dbg_event(const char* e) { if (g_dbg) { *g_dbg += e; *g_dbg += '\n'; } }
 struct Counters { uint64_t rays = 0, nodes = 0, leaves = 0, tris = 0; };
+// Integrator census (orc_render_census, rt_oracle.h: ORC_CENSUS_*): how often propagate_gpu and
+// attenuate took each branch.  Counting only; no rendered value depends on it.
+struct Census {
+    uint64_t v[ORC_CENSUS_N] = {};
+    void add(int k) { v[k]++; }
+    void top(uint64_t t) { if (t > v[ORC_CENSUS_MAX_TOP]) v[ORC_CENSUS_MAX_TOP] = t; }
+    void merge(const Census& o) {
+        for (int k = 0; k < ORC_CENSUS_N; k++) {
+            if (k == ORC_CENSUS_MAX_TOP) top(o.v[k]);
+            else v[k] += o.v[k];
+        }
+    }
+};
 
 struct Ctx {
     const orc_scene* s; const BVH* bvh; bool use_bvh; bool cpu_sem; Counters* c;
+    Census* z = nullptr;                                                     // NULL: not counted
 };
 
 bool tri_hit(const Ctx& x, int t, const Ray& lr, Isect& is) {               // trimesh.cu:46-68
@@ -702,9 +716,10 @@ V4 attenuate(const Ctx& x, const Light& L, const Ray& to_light, float max_t) {  
         Isect si; si.time = INFINITY; si.mat = -1; si.inst = -1; si.tri = -1; si.norm = v3(0, 0, 0);
         dbg_event("shooting shadow ray");                                    // light.cu:38-39
         if (cast_ray(x, cur, si)) {
-            if (si.time > max_t) return rv;
+            if (si.time > max_t) { if (x.z) x.z->add(ORC_CENSUS_SHADOW_PAST_LIGHT); return rv; }
             const Material& m = x.s->mats[si.mat];
             if (!refractive(m)) return V4{0, 0, 0, 0};
+            if (x.z) { x.z->add(ORC_CENSUS_SHADOW_CONTINUED); if (dot(si.norm, cur.d) > 0) x.z->add(ORC_CENSUS_SHADOW_BACK_FACE); }
             if (dot(si.norm, cur.d) > 0) rv = mul4(rv, calc_shadow_atten(m.Kt, si.time));
             cur = make_ray(ray_at(cur, si.time), cur.d);
             max_t -= si.time;
@@ -758,7 +773,10 @@ V4 illuminate(const Ctx& x, const Ray& org, const Isect& is) {              // p
 // Integrators
 // ----------------------------------------------------------------------------
 enum FrameType { NORMAL, REFLECT, REFRACT };
-struct RayFrame { Ray ray; V3 hit_pt, norm; V4 atten; int last_mat; FrameType type; int depth; bool in_obj; };
+struct RayFrame {
+    Ray ray; V3 hit_pt, norm; V4 atten; int last_mat; FrameType type; int depth; bool in_obj;
+    bool pushed = false;   // census only: this frame's REFLECT step pushed a child since its last hit
+};
 
 V4 propagate_gpu(const Ctx& x, const Ray& r, Isect& is) {                   // scene.cu:92-188
     const orc_scene& s = *x.s;
@@ -766,13 +784,23 @@ V4 propagate_gpu(const Ctx& x, const Ray& r, Isect& is) {                   // s
     frames[0] = RayFrame{r, v3(0, 0, 0), v3(0, 0, 0), V4{1, 1, 1, 1}, -1, NORMAL, s.depth, false};
     int top_i = 0;
     V4 acc{0, 0, 0, 0};
+    Census* z = x.z;
     while (top_i >= 0) {
         RayFrame& top = frames[top_i];
+        if (z) z->top((uint64_t)top_i);
         switch (top.type) {
             case NORMAL: {
                 is.time = INFINITY;
                 dbg_event("shooting a ray");                                     // scene.cu:107-108
                 if (cast_ray(x, top.ray, is)) {
+                    if (z) {
+                        if (top.depth == 0) z->add(ORC_CENSUS_DEPTH0_HITS);
+                        else if (top.in_obj) {
+                            z->add(ORC_CENSUS_INOBJ_HITS);
+                            if (is.mat != top.last_mat) z->add(ORC_CENSUS_INOBJ_OTHER_MAT);
+                        }
+                        top.pushed = false;
+                    }
                     if (top.depth > 0) {
                         if (top.in_obj) top.atten = mul4(top.atten, trans_atten(s.mats[is.mat], is.time));
                         top.type = REFLECT;
@@ -793,8 +821,10 @@ V4 propagate_gpu(const Ctx& x, const Ray& r, Isect& is) {                   // s
                 top.type = REFRACT;
                 if (reflective(m)) {
                     dbg_event("preparing to shoot a reflection ray");            // scene.cu:134-135
+                    top.pushed = true;
                     top_i++;
                     RayFrame& nt = frames[top_i];
+                    nt.pushed = false;
                     nt.type = NORMAL; nt.last_mat = top.last_mat; nt.in_obj = top.in_obj;
                     nt.atten = mul4(top.atten, m.Kr);
                     nt.depth = top.depth - 1;
@@ -804,13 +834,22 @@ V4 propagate_gpu(const Ctx& x, const Ray& r, Isect& is) {                   // s
             }
             case REFRACT: {
                 const Material& m = s.mats[is.mat];
+                if (z && is.mat != top.last_mat) {
+                    z->add(ORC_CENSUS_REFRACT_MAT_DIFFERS);
+                    if (refractive(m)) {
+                        z->add(ORC_CENSUS_REFRACT_MAT_DIFFERS_REFRACTIVE);
+                        if (m.eta != s.mats[top.last_mat].eta) z->add(ORC_CENSUS_REFRACT_ETA_DIFFERS);
+                    }
+                }
                 if (refractive(m)) {
+                    if (z && top.pushed) z->add(ORC_CENSUS_REFRACT_RESUMED);
                     dbg_event("preparing to shoot a refraction ray");            // scene.cu:152-153
                     top.type = NORMAL;
                     float n1, n2; bool tir;
                     if (top.in_obj) { n1 = s.mats[top.last_mat].eta; n2 = 1.0f; }
                     else { n1 = 1.0f; n2 = s.mats[top.last_mat].eta; }
                     V3 rd = refract(top.ray.d, normalized(top.norm), n1, n2, tir);
+                    if (z && tir) { z->add(ORC_CENSUS_TIR); if (!top.in_obj) z->add(ORC_CENSUS_TIR_ENTERING); }
                     if (tir) top_i--;
                     else { top.ray = make_ray(top.hit_pt, rd); top.in_obj = !top.in_obj; top.depth--; }
                 } else top_i--;
@@ -862,12 +901,14 @@ struct RenderJob {
     const std::vector<int>* rows; size_t r_begin, r_end;
     uint32_t* rgba; float* rad; int32_t* hi; int32_t* ht;
     Counters cnt;
+    Census cen;
 };
 
 void render_rows(RenderJob* J) {
     const orc_scene& s = *J->s;
     CamBasis cb = cam_basis(s.cam);
     Ctx x{&s, J->bvh, J->use_bvh != 0, J->sem == ORC_SEM_CPU, &J->cnt};
+    if (J->sem == ORC_SEM_GPU) x.z = &J->cen;
     for (size_t ri = J->r_begin; ri < J->r_end; ri++) {
         int y = (*J->rows)[ri];
         for (int xx = 0; xx < s.W; xx++) {
@@ -882,7 +923,7 @@ void render_rows(RenderJob* J) {
                 else {
                     if (k == 0 && (J->hi || J->ht)) {
                         // primary hit ids: an extra probe of the primary ray (not counted)
-                        Counters dummy; Ctx px = x; px.c = &dummy;
+                        Counters dummy; Ctx px = x; px.c = &dummy; px.z = nullptr;
                         Isect ps = is; ps.time = INFINITY;
                         if (cast_ray(px, r, ps)) { hinst = ps.inst; htri = ps.tri; }
                     }
@@ -1127,8 +1168,8 @@ int orc_build_bvh(const orc_scene* s, float* boxes, int32_t* ordering, int max_n
     return b.n;
 }
 
-int orc_render(const orc_scene* s, int sem, int use_bvh, int spp, int row0, int row_step, int nthreads,
-               uint32_t* rgba, float* rad, int32_t* hi, int32_t* ht, uint64_t* stats) {
+static int render_frame(const orc_scene* s, int sem, int use_bvh, int spp, int row0, int row_step, int nthreads,
+                        uint32_t* rgba, float* rad, int32_t* hi, int32_t* ht, uint64_t* stats, uint64_t* census) {
     if (spp < 1 || row_step < 1 || row0 < 0) { g_err = "bad arguments"; return -1; }
     if (s->building) { g_err = "builder scene not finished"; return -1; }
     BVH bvh = build_bvh(*s, sem == ORC_SEM_CPU);
@@ -1142,7 +1183,7 @@ int orc_render(const orc_scene* s, int sem, int use_bvh, int spp, int row0, int 
     for (size_t i = 0; i < rows.size(); i++) per[i % nthreads].push_back(rows[i]);
     std::vector<pthread_t> th(nthreads);
     for (int t = 0; t < nthreads; t++) {
-        jobs[t] = RenderJob{s, &bvh, sem, use_bvh, spp, &per[t], 0, per[t].size(), rgba, rad, hi, ht, Counters{}};
+        jobs[t] = RenderJob{s, &bvh, sem, use_bvh, spp, &per[t], 0, per[t].size(), rgba, rad, hi, ht, Counters{}, Census{}};
     }
     if (nthreads == 1 && sem == ORC_SEM_GPU) {
         render_rows(&jobs[0]);
@@ -1157,7 +1198,23 @@ int orc_render(const orc_scene* s, int sem, int use_bvh, int spp, int row0, int 
         stats[0] = stats[1] = stats[2] = stats[3] = 0;
         for (auto& j : jobs) { stats[0] += j.cnt.rays; stats[1] += j.cnt.nodes; stats[2] += j.cnt.leaves; stats[3] += j.cnt.tris; }
     }
+    if (census) {
+        Census all;
+        for (auto& j : jobs) all.merge(j.cen);
+        memcpy(census, all.v, sizeof all.v);
+    }
     return 0;
+}
+
+int orc_render(const orc_scene* s, int sem, int use_bvh, int spp, int row0, int row_step, int nthreads,
+               uint32_t* rgba, float* rad, int32_t* hi, int32_t* ht, uint64_t* stats) {
+    return render_frame(s, sem, use_bvh, spp, row0, row_step, nthreads, rgba, rad, hi, ht, stats, nullptr);
+}
+
+int orc_render_census(const orc_scene* s, int use_bvh, int spp, int row0, int row_step, int nthreads,
+                      uint32_t* rgba, float* rad, int32_t* hi, int32_t* ht, uint64_t* stats, uint64_t* census) {
+    if (!census) { g_err = "census: no output array"; return -1; }
+    return render_frame(s, ORC_SEM_GPU, use_bvh, spp, row0, row_step, nthreads, rgba, rad, hi, ht, stats, census);
 }
 
 // ---- KATs ----

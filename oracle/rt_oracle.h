@@ -90,6 +90,31 @@ int orc_render(const orc_scene* s, int semantics, int use_bvh, int spp,
                uint32_t* rgba, float* radiance, int32_t* hit_inst, int32_t* hit_tri,
                uint64_t* stats);
 
+/* orc_render with ORC_SEM_GPU, and an integrator census beside it: how often the frame's
+ * propagate_ray (scene.cu:92-188) and Light::attenuate (light.cu:29-61) took each branch, so
+ * that a test scene can prove it reaches them.  The rendered outputs are orc_render's, bit for
+ * bit.  census[ORC_CENSUS_N], summed over the rendered samples (MAX_TOP: the maximum):
+ *   MAX_TOP                        the largest frame-stack index top_i
+ *   INOBJ_HITS                     NORMAL hits with in_obj and depth > 0 (trans_atten applied)
+ *   INOBJ_OTHER_MAT                ... whose material is not the frame's last_mat
+ *   REFRACT_MAT_DIFFERS            REFRACT steps where the shared Isect's material is not last_mat
+ *   REFRACT_MAT_DIFFERS_REFRACTIVE ... and is refractive (the step refracts, with last_mat's eta)
+ *   REFRACT_ETA_DIFFERS            ... and the two materials' eta differ
+ *   REFRACT_RESUMED                refracting REFRACT steps of a frame whose REFLECT step pushed a child
+ *                                  (hit point and normal are the frame's saved ones, not the Isect's)
+ *   TIR, TIR_ENTERING              total internal reflections; those with in_obj false
+ *   SHADOW_CONTINUED               shadow segments continued through a refractive hit
+ *   SHADOW_BACK_FACE               ... with dot(norm, d) > 0 (calc_shadow_atten applied)
+ *   SHADOW_PAST_LIGHT              shadow hits beyond the light (time > max_t)
+ *   DEPTH0_HITS                    NORMAL hits at depth 0 (lit, then popped) */
+enum { ORC_CENSUS_MAX_TOP = 0, ORC_CENSUS_INOBJ_HITS, ORC_CENSUS_INOBJ_OTHER_MAT, ORC_CENSUS_REFRACT_MAT_DIFFERS,
+       ORC_CENSUS_REFRACT_MAT_DIFFERS_REFRACTIVE, ORC_CENSUS_REFRACT_ETA_DIFFERS, ORC_CENSUS_REFRACT_RESUMED,
+       ORC_CENSUS_TIR, ORC_CENSUS_TIR_ENTERING, ORC_CENSUS_SHADOW_CONTINUED, ORC_CENSUS_SHADOW_BACK_FACE,
+       ORC_CENSUS_SHADOW_PAST_LIGHT, ORC_CENSUS_DEPTH0_HITS, ORC_CENSUS_N };
+int orc_render_census(const orc_scene* s, int use_bvh, int spp, int row0, int row_step, int nthreads,
+                      uint32_t* rgba, float* radiance, int32_t* hit_inst, int32_t* hit_tri,
+                      uint64_t* stats, uint64_t* census);
+
 /* debug_cast (raytracer.cu:91-100): the event log ("shooting a ray", "preparing to shoot a
  * reflection ray", "preparing to shoot a refraction ray", "shooting shadow ray", one per line,
  * scene.cu:107-153 / light.cu:38-39) of pixel (x, y)'s ray, into buf (NUL-terminated). */

@@ -14,7 +14,9 @@ Two families:
    ids, counters).  These are produced by the oracle restatement and are pinned
    indirectly: their ray/node/leaf/triangle counters equal the measurements of
    the reference recorded in SURVEY.md Appendix D (checked by
-   tests/test_oracle.py).
+   tests/test_oracle.py).  ``frame_media_48x32_d9.npz`` is the same for a built scene
+   (tests/integrator_cases.py), with the integrator census; tests/test_integrator_host.py
+   re-renders it.
 
 Run in the build container (needs /root/reference for family 1):
     make -C oracle ref && python tests/golden/make_golden.py
@@ -218,11 +220,29 @@ def make_frames():
         print("frame", name, fr["stats"])
 
 
+def make_integrator_frame():
+    """frame_media_48x32_d9.npz: the oracle's frame of tests/integrator_cases.py's `media` scene (built through
+    the SceneBuilder calls, no scene file) from its first pose at depth 9, 1 spp, with the integrator
+    census beside it (oracle_lib.CENSUS order).  tests/test_integrator_host.py re-renders it."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import integrator_cases as ic  # noqa: E402
+    from oracle_lib import CENSUS, Oracle  # noqa: E402
+    orc = Oracle()
+    s = orc.create()
+    ic.build(s, "media", size=(48, 32), depth=9)
+    fr = orc.render(s, nthreads=8, census=True)
+    fr["census"] = np.array([fr["census"][k] for k in CENSUS], np.uint64)
+    np.savez_compressed(os.path.join(HERE, "frame_media_48x32_d9.npz"), **fr)
+    print("frame frame_media_48x32_d9.npz", fr["stats"], fr["census"])
+
+
 if __name__ == "__main__":
-    what = sys.argv[1:] or ["kats", "frames"]
+    what = sys.argv[1:] or ["kats", "frames", "integrator"]
     if "kats" in what:
         make_kats()
     if "kats" in what or "geometry" in what:
         make_kats_geometry()
     if "frames" in what:
         make_frames()
+    if "integrator" in what:
+        make_integrator_frame()

@@ -39,6 +39,10 @@ Variants: `_r` one refractive material (Kt in (0, 1), eta 1.3; with Kr and Ka so
 bounce shows): ns = max(depth, 1), NS 2 at depth 2 and NS 9 at depth 3 or 4 (rt_env_set); all-opaque
 scenes have ns = 0.  `_rot` one instance turned 45 degrees about y: S.tri_ax = nullptr, the kernels
 without M_AXIS / M_SHADE / M_BRUTE.
+
+Depths outside 2 to 4 (0 and 1 in the NS 2 bucket, 5 to 9 with the NS 9 stack full), several refractive
+media of different eta and Kt, and total internal reflection: tests/integrator_cases.py and
+tests/test_gpu_integrator.py, over the kernels a small scene reaches (M180, M420, M116, M2).
 """
 import json
 import os

@@ -17,6 +17,12 @@ _u = ctypes.POINTER(ctypes.c_uint64)
 _u32 = ctypes.POINTER(ctypes.c_uint32)
 
 
+# orc_render_census's counts, in the order of rt_oracle.h's ORC_CENSUS_* (max_top is a maximum, the rest are sums)
+CENSUS = ("max_top", "inobj_hits", "inobj_other_mat", "refract_mat_differs", "refract_mat_differs_refractive",
+          "refract_eta_differs", "refract_resumed", "tir", "tir_entering", "shadow_continued", "shadow_back_face",
+          "shadow_past_light", "depth0_hits")
+
+
 def _p(a, t):
     return None if a is None else a.ctypes.data_as(t)
 
@@ -35,6 +41,8 @@ class Oracle:
         L.orc_free.argtypes = [ctypes.c_void_p]
         L.orc_render.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                  ctypes.c_int, _u32, _f, _i, _i, _u]
+        L.orc_render_census.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                        ctypes.c_int, _u32, _f, _i, _i, _u, _u]
         L.orc_build_bvh.argtypes = [ctypes.c_void_p, _f, _i, ctypes.c_int]
         for name in ["orc_scene_counts", "orc_scene_vertices", "orc_scene_normals", "orc_scene_tris",
                      "orc_scene_materials", "orc_scene_lights"]:
@@ -80,18 +88,28 @@ class Oracle:
         return dx.value, dy.value
 
     def render(self, scene, semantics=0, use_bvh=1, spp=1, row0=0, row_step=1, nthreads=8,
-               want=("rgba", "radiance", "hit_inst", "hit_tri")):
+               want=("rgba", "radiance", "hit_inst", "hit_tri"), census=False):
+        """census=True (semantics 0 only): orc_render_census, the same frame with out["census"] = {name: count}
+        over CENSUS beside it."""
         W, H = scene.W, scene.H
         rgba = np.zeros(W * H, np.uint32) if "rgba" in want else None
         rad = np.zeros(W * H * 4, np.float32) if "radiance" in want else None
         hi = np.full(W * H, -1, np.int32) if "hit_inst" in want else None
         ht = np.full(W * H, -1, np.int32) if "hit_tri" in want else None
         st = np.zeros(4, np.uint64)
-        r = self.L.orc_render(scene.h, semantics, use_bvh, spp, row0, row_step, nthreads,
-                              _p(rgba, _u32), _p(rad, _f), _p(hi, _i), _p(ht, _i), _p(st, _u))
+        if census:
+            assert semantics == 0, "the census counts propagate_ray's GPU semantics"
+            cen = np.zeros(len(CENSUS), np.uint64)
+            r = self.L.orc_render_census(scene.h, use_bvh, spp, row0, row_step, nthreads,
+                                         _p(rgba, _u32), _p(rad, _f), _p(hi, _i), _p(ht, _i), _p(st, _u), _p(cen, _u))
+        else:
+            r = self.L.orc_render(scene.h, semantics, use_bvh, spp, row0, row_step, nthreads,
+                                  _p(rgba, _u32), _p(rad, _f), _p(hi, _i), _p(ht, _i), _p(st, _u))
         if r != 0:
             raise RuntimeError(self.L.orc_last_error().decode())
         out = {"stats": st}
+        if census:
+            out["census"] = {k: int(v) for k, v in zip(CENSUS, cen)}
         if rgba is not None:
             out["rgba"] = rgba.reshape(H, W)
         if rad is not None:

@@ -9,6 +9,8 @@
 //                                               (n_leaf padded from n_inst; tests/kernel_recipes.py)
 //   plan_host scene_bytes n_inst n_real n_tris n_mats n_lights n_meshes
 //                                               lds_bytes(S, true, true), rt_work.scene_bytes
+//   plan_host shortcuts want_stats dbg depth amb(4) n_mats n_lights {Ke(4) Ka(4) Kt(4)} x n_mats {col(4)} x n_lights
+//                                               shade_shortcuts' unlit_skip, occl_exit, ns (tests/test_integrator_host.py)
 //   plan_host geometry W H row0 row_step spp    frame_geometry's fields
 //   plan_host grid n_cu per_cu n_groups n_slots overlap other_running ranks_per_device
 //   plan_host history want_stats dbg sky prof heavy_q n_groups full_waves
@@ -92,8 +94,25 @@ int main(int argc, char** argv) {
         printf("blocks %d grid_waves %d heavy_static %d heavy_cap %d\n", p.blocks, p.grid_waves, p.heavy_static, p.heavy_cap);
     } else if (argc == 9 && !strcmp(argv[1], "history")) {
         printf("hist %d\n", history_mode(arg(2) != 0, arg(3) != 0, arg(4) != 0, arg(5) != 0, (int)arg(6), arg(7), arg(8)));
+    } else if (argc >= 11 && !strcmp(argv[1], "shortcuts") && argc == 11 + 12 * atoi(argv[9]) + 4 * atoi(argv[10])) {
+        // shade_shortcuts over the fields it reads: the ambience, the depth, every material's Ke, Ka, Kt
+        // (refractive as flatten sets it: some Kt channel > 0) and every light's colour
+        rt::Scene h;
+        h.ambience = rtm::V4{(float)atof(argv[5]), (float)atof(argv[6]), (float)atof(argv[7]), (float)atof(argv[8])};
+        h.depth = (int)arg(4);
+        const char* const* f = argv + 11;
+        auto v4 = [&]() { rtm::V4 v{(float)atof(f[0]), (float)atof(f[1]), (float)atof(f[2]), (float)atof(f[3])}; f += 4; return v; };
+        for (int i = 0; i < atoi(argv[9]); i++) {
+            rt::DMat m{};
+            m.Ke = v4(); m.Ka = v4(); m.Kt = v4();
+            m.refractive = m.Kt.x > 0 || m.Kt.y > 0 || m.Kt.z > 0 || m.Kt.w > 0;
+            h.d_mats.push_back(m);
+        }
+        for (int i = 0; i < atoi(argv[10]); i++) { rt::DLight l{}; l.col = v4(); h.d_lights.push_back(l); }
+        const ShadeShortcuts c = shade_shortcuts(h, arg(2) != 0, arg(3) != 0, -1);
+        printf("unlit_skip %d occl_exit %d ns %d\n", c.unlit_skip, c.occl_exit, c.ns);
     } else {
-        fprintf(stderr, "usage: plan_host variants | key ... | scene_bytes ... | geometry ... | grid ... | history ...\n");
+        fprintf(stderr, "usage: plan_host variants | key ... | scene_bytes ... | shortcuts ... | geometry ... | grid ... | history ...\n");
         return 2;
     }
     return 0;
