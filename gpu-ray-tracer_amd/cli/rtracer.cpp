@@ -2,7 +2,7 @@
 //
 //   rtracer -c world8.json [-b] [-r] [-s] [-d DIM] [--frames N] [--spp K]
 //           [--width W --height H] [--out frame.ppm] [--debug X,Y] [--textures [ATLAS.png]]
-//           [--gpus N [--ranks R]] [--in-flight D] [--pick X,Y]
+//           [--gpus N [--ranks R]] [--in-flight D] [--pick X,Y] [--accumulate N]
 //
 // -c config (worldN.json), -b benchmark (one timed frame, "Time: X ms" as main.cc:210-216),
 // -r unoptimize (brute force, no BVH), -d kernel dimension (accepted; the HIP path
@@ -20,6 +20,9 @@
 // --overlap sets the frames' grid policy (rt_scene_set_overlap; default stream).
 // --pick X,Y (build extension, rt_query): the instance under pixel (X, Y) -- one line,
 // "pick X Y inst I tri T t <distance>" or "pick X Y miss" -- and nothing is rendered.
+// --accumulate N (build extension, rt_accumulate): progressive refinement -- N calls that add one
+// sample each to the scene's running sums, as an interactive loop does while nothing moves; the
+// frame after the last call is the --spp N frame, and --out writes it.  -b prints each call's time.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -37,7 +40,7 @@ static void usage() {
     std::fprintf(stderr,
                  "usage: rtracer -c CONFIG [-b] [-r] [-s] [-d DIM] [--frames N] [--spp K] [--width W --height H]\n"
                  "               [--out FILE.ppm] [--debug X,Y] [--textures [ATLAS.png]] [--gpus N [--ranks R]]\n"
-                 "               [--in-flight D [--readback] [--overlap stream|half|full]] [--pick X,Y]\n");
+                 "               [--in-flight D [--readback] [--overlap stream|half|full]] [--pick X,Y] [--accumulate N]\n");
 }
 
 static bool write_ppm(const char* path, const uint32_t* px, int w, int h) {
@@ -60,7 +63,7 @@ int main(int argc, char** argv) {
     std::string config, out;
     bool bench = false, unopt = false, serial = false, textures = false, readback = false;
     std::string atlas, overlap = "stream";
-    int dim = 16, frames = 1, spp = 1, width = 0, height = 0, dbg_x = -1, dbg_y = -1, pick_x = -1, pick_y = -1, gpus = 1, ranks = 0, in_flight = 0;
+    int dim = 16, frames = 1, spp = 1, width = 0, height = 0, dbg_x = -1, dbg_y = -1, pick_x = -1, pick_y = -1, gpus = 1, ranks = 0, in_flight = 0, accumulate = 0;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto val = [&](const char* name) -> const char* {
@@ -80,6 +83,7 @@ int main(int argc, char** argv) {
         else if (a == "--gpus") gpus = std::atoi(val("--gpus"));
         else if (a == "--ranks") ranks = std::atoi(val("--ranks"));
         else if (a == "--in-flight") in_flight = std::atoi(val("--in-flight"));
+        else if (a == "--accumulate") { accumulate = std::atoi(val("--accumulate")); if (accumulate < 1) { usage(); return 2; } }
         else if (a == "--readback") readback = true;
         else if (a == "--overlap") {
             overlap = val("--overlap");
@@ -136,6 +140,35 @@ int main(int argc, char** argv) {
         }
         if (inst >= 0) std::printf("pick %d %d inst %d tri %d t %.9g\n", pick_x, pick_y, inst, tri, (double)t);
         else std::printf("pick %d %d miss\n", pick_x, pick_y);
+        rt_scene_free(handle);
+        return 0;
+    }
+    if (accumulate > 0) {                                  // one sample per call into the scene's sums
+        int32_t info[10];
+        rtamd_detail::check(rt_scene_info(handle, info), "rt_scene_info");
+        std::vector<uint32_t> frame((size_t)info[0] * info[1]);
+        int n = 0;
+        for (int k = 0; k < accumulate; k++) {
+            rt_accum_opts o;
+            rt_accum_opts_default(&o);
+            o.use_bvh = unopt ? 0 : 1; o.textures = textures ? 1 : 0;
+            o.rebuild_bvh = k == 0;                            // nothing moves between the calls
+            o.host_outputs = 1; o.rgba = frame.data();
+            auto from = std::chrono::high_resolution_clock::now();
+            if (rt_accumulate(handle, &o, &n) != RT_OK) {
+                std::fprintf(stderr, "accumulate failed: %s\n", rt_last_error());
+                rt_scene_free(handle);
+                return 1;
+            }
+            auto to = std::chrono::high_resolution_clock::now();
+            if (bench) std::printf("Sample %d: %g ms\n", n, std::chrono::duration<double, std::milli>(to - from).count());
+        }
+        std::printf("Accumulated %d samples\n", n);
+        if (!out.empty() && !write_ppm(out.c_str(), frame.data(), info[0], info[1])) {
+            std::fprintf(stderr, "cannot write %s\n", out.c_str());
+            rt_scene_free(handle);
+            return 1;
+        }
         rt_scene_free(handle);
         return 0;
     }

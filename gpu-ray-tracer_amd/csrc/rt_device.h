@@ -160,6 +160,9 @@ struct TraceParams {
     int heavy_static;         // 1: heavy-list tickets assigned statically (frames issued alone)
     int unlit_skip;           // fast frames: no shadow segments for a light whose phong factor is zero (1),
                               // and no phong term for it either (2)
+    int k0;                   // sample base (rt_accumulate), 1-spp launches only: the launch's one sample is the
+                              // frame's sample k0 -- its sub-pixel offset, and whether it is "sample 0" (hit ids;
+                              // no debug pixel with k0 > 0); 0 in every other launch
 };
 
 // query_kernel's arguments (rt_query): n caller-supplied rays (origin / dir, normalised on the
@@ -220,6 +223,11 @@ hipError_t launch_ray_keys(QueryParams& Q, const rtk::KeyBox& box, unsigned long
 // The single-workgroup BVH build (A.n <= BVH_WG_LEAVES) with `lds` bytes of dynamic LDS.
 hipError_t launch_bvh_build(rtb::BvhArgs& A, bool lds_tree, size_t lds, hipStream_t st, hipEvent_t e0, hipEvent_t e1);
 size_t scene_image_bytes(const SceneView& S);   // the scene image a fast kernel's block stages in LDS
+// accum_fold_kernel (rt_accumulate): one more sample (`pass`: a 1-sample frame's raw radiance)
+// into n_px pixels' running sums, which hold n_before samples (0: they are taken as zero, not
+// read); resolve: the frame of n_before + 1 samples into rgba / radiance (each may be null).
+hipError_t launch_accum_fold(const float4* pass, float4* sum_r, float4* sum_c, int n_px, int n_before, bool resolve,
+                             uint32_t* rgba, float4* radiance, hipStream_t st, hipEvent_t e0, hipEvent_t e1);
 void launch_unpermute(const uint32_t* g, uint32_t* out, int W, int H, int N, int rows_max, hipStream_t st);
 void launch_profile_marker(int tag, hipStream_t st);
 void launch_copy_gate(const unsigned* flag, unsigned long long max_ticks, hipStream_t st);

@@ -165,6 +165,22 @@ struct rt_scene {
     int ranks_per_device = 1;                    // > 1: virtual ranks of rt_scene_set_devices share this device
     unsigned inst_gen = 1;                       // generation of the host instance array (set_trans bumps it)
     unsigned shape_gen = 0;                      // generation n_real / fdepth were computed for
+    // generations of what else decides a sample (rt_accumulate's staleness test): the camera
+    // (rt_camera_*), the environment (rt_env_set) and the atlas (rt_scene_set_atlas)
+    unsigned cam_gen = 1, env_gen = 1, atlas_gen = 1;
+    // rt_accumulate: the scene-owned running sums of `n` samples (raw and clamped per sample), the
+    // pass buffer a sample is traced into, sample 0's kept hit ids, and what the first sample saw
+    // (generations, the textures flag).  Allocated on first use (px pixels), freed with the scene;
+    // rt_render and rt_update_scene never touch them.
+    struct Accum {
+        float4 *d_sum_r = nullptr, *d_sum_c = nullptr, *d_pass = nullptr;
+        int32_t *d_hit_inst = nullptr, *d_hit_tri = nullptr;
+        size_t px = 0;
+        int n = 0, restarts = 0;
+        unsigned inst_gen = 0, cam_gen = 0, env_gen = 0, atlas_gen = 0;
+        int textures = 0;
+        void release() { rti::dfree(d_sum_r); rti::dfree(d_sum_c); rti::dfree(d_pass); rti::dfree(d_hit_inst); rti::dfree(d_hit_tri); px = 0; }
+    } accum;
     static constexpr int MAX_SLOTS = RT_MAX_SLOTS;
     rti::FrameSlot slots[MAX_SLOTS];             // slots[0, n_slots) are in rotation (FrameSlot)
     int n_slots = 1, cur_slot = 0;

@@ -35,6 +35,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "rt_accum.h"
 #include "rt_bvh.h"
 #include "rt_device.h"
 #include "rt_math.h"
@@ -1524,7 +1525,7 @@ __global__ __launch_bounds__(TRACE_BLOCK_P) void trace_kernel(TraceParams P_arg,
         const GroupLane gl = group_lane(g);
         const int sub_g = gl.sub, px = gl.px, py = gl.py;
         const bool valid = gl.valid;
-        const bool me = valid && sub_g == 0 && px == P.dbg_x && py == P.dbg_y;
+        const bool me = valid && sub_g == 0 && px == P.dbg_x && py == P.dbg_y;   // (no debug pixel with a sample base: launch_trace)
         V4 sum_c = v4(0, 0, 0, 0), sum_r = v4(0, 0, 0, 0);
         float acc = 0.0f;                                      // RT_LDS_SUM: this lane's (pixel, channel) sum
         const unsigned long long g_t0 = CYC ? __builtin_amdgcn_s_memrealtime() : 0, g_q0 = wc.wq;
@@ -1536,8 +1537,13 @@ __global__ __launch_bounds__(TRACE_BLOCK_P) void trace_kernel(TraceParams P_arg,
             const int k = rd * L + sub_g;
             const bool act = valid && k < P.spp;
             Ray r0{v3(0, 0, 0), v3(0, 0, 1)};
+            // The frame's sample: k, and in 1-spp launches (L = 1: k = 0) the sample base, which
+            // rt_accumulate's passes set.  Read under the uniform branch only (the asm keeps it
+            // there): launches of more samples, the headline's among them, pay a scalar compare.
+            int kg = k;
+            if (L == 1) { kg = kparams().k0; asm volatile("" : "+v"(kg)); }
             if (act) {
-                const float2 o = spp_offset_dev(k);
+                const float2 o = spp_offset_dev(kg);
                 DCamera cam = kld(P.cam);
                 cam.W = fresh_s(cam.W); cam.H = fresh_s(cam.H); cam.near_ = fresh_s(cam.near_);
                 r0 = camera_at(cam, (float)px + o.x, (float)py + o.y);
@@ -1548,7 +1554,7 @@ __global__ __launch_bounds__(TRACE_BLOCK_P) void trace_kernel(TraceParams P_arg,
             // radiance is the integrator's initial zero (scene.cu:124-126) and the group's
             // outputs are zeros (and -1 hit ids).  Most groups of the reference scenes are sky.
             if (FT && !STATS && !PROF && !MULTI && SV().use_bvh && SV().n_leaf > 0 && !kparams().gsky && !__ballot(ft_root_hit(SV(), bv, act, r0))) {
-                if (act && k == 0) {
+                if (act && kg == 0) {
                     int gq = g;                                // (the pixel recomputed here: its two store
                     asm volatile("" : "+s"(gq));               // addresses are not held in VGPRs over the group)
                     const int op = group_lane(gq).pix;
@@ -1561,12 +1567,9 @@ __global__ __launch_bounds__(TRACE_BLOCK_P) void trace_kernel(TraceParams P_arg,
             // test); occupancy counters are taken over live groups' queries only
             if (PROF && FT) wc.live = __ballot(ft_root_hit(SV(), bv, act, r0)) != 0;
             const unsigned long long cs = CYC ? __builtin_amdgcn_s_memtime() : 0;
-            V4 c = trace_sample<NS, STATS, PARK, TEX, FT, AXIS, PROF, BRUTE, PART>(S, bv, act, r0, me && rd == 0, act && k == 0, g, wc,
+            V4 c = trace_sample<NS, STATS, PARK, TEX, FT, AXIS, PROF, BRUTE, PART>(S, bv, act, r0, me && rd == 0, act && kg == 0, g, wc,
                                                  park, nq);
             if (CYC) wc.cyc_sample += __builtin_amdgcn_s_memtime() - cs;
-            auto clamp1 = [](V4 v) {                           // raytracer.cu:37-40
-                return v4(v.x > 1.0f ? 1.0f : v.x, v.y > 1.0f ? 1.0f : v.y, v.z > 1.0f ? 1.0f : v.z, v.w > 1.0f ? 1.0f : v.w);
-            };
             // in-order reduction over samples (ds_bpermute: the LDS pipe has room, the VALU
             // does not -- a DPP row-shift form measured 4% slower).  Each lane clamps its own
             // sample before the exchange (the same bits the leader would compute), and the raw
@@ -1578,7 +1581,7 @@ __global__ __launch_bounds__(TRACE_BLOCK_P) void trace_kernel(TraceParams P_arg,
             const int spp_n = Pr.spp;
             const GroupLane ga = group_lane(g);                // after the trace (not held across it)
             const int bb = ga.base, sub_a = ga.sub;
-            const V4 cc = clamp1(c);
+            const V4 cc = rta::clamp1(c);                      // raytracer.cu:37-40 (rt_accum.h)
             if (L == 8) {                               // spp = 8: all permutes in one LDS round trip
                 V4 v[8];
 #pragma unroll
@@ -1655,13 +1658,10 @@ __global__ __launch_bounds__(TRACE_BLOCK_P) void trace_kernel(TraceParams P_arg,
             KTP& P = kparams();
             const int p = go.pix;
             const float inv = (float)P.spp;
-            // mean = sum / spp (raytracer.cu's per-sample colour, build-defined spp average);
-            // for spp = 2^k, x * 2^-k is the same correctly rounded value as x / 2^k
-            auto mean = [&](float x) { return P.spp_recip != 0.0f ? x * P.spp_recip : x / inv; };
-            const float mr = mean(sum_c.x), mg = mean(sum_c.y), mb = mean(sum_c.z), ma = mean(sum_c.w);
-            // Color(float r, g, b, a) truncation to uint8 and to_encoding (color.h:41-42, color.cu:23-26)
-            const uint32_t enc = ((uint32_t)(uint8_t)((float)255 * mr) << 24) + ((uint32_t)(uint8_t)((float)255 * mg) << 16) +
-                                 ((uint32_t)(uint8_t)((float)255 * mb) << 8) + (uint32_t)(uint8_t)((float)255 * ma);
+            // mean = sum / spp and Color's truncation to bytes: rt_accum.h, shared with the fold
+            // kernel of rt_accumulate
+            auto mean = [&](float x) { return rta::mean(x, P.spp_recip, inv); };
+            const uint32_t enc = rta::pack(v4(mean(sum_c.x), mean(sum_c.y), mean(sum_c.z), mean(sum_c.w)));
             if (wide) { w_enc = enc; w_pix = p; }
             else if (P.rgba) P.rgba[p] = enc;
             if (P.radiance) P.radiance[p] = make_float4(mean(sum_r.x), mean(sum_r.y), mean(sum_r.z), mean(sum_r.w));
@@ -1993,7 +1993,7 @@ __global__ __launch_bounds__(SKY_THREADS) void sky_kernel(TraceParams P, SceneVi
         bool rlive = false;
         if (in && !csky) {
             const int gy = (int)udiv((unsigned)gl, P.div_ngx), gx = gl - gy * P.n_gx;
-            const float2 o = spp_offset_dev(0);
+            const float2 o = spp_offset_dev(P.k0);
             const Ray rr = camera_at(P.cam, (float)(gx * P.gw) + o.x, (float)(P.row0 + gy * P.gh * P.row_step) + o.y);
             rlive = root_hit(true, rr);
         }
@@ -2029,8 +2029,8 @@ __global__ __launch_bounds__(SKY_THREADS) void sky_kernel(TraceParams P, SceneVi
         const int px = gx * P.gw + qx, pr = gy * P.gh + qy;
         if (!(px < P.W && pr < P.n_rows)) return;
         const int pix_index = P.compact ? pr * P.W + px : (P.row0 + pr * P.row_step) * P.W + px;
-        if (P.hit_inst) P.hit_inst[pix_index] = -1;
-        if (P.hit_tri) P.hit_tri[pix_index] = -1;
+        if (P.hit_inst && P.k0 == 0) P.hit_inst[pix_index] = -1;   // (sample 0's hit ids)
+        if (P.hit_tri && P.k0 == 0) P.hit_tri[pix_index] = -1;
         if (P.rgba) P.rgba[pix_index] = 0u;                   // to_encoding of Color(0, 0, 0, 0)
         if (P.radiance) P.radiance[pix_index] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     };
@@ -2059,7 +2059,7 @@ __global__ __launch_bounds__(SKY_THREADS) void sky_kernel(TraceParams P, SceneVi
         const bool act = valid && lane_ok;
         Ray r0{v3(0, 0, 0), v3(0, 0, 1)};
         if (act) {
-            const float2 o = spp_offset_dev(sub_g);            // the trace kernel's own offsets
+            const float2 o = spp_offset_dev(P.k0 + sub_g);     // the trace kernel's own offsets
             r0 = camera_at(P.cam, (float)px + o.x, (float)py + o.y);
         }
         const bool sky = __ballot(root_hit(act, r0)) == 0;
@@ -2523,6 +2523,35 @@ __global__ __launch_bounds__(256) void unpermute_kernel(const uint32_t* __restri
     out[i] = g[((size_t)(y % N) * rows_max + y / N) * W + x];         // frame row y = slice y % N, row y / N
 }
 
+// rt_accumulate's fold: pixel i's running sums take one more sample, the raw radiance `pass`
+// of a 1-sample frame (rta::fold), and with `resolve` (uniform: the call's last pass) the frame of
+// n_before + 1 samples is written (rta::resolve_*: the trace kernel's mean and truncation).
+// n_before = 0: the sums start at zero and are not read (0 + c_0 is still added: -0 becomes +0,
+// as in the trace kernel's own sum).  One pixel per lane, every access but the RGBA word 16 bytes
+// wide and contiguous over the wave; per pixel 16 B of the pass and 32 B of sums read, 32 B
+// written, plus 4 + 16 B resolved: 80 to 100 B, no reuse -- bandwidth-bound.  No LDS, no atomics.
+constexpr int FOLD_BLOCK = 256;
+__global__ __launch_bounds__(FOLD_BLOCK) void accum_fold_kernel(const float4* __restrict__ pass, float4* __restrict__ sum_r,
+                                                                float4* __restrict__ sum_c, int n_px, int n_before, int resolve,
+                                                                uint32_t* __restrict__ rgba, float4* __restrict__ radiance) {
+    const long long i = (long long)blockIdx.x * FOLD_BLOCK + threadIdx.x;   // (n_px may be within a block of 2^31)
+    if (i >= n_px) return;                                                   // the tail block
+    const float4 r = pass[i];
+    float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = a;
+    if (n_before > 0) { a = sum_r[i]; b = sum_c[i]; }
+    V4 sr = v4(a.x, a.y, a.z, a.w), sc = v4(b.x, b.y, b.z, b.w);
+    rta::fold(sr, sc, v4(r.x, r.y, r.z, r.w));
+    sum_r[i] = make_float4(sr.x, sr.y, sr.z, sr.w);
+    sum_c[i] = make_float4(sc.x, sc.y, sc.z, sc.w);
+    if (resolve) {
+        if (rgba) rgba[i] = rta::resolve_rgba(sc, n_before + 1);
+        if (radiance) {
+            const V4 m = rta::resolve_radiance(sr, n_before + 1);
+            radiance[i] = make_float4(m.x, m.y, m.z, m.w);
+        }
+    }
+}
+
 extern "C" {   // (unmangled names: profiler traces are searched for them, tools/pmc_step.py)
 // Profile marker (rt_profile_marker): an empty kernel whose grid (64 x tag threads) tells a
 // rocprofv3 trace where a caller's timed region begins and ends (tools/pmc_step.py).
@@ -2652,6 +2681,15 @@ hipError_t launch_bvh_build(BvhArgs& A, bool lds_tree, size_t lds, hipStream_t s
     if (lds > 64 * 1024) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     void* args[] = {&A};
     return hipExtLaunchKernel(fn, dim3(1), dim3(BVH_WG_THREADS), args, lds, st, e0, e1, 0);
+}
+
+hipError_t launch_accum_fold(const float4* pass, float4* sum_r, float4* sum_c, int n_px, int n_before, bool resolve,
+                             uint32_t* rgba, float4* radiance, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
+    if (n_px <= 0) return hipSuccess;
+    int res = resolve ? 1 : 0;
+    void* args[] = {&pass, &sum_r, &sum_c, &n_px, &n_before, &res, &rgba, &radiance};
+    return hipExtLaunchKernel((const void*)accum_fold_kernel, dim3((unsigned)((n_px + FOLD_BLOCK - 1) / FOLD_BLOCK)), dim3(FOLD_BLOCK),
+                              args, 0, st, e0, e1, 0);
 }
 
 void launch_unpermute(const uint32_t* g, uint32_t* out, int W, int H, int N, int rows_max, hipStream_t st) {

@@ -16,6 +16,7 @@
 #include <string>
 #include <vector>
 
+#include "rt_accum.h"
 #include "rt_internal.h"
 
 using namespace rtm;
@@ -481,6 +482,18 @@ int ensure_spp(rt_scene* s, int spp) {
     return RT_OK;
 }
 
+// Device staging of host_outputs frames (rgba, radiance, hit_inst, hit_tri), whole-frame sized.
+int ensure_out_staging(rt_scene* s) {
+    const size_t px = (size_t)s->h.cam.W * s->h.cam.H;
+    if (s->d_out_px >= px) return RT_OK;
+    for (auto& p : s->d_out) dfree(p);
+    s->d_out_px = 0;
+    HIPCHK(hipMalloc(&s->d_out[0], px * 4)); HIPCHK(hipMalloc(&s->d_out[1], px * 16));
+    HIPCHK(hipMalloc(&s->d_out[2], px * 4)); HIPCHK(hipMalloc(&s->d_out[3], px * 4));
+    s->d_out_px = px;
+    return RT_OK;
+}
+
 int build_bvh(rt_scene* s, hipStream_t st, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr) {
     FrameSlot& f = s->cur();
     if (s->n_leaf == 0) {
@@ -578,6 +591,7 @@ struct TraceRequest {
     hipEvent_t e0 = nullptr, e1 = nullptr;                     // timestamps taken by the dispatches themselves
     bool prof = false;                                         // the fast kernel's profiling variant (M_PROF)
     unsigned* gdur = nullptr;                                  // per-group durations (rt_profile_groups)
+    int k0 = 0;                                                // sample base (rt_accumulate; TraceParams::k0)
     int* geo = nullptr;                                        // out: {n_groups, gw, gh, n_gx}
 };
 
@@ -596,7 +610,9 @@ int launch_trace(rt_scene* s, const rt_render_opts& o, const TraceRequest& q) {
     P.cam = h.d_cam; P.dist_atten = h.dist_atten; P.ambience = h.ambience;
     P.W = h.cam.W; P.H = h.cam.H; P.row0 = o.row0; P.row_step = o.row_step; P.n_rows = g.n_rows;
     P.compact = o.compact; P.spp = o.spp; P.depth = h.depth;
-    P.spp_recip = (o.spp & (o.spp - 1)) == 0 ? 1.0f / (float)o.spp : 0.0f;
+    P.spp_recip = rta::mean_recip(o.spp);
+    if (q.k0 != 0 && (o.spp != 1 || q.dbg)) return fail(RT_ERR_ARG, "a sample base needs a 1-spp launch without a debug pixel");
+    P.k0 = q.k0;
     P.spp_off = s->d_spp;
     P.rgba = q.rgba; P.radiance = reinterpret_cast<float4*>(o.radiance); P.hit_inst = o.hit_inst; P.hit_tri = o.hit_tri;
     P.stats = (q.want_stats || q.prof) ? s->d_stats : nullptr; P.dbg_log = q.dbg; P.dbg_x = q.dbg_x; P.dbg_y = q.dbg_y;
@@ -763,6 +779,7 @@ rt_scene::~rt_scene() {
     dfree(d_mesh_box); dfree(d_spp); dfree(d_stats); dfree(d_canvas); dfree(d_dbg);
     for (auto& p : d_out) dfree(p);
     dfree(q_dev); hfree(q_host); dfree(qo_dev);
+    accum.release();
     for (auto& e : ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : tev) (void)hipEventDestroy(e);
     for (auto& f : slots) f.release();
@@ -1039,6 +1056,7 @@ int rt_camera_set(rt_scene* s, const float* pos, const float* q) {
     if (pos) s->h.cam.pos = v3(pos[0], pos[1], pos[2]);
     if (q) s->h.cam.rot = Q{q[0], q[1], q[2], q[3]};
     s->h.update_camera_basis();
+    s->cam_gen++;
     return RT_OK;
 }
 int rt_camera_translate(rt_scene* s, const float* d) {           // entity.h:53-56: translate_global(vec_to_local(dp))
@@ -1046,6 +1064,7 @@ int rt_camera_translate(rt_scene* s, const float* d) {           // entity.h:53-
     if (!d) return fail(RT_ERR_ARG, "null argument");
     s->h.cam.pos = s->h.cam.pos + qrot(s->h.cam.rot, v3(d[0], d[1], d[2]));
     s->h.update_camera_basis();
+    s->cam_gen++;
     return RT_OK;
 }
 int rt_camera_rotate(rt_scene* s, const float* dq) {             // entity.h:63-65: o = dr * o
@@ -1053,6 +1072,7 @@ int rt_camera_rotate(rt_scene* s, const float* dq) {             // entity.h:63-
     if (!dq) return fail(RT_ERR_ARG, "null argument");
     s->h.cam.rot = qmul(Q{dq[0], dq[1], dq[2], dq[3]}, s->h.cam.rot);
     s->h.update_camera_basis();
+    s->cam_gen++;
     return RT_OK;
 }
 int rt_camera_axes(const rt_scene* s, float* r, float* u, float* f) {
@@ -1069,6 +1089,7 @@ int rt_env_set(rt_scene* s, const float* amb, const float* da, int depth) {
     if (amb) s->h.ambience = v4(amb[0], amb[1], amb[2], amb[3]);
     if (da) s->h.dist_atten = v3(da[0], da[1], da[2]);
     s->h.depth = depth;
+    s->env_gen++;
     return RT_OK;
 }
 
@@ -1078,6 +1099,7 @@ int rt_scene_set_atlas(rt_scene* s, const uint8_t* rgba8, int w, int h) {
     s->h.atlas_rgba.assign(rgba8, rgba8 + (size_t)w * h * 4);
     s->h.atlas_w = w; s->h.atlas_h = h;
     s->atlas_dirty = true;
+    s->atlas_gen++;
     return RT_OK;
 }
 int rt_scene_load_atlas(rt_scene* s, const char* path) {
@@ -1153,12 +1175,7 @@ int rt_render(rt_scene* s, const rt_render_opts* o, rt_stats* stats) {
     const size_t n_rows = (H > (size_t)o->row0) ? (H - o->row0 + o->row_step - 1) / o->row_step : 0;
     const size_t out_px = o->compact ? n_rows * W : W * H;
     if (o->host_outputs) {                                   // stage through device buffers
-        if (s->d_out_px < W * H) {
-            for (auto& p : s->d_out) dfree(p);
-            HIPCHK(hipMalloc(&s->d_out[0], W * H * 4)); HIPCHK(hipMalloc(&s->d_out[1], W * H * 16));
-            HIPCHK(hipMalloc(&s->d_out[2], W * H * 4)); HIPCHK(hipMalloc(&s->d_out[3], W * H * 4));
-            s->d_out_px = W * H;
-        }
+        if ((r = ensure_out_staging(s)) != RT_OK) return r;
         oo.rgba = o->rgba ? (uint32_t*)s->d_out[0] : nullptr;
         oo.radiance = o->radiance ? (float*)s->d_out[1] : nullptr;
         oo.hit_inst = o->hit_inst ? (int32_t*)s->d_out[2] : nullptr;
@@ -1364,6 +1381,148 @@ int rt_frame_work(rt_scene* s, const rt_render_opts* o, rt_work* w) {
         w->hist_pair_steps[i] = v[PROF_HIST_PAIR + i];
         w->hist_leaf_visits[i] = v[PROF_HIST_LEAF + i];
     }
+    return RT_OK;
+}
+
+void rt_accum_opts_default(rt_accum_opts* o) {
+    if (!o) return;
+    memset(o, 0, sizeof *o);
+    o->samples = 1; o->use_bvh = 1; o->rebuild_bvh = 1;
+}
+
+namespace {
+constexpr int ACCUM_MAX_SAMPLES = 65536;
+
+// Has anything that decides a sample changed since the accumulation's first one?
+bool accum_stale(const rt_scene* s, int textures) {
+    const rt_scene::Accum& a = s->accum;
+    return a.n > 0 && (a.inst_gen != s->inst_gen || a.cam_gen != s->cam_gen || a.env_gen != s->env_gen ||
+                       a.atlas_gen != s->atlas_gen || a.textures != textures);
+}
+void accum_drop(rt_scene* s) {
+    if (s->accum.n > 0) s->accum.restarts++;
+    s->accum.n = 0;
+}
+// The scene-owned buffers for the canvas; a failed allocation leaves none of them (and no samples).
+int ensure_accum(rt_scene* s) {
+    rt_scene::Accum& a = s->accum;
+    const size_t px = std::max<size_t>(1, (size_t)s->h.cam.W * s->h.cam.H);
+    if (a.px >= px) return RT_OK;
+    a.release(); a.n = 0;
+    if (hipMalloc((void**)&a.d_sum_r, px * sizeof(float4)) != hipSuccess || hipMalloc((void**)&a.d_sum_c, px * sizeof(float4)) != hipSuccess ||
+        hipMalloc((void**)&a.d_pass, px * sizeof(float4)) != hipSuccess || hipMalloc((void**)&a.d_hit_inst, px * sizeof(int32_t)) != hipSuccess ||
+        hipMalloc((void**)&a.d_hit_tri, px * sizeof(int32_t)) != hipSuccess) {
+        const std::string why = hipGetErrorString(hipGetLastError());
+        a.release();
+        return fail(RT_ERR_HIP, "rt_accumulate: no memory for the sums of " + std::to_string(px) + " pixels: " + why);
+    }
+    a.px = px;
+    return RT_OK;
+}
+}  // namespace
+
+// Progressive refinement (rt_amd.h): a side entry like rt_frame_work.  Sample k of the
+// accumulation is a 1-spp trace launch with sample base k into the pass buffer, then one fold
+// (accum_fold_kernel); the call's last fold resolves the frame.
+int rt_accumulate(rt_scene* s, const rt_accum_opts* o, int* n_samples) {
+    CHECK_FINISHED(s);
+    if (!o) return fail(RT_ERR_ARG, "null options");
+    if (o->samples < 1) return fail(RT_ERR_ARG, "rt_accumulate: samples >= 1 required");
+    if (!(o->rgba || o->radiance || o->hit_inst || o->hit_tri)) return fail(RT_ERR_ARG, "rt_accumulate: no output requested");
+    const int textures = o->textures ? 1 : 0;
+    const bool fresh = o->restart || accum_stale(s, textures);
+    if ((long long)(fresh ? 0 : s->accum.n) + o->samples > ACCUM_MAX_SAMPLES)
+        return fail(RT_ERR_LIMIT, "rt_accumulate: more than 65536 samples held (rt_accumulate_reset starts again)");
+    if (s->multi) return fail(RT_ERR_STATE, "rt_accumulate: not on a scene split by rt_scene_set_devices");
+    int r;
+    if ((r = upload(s)) != RT_OK) return r;
+    HIPCHK(hipSetDevice(s->device));
+    const size_t px = (size_t)s->h.cam.W * s->h.cam.H;
+    if (px > (size_t)INT32_MAX) return fail(RT_ERR_LIMIT, "frame larger than 2^31 pixels");
+    if (textures && s->h.atlas_rgba.empty())
+        return fail(RT_ERR_STATE, "textured rendering needs an atlas: rt_scene_load_atlas / rt_scene_set_atlas");
+    if (fresh) accum_drop(s);
+    if ((r = ensure_accum(s)) != RT_OK) return r;
+    if (o->host_outputs && (r = ensure_out_staging(s)) != RT_OK) return r;
+    rt_scene::Accum& a = s->accum;
+    // frames in flight (any slot) first; the BVH at most once, for every sample of the call
+    if ((r = begin_side_entry(s, 1, o->use_bvh && (o->rebuild_bvh || !s->cur().bvh_valid))) != RT_OK) return r;
+    hipStream_t st = sstream(s);
+    uint32_t* d_rgba = !o->rgba ? nullptr : o->host_outputs ? (uint32_t*)s->d_out[0] : o->rgba;
+    float4* d_rad = !o->radiance ? nullptr : o->host_outputs ? (float4*)s->d_out[1] : reinterpret_cast<float4*>(o->radiance);
+    rt_render_opts ro;
+    rt_render_opts_default(&ro);
+    ro.use_bvh = o->use_bvh; ro.textures = textures;
+    ro.radiance = reinterpret_cast<float*>(a.d_pass);
+    for (int i = 0; i < o->samples; i++) {
+        if (a.n == 0) {                                       // what this accumulation's samples see
+            a.inst_gen = s->inst_gen; a.cam_gen = s->cam_gen; a.env_gen = s->env_gen; a.atlas_gen = s->atlas_gen;
+            a.textures = textures;
+        }
+        ro.hit_inst = a.n == 0 ? a.d_hit_inst : nullptr;      // sample 0's primary hit, kept
+        ro.hit_tri = a.n == 0 ? a.d_hit_tri : nullptr;
+        TraceRequest q;
+        q.stream = st; q.k0 = a.n;                            // (no RGBA8 of the pass: the fold resolves)
+        const int before = a.n;
+        a.n = 0;                                              // a failed launch leaves no samples, not stale sums
+        if ((r = launch_trace(s, ro, q)) != RT_OK) return r;
+        HIPCHK(launch_accum_fold(a.d_pass, a.d_sum_r, a.d_sum_c, (int)px, before, i == o->samples - 1, d_rgba, d_rad, st, nullptr, nullptr));
+        a.n = before + 1;
+    }
+    const bool host = o->host_outputs != 0;
+    const hipMemcpyKind kind = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    if (!host) {                                              // the kept hit ids into the caller's device arrays
+        if (o->hit_inst) HIPCHK(hipMemcpyAsync(o->hit_inst, a.d_hit_inst, px * 4, kind, st));
+        if (o->hit_tri) HIPCHK(hipMemcpyAsync(o->hit_tri, a.d_hit_tri, px * 4, kind, st));
+    }
+    if ((r = end_frame(s, st)) != RT_OK) return r;
+    HIPCHK(hipStreamSynchronize(st));
+    if (host) {
+        if (o->rgba) HIPCHK(hipMemcpy(o->rgba, d_rgba, px * 4, kind));
+        if (o->radiance) HIPCHK(hipMemcpy(o->radiance, d_rad, px * 16, kind));
+        if (o->hit_inst) HIPCHK(hipMemcpy(o->hit_inst, a.d_hit_inst, px * 4, kind));
+        if (o->hit_tri) HIPCHK(hipMemcpy(o->hit_tri, a.d_hit_tri, px * 4, kind));
+    }
+    if (n_samples) *n_samples = a.n;
+    return RT_OK;
+}
+
+int rt_accumulate_reset(rt_scene* s) {
+    CHECK_SCENE(s);
+    accum_drop(s);
+    return RT_OK;
+}
+
+int rt_accumulate_info(const rt_scene* s, int32_t* out4) {
+    CHECK_SCENE(s);
+    if (!out4) return fail(RT_ERR_ARG, "null argument");
+    out4[0] = s->accum.n; out4[1] = s->h.cam.W; out4[2] = s->h.cam.H; out4[3] = s->accum.restarts;
+    return RT_OK;
+}
+
+// Profiling aid (tools/accum_bench.py, not part of rt_amd.h's stable surface): the fold kernel
+// alone over buffers of the scene's canvas size, `reps` launches timed by the dispatches' own
+// events; *ms = the mean of all but the first.  The scene's accumulation is not touched.
+int rt_accum_fold_time(rt_scene* s, int reps, int resolve, double* ms) {
+    CHECK_FINISHED(s);
+    if (reps < 1 || !ms) return fail(RT_ERR_ARG, "bad arguments");
+    int r;
+    if ((r = begin_side_entry(s, 1, false)) != RT_OK) return r;
+    const size_t px = (size_t)s->h.cam.W * s->h.cam.H;
+    if (px == 0 || px > (size_t)INT32_MAX) return fail(RT_ERR_LIMIT, "frame of no pixels, or of more than 2^31");
+    DevBuf<float4> pass, sr, sc, rad;
+    DevBuf<uint32_t> rgba;
+    HIPCHK(pass.alloc(px)); HIPCHK(sr.alloc(px)); HIPCHK(sc.alloc(px)); HIPCHK(rad.alloc(px)); HIPCHK(rgba.alloc(px));
+    hipStream_t st = sstream(s);
+    HIPCHK(hipMemsetAsync(pass.p, 0, px * sizeof(float4), st));
+    float total = 0;
+    for (int i = 0; i < reps; i++) {
+        HIPCHK(launch_accum_fold(pass.p, sr.p, sc.p, (int)px, i, resolve != 0, rgba.p, rad.p, st, s->ev[0], s->ev[1]));
+        HIPCHK(hipEventSynchronize(s->ev[1]));
+        float t = 0; HIPCHK(hipEventElapsedTime(&t, s->ev[0], s->ev[1]));
+        if (i > 0 || reps == 1) total += t;
+    }
+    *ms = total / (reps > 1 ? reps - 1 : 1);
     return RT_OK;
 }
 

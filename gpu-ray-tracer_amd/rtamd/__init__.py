@@ -44,6 +44,7 @@ SYMBOLS = [
     "rt_scene_set_devices", "rt_profile_marker", "rt_host_alloc", "rt_host_free", "rt_copy_to_host_async",
     "rt_copy_engines_warm", "rt_scene_last_trace", "rt_query_opts_default", "rt_query",
     "rt_query_set_order", "rt_query_last",
+    "rt_accum_opts_default", "rt_accumulate", "rt_accumulate_reset", "rt_accumulate_info",
 ]
 RT_QUERY_ORDER_CALLER, RT_QUERY_ORDER_SORTED = 0, 1
 
@@ -61,6 +62,13 @@ class RenderOpts(ctypes.Structure):
                 ("radiance", ctypes.c_void_p), ("hit_inst", ctypes.c_void_p), ("hit_tri", ctypes.c_void_p),
                 ("sync", ctypes.c_int), ("host_outputs", ctypes.c_int), ("timing", ctypes.c_int),
                 ("textures", ctypes.c_int)]
+
+
+class AccumOpts(ctypes.Structure):
+    _fields_ = [("samples", ctypes.c_int), ("use_bvh", ctypes.c_int), ("rebuild_bvh", ctypes.c_int),
+                ("textures", ctypes.c_int), ("restart", ctypes.c_int), ("host_outputs", ctypes.c_int),
+                ("rgba", ctypes.c_void_p), ("radiance", ctypes.c_void_p), ("hit_inst", ctypes.c_void_p),
+                ("hit_tri", ctypes.c_void_p)]
 
 
 class QueryOpts(ctypes.Structure):
@@ -164,6 +172,12 @@ def lib():
     L.rt_query_opts_default.argtypes = [ctypes.POINTER(QueryOpts)]
     L.rt_query_opts_default.restype = None
     L.rt_query.argtypes = [vp, ctypes.POINTER(QueryOpts), ctypes.POINTER(Stats)]
+    if hasattr(L, "rt_accumulate"):             # (absent from libraries before progressive refinement: A/B runs)
+        L.rt_accum_opts_default.argtypes = [ctypes.POINTER(AccumOpts)]
+        L.rt_accum_opts_default.restype = None
+        L.rt_accumulate.argtypes = [vp, ctypes.POINTER(AccumOpts), ctypes.POINTER(ip)]
+        L.rt_accumulate_reset.argtypes = [vp]
+        L.rt_accumulate_info.argtypes = [vp, vp]
     if hasattr(L, "rt_query_set_order"):        # (absent from libraries before the coherence sort: A/B runs)
         L.rt_query_set_order.argtypes = [vp, ip]
         L.rt_query_last.argtypes = [vp, vp, vp, vp, ctypes.c_int64]
@@ -482,6 +496,60 @@ class Scene:
         st = Stats()
         _check(lib().rt_render(self._h, ctypes.byref(o), ctypes.byref(st) if stats else None))
         return st.as_dict() if stats else None
+
+    # ---- progressive refinement (rt_accumulate) ----
+    def _accum_opts(self, samples, restart, use_bvh, rebuild_bvh, textures):
+        o = AccumOpts()
+        lib().rt_accum_opts_default(ctypes.byref(o))
+        o.samples, o.restart, o.use_bvh, o.rebuild_bvh, o.textures = int(samples), int(restart), int(use_bvh), int(rebuild_bvh), int(textures)
+        return o
+
+    def accumulate(self, samples=1, restart=False, use_bvh=True, rebuild_bvh=True, textures=False, want=("rgba",)):
+        """Add `samples` samples per pixel to the scene's running sums and return the frame of all
+        the samples held, as host numpy arrays, plus "n", their number: the frame render(spp=n)
+        returns.  The sums start again by themselves when the camera, an instance, the environment,
+        the atlas or `textures` changed (rt_accumulate); hit_inst / hit_tri are sample 0's."""
+        W, H = self.width, self.height
+        o = self._accum_opts(samples, restart, use_bvh, rebuild_bvh, textures)
+        o.host_outputs = 1
+        out = {}
+        if "rgba" in want:
+            out["rgba"] = np.zeros((H, W), np.uint32)
+            o.rgba = _ptr(out["rgba"])
+        if "radiance" in want:
+            out["radiance"] = np.zeros((H, W, 4), np.float32)
+            o.radiance = _ptr(out["radiance"])
+        if "hit_inst" in want:
+            out["hit_inst"] = np.full((H, W), -1, np.int32)
+            o.hit_inst = _ptr(out["hit_inst"])
+        if "hit_tri" in want:
+            out["hit_tri"] = np.full((H, W), -1, np.int32)
+            o.hit_tri = _ptr(out["hit_tri"])
+        n = ctypes.c_int(0)
+        _check(lib().rt_accumulate(self._h, ctypes.byref(o), ctypes.byref(n)))
+        out["n"] = n.value
+        return out
+
+    def accumulate_device(self, samples=1, restart=False, use_bvh=True, rebuild_bvh=True, textures=False,
+                          rgba_ptr=None, radiance_ptr=None, hit_inst_ptr=None, hit_tri_ptr=None):
+        """accumulate into caller-owned DEVICE buffers (e.g. torch tensors' data_ptr()), complete on
+        return; returns the number of samples held."""
+        o = self._accum_opts(samples, restart, use_bvh, rebuild_bvh, textures)
+        o.rgba, o.radiance, o.hit_inst, o.hit_tri = rgba_ptr, radiance_ptr, hit_inst_ptr, hit_tri_ptr
+        n = ctypes.c_int(0)
+        _check(lib().rt_accumulate(self._h, ctypes.byref(o), ctypes.byref(n)))
+        return n.value
+
+    def accumulate_reset(self):
+        """Drop the accumulated samples (rt_accumulate_reset)."""
+        _check(lib().rt_accumulate_reset(self._h))
+
+    @property
+    def accumulated(self):
+        """(samples held, W, H, restarts so far) (rt_accumulate_info)."""
+        a = np.zeros(4, np.int32)
+        _check(lib().rt_accumulate_info(self._h, _ptr(a)))
+        return tuple(int(x) for x in a)
 
     def frame_work(self, spp=1, row0=0, row_step=1, compact=True, want_rgba=False):
         """What the fast kernels do for this frame (rt_frame_work): queries issued after the

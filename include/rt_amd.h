@@ -208,6 +208,45 @@ typedef struct rt_work {
  * ignored: the call runs on the scene's own stream and returns when the frame is done. */
 int rt_frame_work(rt_scene* s, const rt_render_opts* opts, rt_work* work);
 
+/* ---- progressive refinement: samples accumulated across calls ----
+ * (still ABI 5: additive.)  The reference has no counterpart: its update_scene traces one sample
+ * per pixel and starts from nothing every frame.  An interactive caller shows the 1-spp frame at
+ * once and, while nothing moves, adds samples redraw by redraw: after n accumulated samples the
+ * frame is the one rt_render(spp = n) returns -- sample k's sub-pixel offset depends on k alone,
+ * and the sums take the samples in k order with the one-shot kernel's float32 additions, mean and
+ * truncation (RGBA8 equal byte for byte).
+ * Each new sample is one 1-spp trace launch (its sample index offset by the samples held) into a
+ * scene-owned pass buffer, folded into scene-owned per-pixel sums; the call's last fold writes
+ * the outputs.  A side entry, as rt_frame_work: it runs on the scene's own stream, waits for
+ * frames in flight, rotates no frame slot and returns when the outputs are complete; its
+ * launches are what rt_scene_last_trace reports.  Sums, pass buffer and kept hit ids are
+ * allocated on first use and freed with the scene (RT_ERR_HIP if they cannot be: the scene stays
+ * usable); rt_render and rt_update_scene never touch them.
+ * The accumulation starts again by itself (sample 0 is traced anew and the restart counter goes
+ * up) when anything that decides a sample changed since its first one: the camera, an instance
+ * pose, rt_env_set, the atlas, or the `textures` flag.  use_bvh / rebuild_bvh do not change the
+ * image and restart nothing. */
+typedef struct rt_accum_opts {
+    int samples;        /* samples to add in this call, >= 1 */
+    int use_bvh, rebuild_bvh, textures;   /* as rt_render_opts; the BVH is built at most once per call */
+    int restart;        /* 1: drop what is accumulated first */
+    int host_outputs;   /* as rt_render_opts */
+    uint32_t* rgba; float* radiance;      /* the frame after this call's samples; each may be NULL */
+    int32_t* hit_inst; int32_t* hit_tri;  /* sample 0's primary hit, kept since it was traced */
+} rt_accum_opts;
+/* zeros, samples = 1, use_bvh = rebuild_bvh = 1 */
+void rt_accum_opts_default(rt_accum_opts* o);
+/* n_samples (may be NULL): the samples held after the call.
+ * Checked before any device work -- RT_ERR_ARG: null opts, samples < 1, no output requested;
+ * RT_ERR_LIMIT: the call would hold more than 65536 samples; RT_ERR_STATE: a scene split by
+ * rt_scene_set_devices (and textures = 1 without an atlas).  RT_ERR_NODEV: no usable device. */
+int rt_accumulate(rt_scene* s, const rt_accum_opts* opts, int* n_samples);
+/* Drop what is accumulated (host state; the next rt_accumulate traces sample 0). */
+int rt_accumulate_reset(rt_scene* s);
+/* out4 = {samples held, W, H, restarts so far (rt_accumulate_reset, restart = 1 and the scene's
+ * own changes, each counted when it dropped at least one sample)} */
+int rt_accumulate_info(const rt_scene* s, int32_t out4[4]);
+
 /* ---- ray queries: closest hit or occlusion for caller-supplied rays ----
  * The reference has no counterpart: its cast_ray (scene.cu:42-73) is reachable only through the
  * integrator.  This entry runs that query for a batch of rays: the result of each ray is the
