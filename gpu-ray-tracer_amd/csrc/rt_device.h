@@ -110,6 +110,10 @@ struct SceneView {           // read-only scene data (HBM, L2-resident)
     int ident_all;            // every instance and mesh rotation is the identity (cube worlds)
     float prune_abs;          // distance-pruning slack M0 (< 0: pruning off), see closest_hit
     const rtm::TriAx* tri_ax; // axis-plane triangle records (fast kernel; null unless ident_all)
+    // Shadow-query occluder hints (trace_sample, closest_hit's seed; rt_plan.h: hint_*): the scene's
+    // table of HINT_SLOTS entries per instance, then its counters (hint_bytes).  Null: off.
+    // Last, so that no field the kernels read in place moves (the kernarg-layout record).
+    int* hint;
 };
 
 struct TraceParams {

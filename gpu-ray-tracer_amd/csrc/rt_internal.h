@@ -119,6 +119,8 @@ struct FrameSlot {
 #define RT_MAX_SLOTS 8
 #endif
 
+inline bool hints_default() { const char* e = getenv("RT_SHADOW_HINTS"); return !e || atoi(e) != 0; }
+
 struct rt_scene {
     rt::Scene h;
     MultiDev* multi = nullptr;                   // rt_scene_set_devices: frames split over several GPUs
@@ -134,6 +136,11 @@ struct rt_scene {
     int n_cu = 0;
     float2* d_spp = nullptr; int spp_cap = 0;
     unsigned long long* d_stats = nullptr;
+    // Shadow-query occluder hints (SceneView::hint): the scene's table and counters, shared by
+    // every frame slot (frames in flight race on it benignly: aligned word stores of a hint);
+    // null for scenes of the grid-wide BVH build.  shadow_hints: rt_scene_set_shadow_hints.
+    int* d_hint = nullptr;
+    bool shadow_hints = hints_default();         // (RT_SHADOW_HINTS=0 in the environment: off, the A/B arm)
     uint32_t* d_canvas = nullptr;
     int* d_dbg = nullptr;
     float4* d_atlas = nullptr;                   // atlas texels (float4, byte / 255)
@@ -211,5 +218,6 @@ void invalidate(rt_scene* s);     // every slot's BVH is stale (instances moved)
 int render_multi(rt_scene* s, const rt_render_opts* o, rt_stats* stats);
 void free_multi(rt_scene* s);
 void set_multi_overlap(rt_scene* s, int policy);   // the replicas of rt_scene_set_devices
+void set_multi_shadow_hints(rt_scene* s, bool on);
 
 }  // namespace rti

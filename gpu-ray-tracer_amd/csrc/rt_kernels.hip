@@ -285,7 +285,8 @@ struct Best { float time; int inst, tri; float u, v; };     // closest accepted 
 // wave-level step counts for the profiling experiment (query iterations, child-pair
 // steps, leaf visits, triangle-loop iterations -- SIMD work regardless of active lanes).
 struct WaveCounters { unsigned long long rays, nodes, leaves, tris, wq, wpair, wleaf, wtri, cyc_q, cyc_leaf, cyc_all, cyc_sample, cyc_post, wbary, lbary, live,
-                      cyc_light, cyc_normal, cyc_park;      // PROF: light step, hit normal, parking
+                      cyc_light, cyc_normal, cyc_park,      // PROF: light step, hit normal, parking
+                      hint;                                 // occluder hints: the wave's three counts (HINT_FIELD_BITS each)
                       unsigned long long* pc; };            // PROF: this wave's occupancy counters in LDS
 
 __device__ __forceinline__ int uni(int x) { return __builtin_amdgcn_readfirstlane(x); }   // value known wave-uniform
@@ -584,10 +585,26 @@ __device__ __forceinline__ bool ft_root_hit(const SceneView& S, const BvhRefs& b
 //    change Light::attenuate (light.cu:35-58).
 //  * triangle skip (cast_local's t_lo): a triangle whose plane crossing is certainly
 //    before tlo(leaf) - M cannot be accepted, so its inside test is not run.
-template <bool NOLEAF, bool STATS, bool FT = false, bool AXIS = false, bool PROF = false, bool BRUTE = false>
+//
+// Occluder hint (HINT: the fast NS = 0 trace kernels; `hslot` non-null: a shadow wave query of an
+// all-opaque scene with the scene's hint table).  `seed` (hint_code, 0: none,
+// its node checked by the caller) names a leaf by its parent's record and side.  The loop's first
+// iteration is then that record's pair test for that child alone -- the popped-leaf-B form -- and
+// the one leaf site, with the root next.  The visit is one the walk itself can make (same pair test,
+// same cut, same entry bound), only early: a lane it occludes (b.time <= occl_t) is done by the
+// criterion above, every other lane's Best is put back to "no hit" and its walk is the unseeded
+// one, bit for bit.  A side that is no leaf in this frame's tree (a stale code) visits nothing.  An occluded
+// lane's b.tri is replaced by the code of the leaf visit that occluded it (nothing reads a shadow
+// hit's triangle in an opaque scene), and after the walk lane 0 stores at most one word to *hslot:
+// the code of a lane the walk occluded and the seed did not, or 0 when a seed decided no lane.
+__device__ __forceinline__ int lane_id_fresh();               // (defined with the launch-parameter helpers below)
+template <bool NOLEAF, bool STATS, bool FT = false, bool AXIS = false, bool PROF = false, bool BRUTE = false,
+          bool HINT = false>
 __device__ __forceinline__ bool closest_hit(const SceneView& S, const BvhRefs& bv, bool active_in, const Ray& r,
                                             Best& b, WaveCounters& wc, float occl_t = -1.0f,
-                                            float lim = INFINITY, float zcut = -1.0f) {
+                                            float lim = INFINITY, float zcut = -1.0f, int seed = 0,
+                                            int* hslot = nullptr) {
+    static_assert(!HINT || (FT && !STATS && !PROF && !BRUTE && !NOLEAF), "hints: the fast kernels' ordered walk");
     const bool prune = !STATS && S.prune_abs >= 0.0f;
     float im = 0.0f;                                           // max_a |1/d_a| (set below)
     auto slack = [&](float t) { return (S.prune_abs + 0x1p-14f * fabsf(t)) * im + 0x1p-14f * fabsf(t); };
@@ -668,7 +685,11 @@ __device__ __forceinline__ bool closest_hit(const SceneView& S, const BvhRefs& b
         // (the stack holds no more than before).  Pushes are v_writelane into the stack VGPR.
         // Same-box A/B (profiles/r02/ab_trav2.log): frame 0.833 -> 0.810 ms, trace 0.973 -> 0.952.
         if (ri.exact) ri.ix = ri.iy = ri.iz = QNAN;           // every box: the exact test (pair_hit_tt2)
+        // bonly: 1 a popped leaf B of `node`; 2 / 3 (HINT) the seed, leaf A / B of `node`.  The seed's
+        // iteration is the only one whose next node is the root (next == 0), and everything it adds sits
+        // on the popped-leaf and leaf-visit paths: a descending step runs what it ran without hints.
         int node = 0, sp = 0, stk = 0, bonly = 0;
+        if (HINT && seed > 0) { node = hint_node(seed); bonly = 2 + hint_side(seed); }
         auto push = [&](int e) { asm("v_writelane_b32 %0, %1, m0" : "+v"(stk) : "s"(e), "{m0}"(sp)); sp++; };
         for (;;) {
             const float4* rec = bv.fnode + 4 * node;
@@ -679,20 +700,27 @@ __device__ __forceinline__ bool closest_hit(const SceneView& S, const BvhRefs& b
             pair_hit_tt2c(rec, r, ri, ct, ta, tb);
             float lt = QNAN, t2 = QNAN;                        // leaf entry bounds (NaN: missed)
             int linst = -1, inst2 = -1, next = -1;             // their instances, the next node (uniform; -1: pop)
+            int lcode = 0;                                     // hint_code of leaf `linst` (HINT)
             if (bonly) {                                       // popped: leaf B of this node
+                if (HINT && bonly > 1) {                       // the seed: that child alone if it is a leaf, then the root
+                    next = 0;
+                    const int rs = bonly == 2 ? ra : rb;
+                    if (rs < 0) { lt = bonly == 2 ? ta : tb; linst = -1 - rs; lcode = seed; }
+                } else {
+                    lt = tb; linst = -1 - rb; lcode = hint_code(node, 1);
+                }
                 bonly = 0;
-                lt = tb; linst = -1 - rb;
             } else {
                 const unsigned hA = any_lane(__ballot(ta <= ct)), hB = any_lane(__ballot(tb <= ct));
                 if (ra >= 0 && hA) {                           // descend into A, B after A's subtree
                     next = ra;
                     if (hB) push(rb >= 0 ? rb : -2 - node);
                 } else {
-                    if (hA) { lt = ta; linst = -1 - ra; }      // leaf A (ra < 0 here)
+                    if (hA) { lt = ta; linst = -1 - ra; lcode = hint_code(node, 0); }   // leaf A (ra < 0 here)
                     if (hB) {
                         if (rb >= 0) next = rb;                // after leaf A, if any
                         else if (linst >= 0) { t2 = tb; inst2 = -1 - rb; }
-                        else { lt = tb; linst = -1 - rb; }
+                        else { lt = tb; linst = -1 - rb; lcode = hint_code(node, 1); }
                     }
                 }
             }
@@ -708,13 +736,20 @@ __device__ __forceinline__ bool closest_hit(const SceneView& S, const BvhRefs& b
                         const unsigned long long cl0 = PROF ? __builtin_amdgcn_s_memtime() : 0;
                         if (PROF) { wc.wleaf++; wc.leaves += __popcll(__ballot(lh)); }
                         if (lh && cast_local<false, AXIS, PROF>(S, bv, linst, r, b, pre, wc, t_low(lt)))
-                            if (b.time <= occl_t) ct = QNAN;   // occluded: this lane is done
+                            if (b.time <= occl_t) {            // occluded: this lane is done
+                                ct = QNAN;
+                                if (HINT) b.tri = lcode;
+                            }
                         if (prune && ct == ct) ct = cut();
                         if (PROF) wc.cyc_leaf += __builtin_amdgcn_s_memtime() - cl0;
                         if (!__ballot(ct == ct)) { next = -1; sp = 0; break; }   // every lane occluded: done
                     }
                     if (inst2 < 0) break;
-                    lt = t2; linst = inst2; inst2 = -1;
+                    lt = t2; linst = inst2; inst2 = -1; lcode++;   // (leaf B after leaf A)
+                }
+                if (HINT && next == 0 && ct == ct) {           // after the seed visit: undecided lanes start clean
+                    b.time = INFINITY; b.inst = -1; b.tri = -1; b.u = 0.0f; b.v = 0.0f;
+                    ct = prune ? cut() : INFINITY;
                 }
             }
             if (next >= 0) { node = next; continue; }
@@ -723,6 +758,18 @@ __device__ __forceinline__ bool closest_hit(const SceneView& S, const BvhRefs& b
             const int e = __builtin_amdgcn_readlane(stk, sp);
             if (e < 0) { node = -2 - e; bonly = 1; }
             else node = e;
+        }
+        if (HINT && hslot) {                                   // (uniform) at most one word, not waited for
+            // A lane the seed visit occluded holds the seed as its code; a lane the walk occluded holds
+            // another (the walk's visit of the seed's leaf decides what the seed visit decided).
+            const unsigned long long oc = __ballot(b.time <= occl_t), sd = oc & __ballot(b.tri == seed);
+            const unsigned long long od = oc & ~sd;
+            wc.hint += 1ull + (seed > 0 ? 1ull << HINT_FIELD_BITS : 0ull) +
+                       (sd && sd == __ballot(active_in) ? 1ull << 2 * HINT_FIELD_BITS : 0ull);
+            if (od || (seed > 0 && !sd)) {
+                const int code = od ? __builtin_amdgcn_readlane(b.tri, __builtin_ctzll(od)) : 0;
+                if (lane_id_fresh() == 0) *hslot = code;
+            }
         }
         return active_in && b.time < INFINITY;                 // an accepted triangle has a finite time
     }
@@ -856,7 +903,8 @@ __device__ __forceinline__ KTP& kparams() {
 #endif
 typedef __attribute__((address_space(4))) const SceneView KSV;
 static_assert(sizeof(TraceParams) % alignof(SceneView) == 0, "SceneView follows TraceParams in the kernarg segment");
-static_assert(sizeof(TraceParams) == 400 && sizeof(SceneView) == 128, "kernarg layout (the kernels read it in place)");
+static_assert(sizeof(TraceParams) == 400 && sizeof(SceneView) == 136 && offsetof(SceneView, hint) == 128,
+              "kernarg layout (the kernels read it in place; the hint table after the 128 bytes every variant had)");
 __device__ __forceinline__ SceneView kscene() {
     const __attribute__((address_space(4))) char* p =
         (const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr();
@@ -983,6 +1031,9 @@ __device__ __forceinline__ V4 trace_sample(const SceneView& S, const BvhRefs& bv
                                            Ray r0, bool me, bool rec_ids, int g, WaveCounters& wc, float* park, int& nq) {
     constexpr bool OPQ = NS == 0;                               // no refractive material in the scene
     constexpr bool NN = PARK;                                   // is_nn parked across the queries
+    // occluder hints (closest_hit): the fast, fully parked or unparked, lockstep (NS = 0) kernels
+    constexpr bool HINT = FT && OPQ && !STATS && !PROF && !BRUTE && !PART;
+    int hkey = -1;                                              // hint_key of the wave's last normal hit (uniform)
     KTP& P0 = kparams();
     Frame cur;
     SavedFrame stk[NS > 0 ? NS : 1];
@@ -1153,6 +1204,19 @@ __device__ __forceinline__ V4 trace_sample(const SceneView& S, const BvhRefs& bv
         float occl = -1.0f;
         if (P.occl_exit && st == ST_WAIT_SHADOW) occl = max_t * (1.0f - 0x1p-21f);
         const float lim = st == ST_WAIT_SHADOW ? max_t : INFINITY;
+        // Occluder hint of a shadow wave query (closest_hit): the entry of the surface the wave
+        // shades (hkey) and its light -- the live lanes of an NS = 0 kernel are on the same light --
+        // read with one scalar load, issued here and used after the parking stores.
+        int seed = 0;
+        int* hslot = nullptr;
+        if (HINT && hkey >= 0 && P.occl_exit) {
+            const unsigned long long sm = __ballot(st == ST_WAIT_SHADOW && max_t >= 0.0f);
+            int* const tab = SV().hint;
+            if (sm && tab) {
+                hslot = tab + hkey + (__builtin_amdgcn_readlane(li, __builtin_ctzll(sm)) & 3);
+                seed = ldc(hslot, 0);
+            }
+        }
         const unsigned long long cpk0 = PROF ? __builtin_amdgcn_s_memtime() : 0;
         if (PARK) {
             float* pk = park;
@@ -1172,7 +1236,16 @@ __device__ __forceinline__ V4 trace_sample(const SceneView& S, const BvhRefs& bv
         // (an unlit-skipped shadow step, max_t = -inf, takes no query)
         const bool qa = st == ST_WAIT_NORMAL || (st == ST_WAIT_SHADOW && max_t >= 0.0f);
         const unsigned long long prof_p0 = wc.wpair, prof_l0 = wc.wleaf;
-        const bool hit = closest_hit<false, STATS, FT, AXIS, PROF, BRUTE>(SV(), bv, qa, q, b, wc, occl, lim);
+        if (HINT && seed != 0 && !hint_node_ok(seed, SV().n_real)) seed = 0;   // any table contents: a record of this tree, or none
+        const bool hit = closest_hit<false, STATS, FT, AXIS, PROF, BRUTE, HINT>(SV(), bv, qa, q, b, wc, occl, lim, -1.0f,
+                                                                               seed, hslot);
+        if (HINT) {                                            // a normal query's first hit keys the wave's shadow queries
+            const unsigned long long hm = __ballot(hit && st == ST_WAIT_NORMAL);
+            if (hm) {
+                const int hl = __builtin_ctzll(hm);
+                hkey = hint_key(__builtin_amdgcn_readlane(b.inst, hl), __builtin_amdgcn_readlane(b.tri, hl));
+            }
+        }
         if (PROF && P.stats) {                                 // query occupancy (rt_frame_work)
             const unsigned long long mp = __ballot(st == ST_WAIT_NORMAL && (fl & 1));
             const unsigned long long mn = __ballot(st == ST_WAIT_NORMAL);
@@ -1714,6 +1787,16 @@ __global__ __launch_bounds__(TRACE_BLOCK_P) void trace_kernel(TraceParams P_arg,
     }
     if (LSUM) wflush();
     if (P.hist == 1 && lane == 0 && wave_sum) atomicAdd(&P.hctl_next[1], wave_sum);
+    if (wc.hint && lane == 0) {                                // occluder hints: the wave's counts, after the table
+        // (one of HINT_STRIPES copies by block: every wave adding to the same three words queued
+        // ~12 k same-address atomics at the kernel's end, +5% on a lone frame's trace)
+        unsigned long long* hc = reinterpret_cast<unsigned long long*>(SV().hint + hint_table_ints(SV().n_inst)) +
+                                 (blockIdx.x % HINT_STRIPES) * HINT_STRIPE_WORDS;
+        for (int i = 0; i < HINT_COUNTERS; i++) {
+            const unsigned long long v = (wc.hint >> i * HINT_FIELD_BITS) & ((1ull << HINT_FIELD_BITS) - 1);
+            if (v) atomicAdd(&hc[i], v);
+        }
+    }
     if (CYC && P.stats && lane == 0) {
         if (wc.rays) atomicAdd(&P.stats[0], wc.rays);
         if (wc.nodes) atomicAdd(&P.stats[1], wc.nodes);

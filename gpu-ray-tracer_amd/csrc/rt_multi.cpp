@@ -212,6 +212,9 @@ int setup_multi(rt_scene* s, MultiDev* m, Rccl* R) {
 void rti::set_multi_overlap(rt_scene* s, int policy) {
     for (rt_scene* rp : s->multi->reps) rp->overlap = policy;
 }
+void rti::set_multi_shadow_hints(rt_scene* s, bool on) {
+    for (rt_scene* rp : s->multi->reps) rp->shadow_hints = on;
+}
 
 int rti::render_multi(rt_scene* s, const rt_render_opts* o, rt_stats* stats) {
     MultiDev* m = s->multi;

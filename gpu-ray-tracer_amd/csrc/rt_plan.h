@@ -231,6 +231,27 @@ inline ShadeShortcuts shade_shortcuts(const rt::Scene& h, bool want_stats, bool 
     return c;
 }
 
+// ---- Shadow-query occluder hints (SceneView::hint)
+// The table is keyed by the shaded surface and the light: HINT_SLOTS entries per instance, the
+// surface triangle's low 4 bits x the light's low 2 bits; aliasing is harmless (a hint only).
+// An entry names a leaf of the ordered LBVH by its parent's record and side, as hint_code; 0: none.
+// A code is taken only if its node is a record of the frame's tree (hint_node_ok) and that side
+// of it is a leaf: the seed visit is then one the walk itself could make (the node's own pair test).
+constexpr int HINT_SLOTS = 64;
+constexpr int HINT_COUNTERS = 3;        // shadow wave queries, those given a seed, those ended by it
+constexpr int HINT_FIELD_BITS = 21;     // a wave's three counts, packed in one 64-bit scalar until it ends
+__host__ __device__ inline int hint_key(int inst, int tri) { return inst * HINT_SLOTS + (tri & 15) * 4; }   // + (light & 3)
+__host__ __device__ inline int hint_code(int node, int side) { return 2 * node + side + 1; }
+__host__ __device__ inline int hint_node(int code) { return (code - 1) >> 1; }
+__host__ __device__ inline int hint_side(int code) { return (code - 1) & 1; }
+__host__ __device__ inline bool hint_node_ok(int code, int n_real) { return code > 0 && hint_node(code) < n_real - 1; }
+__host__ __device__ inline size_t hint_table_ints(int n_inst) { return (size_t)n_inst * HINT_SLOTS; }
+// the counters: HINT_STRIPES copies, one 64-byte line each (a block adds to copy block % HINT_STRIPES; the host sums)
+constexpr int HINT_STRIPES = 64, HINT_STRIPE_WORDS = 8;
+inline size_t hint_bytes(int n_inst) {
+    return hint_table_ints(n_inst) * sizeof(int) + (size_t)HINT_STRIPES * HINT_STRIPE_WORDS * sizeof(unsigned long long);
+}
+
 // ---- Grid policy
 struct GridPlan { int blocks, grid_waves, heavy_static, heavy_cap; };
 // per_cu: blocks of the chosen kernel a CU holds; other_running: another frame of the scene is

@@ -232,6 +232,13 @@ int rti::upload(rt_scene* s) {
     HIPCHK(hipMalloc((void**)&f.d_tree, 2 * nl * sizeof(Box)));
     if (s->n_leaf > BVH_WG_LEAVES) HIPCHK(hipMalloc(&f.d_bscratch, bvh_large_scratch_bytes(s->n_leaf)));
     HIPCHK(hipMalloc((void**)&s->d_stats, STATS_N * sizeof(unsigned long long)));
+    // the occluder hint table (rt_plan.h: hint_*), empty; scenes of the grid-wide BVH build get none.
+    // The instance set is fixed once the scene is finished: moved instances leave stale entries,
+    // which the kernels check, replace and clear themselves.
+    if (s->n_leaf <= BVH_WG_LEAVES && !h.d_insts.empty()) {
+        HIPCHK(hipMalloc((void**)&s->d_hint, hint_bytes((int)h.d_insts.size())));
+        HIPCHK(hipMemset(s->d_hint, 0, hint_bytes((int)h.d_insts.size())));
+    }
     HIPCHK(hipMalloc((void**)&s->d_canvas, (size_t)h.cam.W * h.cam.H * sizeof(uint32_t)));
     HIPCHK(hipMalloc((void**)&s->d_dbg, 4096 * sizeof(int)));
     for (auto& o : s->slots) if (!o.done) HIPCHK(hipEventCreateWithFlags(&o.done, hipEventDisableTiming));
@@ -564,6 +571,7 @@ SceneView view_of(const rt_scene* s, bool use_bvh) {
     const rtm::V3 cp = s->h.d_cam.pos;
     v.prune_abs = prune_slack(s, std::max(std::fabs(cp.x), std::max(std::fabs(cp.y), std::fabs(cp.z))));
     v.tri_ax = (v.ident_all && !s->h.d_tris.empty()) ? s->d_tri_ax : nullptr;
+    v.hint = nullptr;                                          // (launch_trace binds the table)
     return v;
 }
 
@@ -622,6 +630,7 @@ int launch_trace(rt_scene* s, const rt_render_opts& o, const TraceRequest& q) {
         P.atlas = s->d_atlas; P.atlas_w = s->h.atlas_w; P.atlas_h = s->h.atlas_h;
     }
     SceneView S = view_of(s, o.use_bvh != 0);
+    S.hint = s->shadow_hints ? s->d_hint : nullptr;
     P.lanes_per_px = g.lanes_per_px; P.px_per_wave = g.px_per_wave; P.gw = g.gw; P.gh = g.gh;
     P.l_shift = g.l_shift; P.gw_shift = g.gw_shift; P.n_gx = g.n_gx; P.n_groups = g.n_groups;
     if (q.geo) { q.geo[0] = g.n_groups; q.geo[1] = g.gw; q.geo[2] = g.gh; q.geo[3] = g.n_gx; }
@@ -776,7 +785,7 @@ rt_scene::~rt_scene() {
     if (uploaded) (void)hipSetDevice(device);
     free_atlas(this);
     dfree(d_tris); dfree(d_meshes); dfree(d_mats); dfree(d_lights); dfree(d_tri_ax);
-    dfree(d_mesh_box); dfree(d_spp); dfree(d_stats); dfree(d_canvas); dfree(d_dbg);
+    dfree(d_mesh_box); dfree(d_spp); dfree(d_stats); dfree(d_hint); dfree(d_canvas); dfree(d_dbg);
     for (auto& p : d_out) dfree(p);
     dfree(q_dev); hfree(q_host); dfree(qo_dev);
     accum.release();
@@ -1699,6 +1708,76 @@ int rt_scene_last_trace(const rt_scene* s, int32_t* out8) {
     const int32_t v[8] = {k.ns_bucket, (int32_t)k.lds, k.mode, (int32_t)k.shm, (int32_t)k.part_k, (int32_t)k.sky,
                           (int32_t)k.sky_brute, s->last_ftree};
     std::copy(v, v + 8, out8);
+    return RT_OK;
+}
+
+int rt_scene_set_shadow_hints(rt_scene* s, int on) {
+    CHECK_SCENE(s);
+    s->shadow_hints = on != 0;
+    if (s->multi) set_multi_shadow_hints(s, on != 0);         // the replicas of rt_scene_set_devices too
+    return RT_OK;
+}
+
+// the test hooks' prologue: the scene's device, every frame in flight done
+static int hints_quiesce(rt_scene* s) {
+    CHECK_FINISHED(s);
+    if (!s->uploaded) return fail(RT_ERR_STATE, "scene is not on a device");
+    HIPCHK(hipSetDevice(s->device));
+    for (auto& f : s->slots) if (f.pending) HIPCHK(hipEventSynchronize(f.done));
+    return RT_OK;
+}
+
+int rt_scene_shadow_hints_fill(rt_scene* s, int32_t value) {
+    int r;
+    if ((r = hints_quiesce(s)) != RT_OK) return r;
+    if (!s->d_hint) return RT_OK;
+    const int n_inst = (int)s->h.d_insts.size();
+    std::vector<int32_t> v(hint_bytes(n_inst) / sizeof(int32_t), 0);   // the counters' words stay zero
+    std::fill(v.begin(), v.begin() + hint_table_ints(n_inst), value);
+    HIPCHK(hipMemcpy(s->d_hint, v.data(), v.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    return RT_OK;
+}
+
+int rt_scene_shadow_hint_code(rt_scene* s, int inst, int32_t* code) {
+    int r;
+    if ((r = hints_quiesce(s)) != RT_OK) return r;
+    if (!code || inst < 0 || inst >= (int)s->h.d_insts.size()) return fail(RT_ERR_ARG, "instance out of range or null argument");
+    *code = 0;
+    const rt_scene::Built& b = s->built;
+    if (b.slot < 0 || !ordered_tree_usable(b.n_real, b.fdepth)) return RT_OK;
+    std::vector<float4> rec(4 * (size_t)(b.n_real - 1));
+    HIPCHK(hipMemcpy(rec.data(), s->slots[b.slot].d_fnode, rec.size() * sizeof(float4), hipMemcpyDeviceToHost));
+    for (int k = 0; k < b.n_real - 1; k++) {                  // a record's child references: -1 - instance for a leaf
+        int32_t ref[2];
+        memcpy(ref, &rec[4 * (size_t)k + 3], sizeof ref);
+        for (int side = 0; side < 2; side++)
+            if (ref[side] == -1 - inst) *code = hint_code(k, side);
+    }
+    return RT_OK;
+}
+
+int rt_scene_shadow_hints_read(rt_scene* s, int32_t* dst, int64_t cap) {
+    int r;
+    if ((r = hints_quiesce(s)) != RT_OK) return r;
+    const size_t n = s->d_hint ? hint_table_ints((int)s->h.d_insts.size()) : 0;
+    if ((n && !dst) || cap < (int64_t)n) return fail(RT_ERR_ARG, "destination too small");
+    if (n) HIPCHK(hipMemcpy(dst, s->d_hint, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+int rt_scene_shadow_hint_counters(rt_scene* s, uint64_t* out4) {
+    int r;
+    if ((r = hints_quiesce(s)) != RT_OK) return r;
+    if (!out4) return fail(RT_ERR_ARG, "null argument");
+    std::fill(out4, out4 + 4, 0);
+    if (!s->d_hint) return RT_OK;
+    const int n_inst = (int)s->h.d_insts.size();
+    static_assert(HINT_COUNTERS == 3 && HINT_COUNTERS <= HINT_STRIPE_WORDS, "out4 = three counters and the entry count");
+    uint64_t c[HINT_STRIPES * HINT_STRIPE_WORDS];
+    HIPCHK(hipMemcpy(c, s->d_hint + hint_table_ints(n_inst), sizeof c, hipMemcpyDeviceToHost));
+    for (int k = 0; k < HINT_STRIPES; k++)
+        for (int i = 0; i < HINT_COUNTERS; i++) out4[i] += c[k * HINT_STRIPE_WORDS + i];
+    out4[3] = hint_table_ints(n_inst);
     return RT_OK;
 }
 

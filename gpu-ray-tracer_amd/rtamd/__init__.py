@@ -45,6 +45,8 @@ SYMBOLS = [
     "rt_copy_engines_warm", "rt_scene_last_trace", "rt_query_opts_default", "rt_query",
     "rt_query_set_order", "rt_query_last",
     "rt_accum_opts_default", "rt_accumulate", "rt_accumulate_reset", "rt_accumulate_info",
+    "rt_scene_set_shadow_hints", "rt_scene_shadow_hints_fill", "rt_scene_shadow_hint_code",
+    "rt_scene_shadow_hint_counters", "rt_scene_shadow_hints_read",
 ]
 RT_QUERY_ORDER_CALLER, RT_QUERY_ORDER_SORTED = 0, 1
 
@@ -169,6 +171,12 @@ def lib():
     L.rt_frame_work.argtypes = [vp, ctypes.POINTER(RenderOpts), ctypes.POINTER(Work)]
     L.rt_scene_set_devices.argtypes = [vp, vp, ip, ip]
     L.rt_scene_last_trace.argtypes = [vp, vp]
+    if hasattr(L, "rt_scene_set_shadow_hints"):  # (absent from libraries before the occluder hints: A/B runs)
+        L.rt_scene_set_shadow_hints.argtypes = [vp, ip]
+        L.rt_scene_shadow_hints_fill.argtypes = [vp, ctypes.c_int32]
+        L.rt_scene_shadow_hint_code.argtypes = [vp, ip, ctypes.POINTER(ctypes.c_int32)]
+        L.rt_scene_shadow_hint_counters.argtypes = [vp, vp]
+        L.rt_scene_shadow_hints_read.argtypes = [vp, vp, ctypes.c_int64]
     L.rt_query_opts_default.argtypes = [ctypes.POINTER(QueryOpts)]
     L.rt_query_opts_default.restype = None
     L.rt_query.argtypes = [vp, ctypes.POINTER(QueryOpts), ctypes.POINTER(Stats)]
@@ -669,6 +677,35 @@ class Scene:
         _check(lib().rt_scene_last_trace(self._h, _ptr(v)))
         keys = ["ns_bucket", "lds", "mode", "shm", "part_k", "sky", "sky_brute", "ftree"]
         return dict(zip(keys, [int(x) for x in v]))
+
+    def set_shadow_hints(self, on):
+        """Shadow-query occluder hints on (default) or off: the frame is the same either way
+        (rt_scene_set_shadow_hints)."""
+        _check(lib().rt_scene_set_shadow_hints(self._h, 1 if on else 0))
+
+    def shadow_hints_fill(self, value):
+        """Test hook: every entry of the hint table set to `value` (any int32), counters zeroed."""
+        _check(lib().rt_scene_shadow_hints_fill(self._h, ctypes.c_int32(int(value) & 0xffffffff).value))
+
+    def shadow_hint_code(self, inst):
+        """Test hook: the table value naming instance `inst`'s leaf in the last built ordered tree (0: none)."""
+        c = ctypes.c_int32()
+        _check(lib().rt_scene_shadow_hint_code(self._h, int(inst), ctypes.byref(c)))
+        return c.value
+
+    def shadow_hints(self):
+        """Test hook: the hint table, [n_inst, 16, 4] int32 (instance, triangle & 15, light & 3)."""
+        n = self.shadow_hint_counters()["entries"]
+        v = np.zeros(n, np.int32)
+        _check(lib().rt_scene_shadow_hints_read(self._h, _ptr(v), n))
+        return v.reshape(-1, 16, 4)
+
+    def shadow_hint_counters(self):
+        """Counters since the last fill: shadow wave queries of the hinted kernels, those given a
+        seed, those ended by the seed; `entries`: the table's size (0: the scene has none)."""
+        v = np.zeros(4, np.uint64)
+        _check(lib().rt_scene_shadow_hint_counters(self._h, _ptr(v)))
+        return dict(zip(("queries", "seeded", "ended", "entries"), [int(x) for x in v]))
 
     def set_devices(self, devices, n_ranks=None):
         """Split every whole frame row-cyclically over `devices` from this process (n_ranks

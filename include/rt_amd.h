@@ -32,7 +32,8 @@ extern "C" {
  *    existing entry or struct changed, so the version callers compare against stays)
  *    (still 5: additive -- rt_query_set_order / rt_query_last and the RT_QUERY_ORDER_* modes;
  *    rt_query_opts keeps its layout, the switch is scene state)
- *    (still 5: additive -- the RT_EXPORT_BVH_* values of rt_scene_export, a test hook) */
+ *    (still 5: additive -- the RT_EXPORT_BVH_* values of rt_scene_export, a test hook)
+ *    (still 5: additive -- rt_scene_set_shadow_hints and its test hooks) */
 #define RT_ABI_VERSION 5
 
 enum {
@@ -404,6 +405,26 @@ int rt_kat_device(const char* op, int n, const float* in0, const float* in1, con
  * usable}.  RT_ERR_STATE before the first launch.  Host state only: no device call.  A scene
  * split by rt_scene_set_devices launches on its replicas, which this does not see. */
 int rt_scene_last_trace(const rt_scene* s, int32_t out8[8]);
+
+/* Shadow-query occluder hints: a per-scene device table, keyed by the shaded
+ * surface (instance, triangle) and the light, that remembers which leaf of the scene's tree last
+ * occluded a shadow query from there; the fast frames of all-opaque scenes try that leaf first.
+ * A hint only: a frame is the same with any table contents, and with the switch off.  Default on;
+ * scenes too large for the single-workgroup BVH build have no table.  A scene split by
+ * rt_scene_set_devices switches its replicas too. */
+int rt_scene_set_shadow_hints(rt_scene* s, int on);
+/* Test hooks.  rt_scene_shadow_hints_fill sets every table entry to `value` (any 32-bit value) and
+ * zeroes the counters, after every frame in flight.  rt_scene_shadow_hint_code gives the entry
+ * value that names instance `inst`'s leaf in the most recently built ordered tree (0: the instance
+ * is no leaf of it, or no such tree was built).  rt_scene_shadow_hint_counters reads the counters
+ * accumulated since the last fill: shadow wave queries of the hinted kernels, those given a seed,
+ * those ended entirely by the seed; out4[3] = the table's entry count (0: no table).
+ * rt_scene_shadow_hints_read copies the table's entries out (`cap` entries of room; entry
+ * inst * 64 + (tri & 15) * 4 + (light & 3)).  RT_ERR_STATE before the scene is on a device. */
+int rt_scene_shadow_hints_fill(rt_scene* s, int32_t value);
+int rt_scene_shadow_hints_read(rt_scene* s, int32_t* dst, int64_t cap);
+int rt_scene_shadow_hint_code(rt_scene* s, int inst, int32_t* code);
+int rt_scene_shadow_hint_counters(rt_scene* s, uint64_t out4[4]);
 
 /* Profiling hook: launches an empty marker kernel of `tag` (1..64) workgroups on `stream` (a
  * hipStream_t; NULL = the default stream), so a rocprofv3 kernel or counter trace can find the

@@ -1,6 +1,8 @@
 #!/bin/bash
 # A/B timing of library variants on the bench workload, interleaved A B A B ... so clock
-# and thermal drift hit every arm alike.  Usage: tools/ab.sh ROUNDS lib1.so lib2.so ... [-- bench args]
+# and thermal drift hit every arm alike.  Usage: tools/ab.sh ROUNDS arm1 arm2 ... [-- bench args]
+# An arm is a library, or library@VAR=VALUE to run it with that environment setting (the same
+# library with a switch off: librt_amd.so@RT_SHADOW_HINTS=0).
 set -o pipefail
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 ROUNDS=$1; shift
@@ -8,9 +10,11 @@ LIBS=()
 while [ $# -gt 0 ] && [ "$1" != "--" ]; do LIBS+=("$1"); shift; done
 [ "$1" == "--" ] && shift
 for r in $(seq 1 $ROUNDS); do
-  for L in "${LIBS[@]}"; do
-    RTAMD_LIB=$L timeout -k 10 120 python3 "$R/bench.py" --full --no-cpu-baseline --steps ${AB_STEPS:-20} --warmup 3 --no-camera-path "$@" > /tmp/ab_out.txt 2>&1 || { cat /tmp/ab_out.txt; exit 1; }
-    python3 - "$L" <<'PY'
+  for A in "${LIBS[@]}"; do
+    L=${A%%@*}; E=
+    [ "$A" != "$L" ] && E=${A#*@}
+    env ${E:+"$E"} RTAMD_LIB=$L timeout -k 10 120 python3 "$R/bench.py" --full --no-cpu-baseline --steps ${AB_STEPS:-20} --warmup 3 --no-camera-path "$@" > /tmp/ab_out.txt 2>&1 || { cat /tmp/ab_out.txt; exit 1; }
+    python3 - "$A" <<'PY'
 import json, sys
 line = [l for l in open('/tmp/ab_out.txt') if l.startswith('{')][-1]
 d = json.loads(line)
