@@ -2,7 +2,7 @@
 //
 //   rtracer -c world8.json [-b] [-r] [-s] [-d DIM] [--frames N] [--spp K]
 //           [--width W --height H] [--out frame.ppm] [--debug X,Y] [--textures [ATLAS.png]]
-//           [--gpus N [--ranks R]] [--in-flight D] [--pick X,Y] [--accumulate N]
+//           [--gpus N [--ranks R]] [--in-flight D] [--pick X,Y] [--accumulate N [--adaptive [THR]]]
 //
 // -c config (worldN.json), -b benchmark (one timed frame, "Time: X ms" as main.cc:210-216),
 // -r unoptimize (brute force, no BVH), -d kernel dimension (accepted; the HIP path
@@ -23,6 +23,9 @@
 // --accumulate N (build extension, rt_accumulate): progressive refinement -- N calls that add one
 // sample each to the scene's running sums, as an interactive loop does while nothing moves; the
 // frame after the last call is the --spp N frame, and --out writes it.  -b prints each call's time.
+// --adaptive [THR] (with --accumulate only; rt_accumulate_set_adaptive): after sample 0 only the
+// 8 x 8 tiles with a contrast above THR (default 8/255) are refined; the others keep the 1-spp
+// frame.  Prints "Adaptive: K of T tiles refined".
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -40,7 +43,8 @@ static void usage() {
     std::fprintf(stderr,
                  "usage: rtracer -c CONFIG [-b] [-r] [-s] [-d DIM] [--frames N] [--spp K] [--width W --height H]\n"
                  "               [--out FILE.ppm] [--debug X,Y] [--textures [ATLAS.png]] [--gpus N [--ranks R]]\n"
-                 "               [--in-flight D [--readback] [--overlap stream|half|full]] [--pick X,Y] [--accumulate N]\n");
+                 "               [--in-flight D [--readback] [--overlap stream|half|full]] [--pick X,Y]\n"
+                 "               [--accumulate N [--adaptive [THR]]]\n");
 }
 
 static bool write_ppm(const char* path, const uint32_t* px, int w, int h) {
@@ -61,7 +65,8 @@ static bool write_ppm(const char* path, const uint32_t* px, int w, int h) {
 
 int main(int argc, char** argv) {
     std::string config, out;
-    bool bench = false, unopt = false, serial = false, textures = false, readback = false;
+    bool bench = false, unopt = false, serial = false, textures = false, readback = false, adaptive = false;
+    float adaptive_thr = RT_ADAPTIVE_THRESHOLD_DEFAULT;
     std::string atlas, overlap = "stream";
     int dim = 16, frames = 1, spp = 1, width = 0, height = 0, dbg_x = -1, dbg_y = -1, pick_x = -1, pick_y = -1, gpus = 1, ranks = 0, in_flight = 0, accumulate = 0;
     for (int i = 1; i < argc; i++) {
@@ -84,6 +89,14 @@ int main(int argc, char** argv) {
         else if (a == "--ranks") ranks = std::atoi(val("--ranks"));
         else if (a == "--in-flight") in_flight = std::atoi(val("--in-flight"));
         else if (a == "--accumulate") { accumulate = std::atoi(val("--accumulate")); if (accumulate < 1) { usage(); return 2; } }
+        else if (a == "--adaptive") {
+            adaptive = true;
+            if (i + 1 < argc && argv[i + 1][0] != '-') {
+                char* end = nullptr;
+                adaptive_thr = std::strtof(argv[++i], &end);
+                if (end == argv[i] || *end) { usage(); return 2; }
+            }
+        }
         else if (a == "--readback") readback = true;
         else if (a == "--overlap") {
             overlap = val("--overlap");
@@ -106,6 +119,7 @@ int main(int argc, char** argv) {
         return 2;
     }
     if (frames < 1 || spp < 1 || gpus < 1 || ranks < 0 || in_flight < 0 || in_flight > 8) { usage(); return 2; }
+    if (adaptive && accumulate < 1) { std::fprintf(stderr, "--adaptive needs --accumulate N\n"); usage(); return 2; }
     // frames in flight use a stream each: HIP maps streams round-robin onto GPU_MAX_HW_QUEUES
     // hardware queues (4 by default), and streams sharing a queue serialise.
     // The HIP runtime reads it when librt_amd.so's kernels are registered, before main: set it
@@ -148,6 +162,11 @@ int main(int argc, char** argv) {
         rtamd_detail::check(rt_scene_info(handle, info), "rt_scene_info");
         std::vector<uint32_t> frame((size_t)info[0] * info[1]);
         int n = 0;
+        if (adaptive && rt_accumulate_set_adaptive(handle, 1, adaptive_thr) != RT_OK) {
+            std::fprintf(stderr, "--adaptive: %s\n", rt_last_error());
+            rt_scene_free(handle);
+            return 2;
+        }
         for (int k = 0; k < accumulate; k++) {
             rt_accum_opts o;
             rt_accum_opts_default(&o);
@@ -164,6 +183,11 @@ int main(int argc, char** argv) {
             if (bench) std::printf("Sample %d: %g ms\n", n, std::chrono::duration<double, std::milli>(to - from).count());
         }
         std::printf("Accumulated %d samples\n", n);
+        if (adaptive) {
+            int32_t t[8];
+            rtamd_detail::check(rt_accumulate_adaptive_info(handle, t, nullptr, nullptr, 0), "rt_accumulate_adaptive_info");
+            std::printf("Adaptive: %d of %d tiles refined\n", t[5], t[3] * t[4]);
+        }
         if (!out.empty() && !write_ppm(out.c_str(), frame.data(), info[0], info[1])) {
             std::fprintf(stderr, "cannot write %s\n", out.c_str());
             rt_scene_free(handle);

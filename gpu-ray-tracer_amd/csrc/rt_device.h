@@ -11,6 +11,7 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "rt_adapt.h"
 #include "rt_bvh.h"
 #include "rt_math.h"
 #include "rt_raykey.h"
@@ -232,6 +233,19 @@ size_t scene_image_bytes(const SceneView& S);   // the scene image a fast kernel
 // read); resolve: the frame of n_before + 1 samples into rgba / radiance (each may be null).
 hipError_t launch_accum_fold(const float4* pass, float4* sum_r, float4* sum_c, int n_px, int n_before, bool resolve,
                              uint32_t* rgba, float4* radiance, hipStream_t st, hipEvent_t e0, hipEvent_t e1);
+// rt_accumulate's adaptive mode (rt_adapt.h).  accum_edge_kernel: need[g] = 1 for every tile with an
+// edge pixel in sum_c at `threshold` (need: n_tiles bytes padded to whole dwords).  accum_lists_kernel:
+// the needed tiles as live-group lists [NQ][live_cap] and, in `image` (WORK_INTS ints, zeroed
+// by the caller), the work counters a trace launch over them starts from (the list lengths sum to
+// the needed-tile count).  accum_fold_tiles_kernel: launch_accum_fold for the needed tiles of a
+// pass with n_before >= 1; the other tiles only resolve, as the 1-sample frame.
+hipError_t launch_accum_edge(const float4* sum_c, const rtad::TileGrid& t, float threshold, unsigned char* need, hipStream_t st,
+                             hipEvent_t e0, hipEvent_t e1);
+hipError_t launch_accum_lists(const unsigned char* need, int n_tiles, int* live, int live_cap, int* image, hipStream_t st,
+                              hipEvent_t e0, hipEvent_t e1);
+hipError_t launch_accum_fold_tiles(const float4* pass, float4* sum_r, float4* sum_c, const unsigned char* need,
+                                   const rtad::TileGrid& t, int n_before, bool resolve, uint32_t* rgba, float4* radiance,
+                                   hipStream_t st, hipEvent_t e0, hipEvent_t e1);
 void launch_unpermute(const uint32_t* g, uint32_t* out, int W, int H, int N, int rows_max, hipStream_t st);
 void launch_profile_marker(int tag, hipStream_t st);
 void launch_copy_gate(const unsigned* flag, unsigned long long max_ticks, hipStream_t st);

@@ -186,7 +186,27 @@ struct rt_scene {
         int n = 0, restarts = 0;
         unsigned inst_gen = 0, cam_gen = 0, env_gen = 0, atlas_gen = 0;
         int textures = 0;
-        void release() { rti::dfree(d_sum_r); rti::dfree(d_sum_c); rti::dfree(d_pass); rti::dfree(d_hit_inst); rti::dfree(d_hit_tri); px = 0; }
+        // Adaptive mode (rt_accumulate_set_adaptive, rt_adapt.h): the switch and its threshold (host
+        // state); the mask of needed tiles, their live-group lists [NQ][live_q] and the image of the
+        // work counters a refinement pass starts from (WORK_INTS ints),
+        // for tile_cap tiles: allocated on first adaptive use, freed with the scene, owned by the
+        // accumulation and not by a frame slot.  have_mask: decided for the samples held (dropped
+        // with them); needed: its count, read back once; traced: the tiles the last pass's trace
+        // launch was given.
+        int mode = 0;
+        float threshold = 8.0f / 255.0f;
+        unsigned char* d_need = nullptr;
+        int *d_live = nullptr, *d_image = nullptr;
+        int tile_cap = 0;
+        rtad::TileGrid tiles{};
+        bool have_mask = false;
+        bool count_pending = false;              // needed not read back yet (a call that failed before its sync leaves it so)
+        int needed = -1, traced = 0;
+        void release_adaptive() { rti::dfree(d_need); rti::dfree(d_live); rti::dfree(d_image); tile_cap = 0; have_mask = false; count_pending = false; needed = -1; }
+        void release() {
+            rti::dfree(d_sum_r); rti::dfree(d_sum_c); rti::dfree(d_pass); rti::dfree(d_hit_inst); rti::dfree(d_hit_tri); px = 0;
+            release_adaptive();
+        }
     } accum;
     static constexpr int MAX_SLOTS = RT_MAX_SLOTS;
     rti::FrameSlot slots[MAX_SLOTS];             // slots[0, n_slots) are in rotation (FrameSlot)

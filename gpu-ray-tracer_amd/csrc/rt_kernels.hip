@@ -36,6 +36,7 @@
 #include <cstring>
 
 #include "rt_accum.h"
+#include "rt_adapt.h"
 #include "rt_bvh.h"
 #include "rt_device.h"
 #include "rt_math.h"
@@ -2635,6 +2636,82 @@ __global__ __launch_bounds__(FOLD_BLOCK) void accum_fold_kernel(const float4* __
     }
 }
 
+// ---- rt_accumulate's adaptive mode (rt_adapt.h) ----
+// Byte g of a flag array padded to whole dwords, g wave-uniform: a scalar load.
+__device__ __forceinline__ unsigned tile_flag(const unsigned char* f, int g) {
+    return (ldc(reinterpret_cast<const uint32_t*>(f), g >> 2) >> (8 * (g & 3))) & 0xffu;
+}
+__device__ __forceinline__ V4 ld_v4(const float4* p, long long i) { const float4 v = p[i]; return v4(v.x, v.y, v.z, v.w); }
+
+// Which tiles have an edge: once per accumulation, after sample 0's fold, from sum_c (= 0 +
+// clamp1(r0)).  One wave per tile, one pixel per lane; each lane reads its own sum and its eight
+// neighbours' with plain 16-byte loads (the frame is L2-resident and this runs once: a 10 x 10
+// LDS halo would save loads the L2 serves and cost a barrier and the partial-tile cases), lanes
+// outside the canvas do not vote, lane 0 stores the ballot as a byte.  No atomics.
+constexpr int TILE_BLOCK = 256;
+__global__ __launch_bounds__(TILE_BLOCK) void accum_edge_kernel(const float4* __restrict__ sum_c, rtad::TileGrid t, float thr,
+                                                                unsigned char* __restrict__ need) {
+    const int g = __builtin_amdgcn_readfirstlane((int)blockIdx.x * (TILE_BLOCK / 64) + (int)(threadIdx.x >> 6));
+    if (g >= rtad::n_tiles(t)) return;
+    int x, y;
+    const bool in = rtad::tile_lane(t, g, (int)(threadIdx.x & 63), x, y);
+    const bool e = in && rtad::edge_pixel(t, x, y, thr, [&](int qx, int qy) { return ld_v4(sum_c, (long long)qy * t.W + qx); });
+    const unsigned long long m = __ballot(e);
+    if ((threadIdx.x & 63) == 0) need[g] = m ? 1 : 0;
+}
+
+// The needed tiles' live lists, in the form sky_kernel leaves them: block b (64 tiles, one per
+// lane) ballot-compacts its needed tiles and appends them to list b % NQ with one atomicAdd, so a
+// list holds at most live_cap = layout_of(n_groups).live_q entries.  `image` is a WORK_INTS image
+// of the work counters (zeroed before: tickets and the heavy length stay zero, the list lengths
+// are set here); the host sums the NQ lengths for the count of needed tiles.  The order of a
+// list's entries is the order its blocks arrive in: it differs from run to run, as sky_kernel's.
+__global__ __launch_bounds__(64) void accum_lists_kernel(const unsigned char* __restrict__ need, int n_tiles, int* __restrict__ live,
+                                                         int live_cap, int* __restrict__ image) {
+    const int lane = threadIdx.x, g = (int)blockIdx.x * 64 + lane;
+    const bool nd = g < n_tiles && need[g] != 0;
+    const unsigned long long m = __ballot(nd);
+    if (!m) return;
+    const int q = blockIdx.x % NQ, n = __popcll(m);
+    int base = 0;
+    if (lane == 0) base = atomicAdd(&image[16 * (NQ + 1 + q)], n);
+    base = __builtin_amdgcn_readfirstlane(base);
+    if (nd) live[q * live_cap + base + __popcll(m & ((1ull << lane) - 1ull))] = g;
+}
+
+// The fold of a refinement pass (sample k >= 1): one wave per tile over all tiles, need[g] read
+// with a scalar load and branched on wave-uniformly.  A tile not needed: nothing without
+// `resolve`; with it the sums are read and the 1-sample frame written (resolve_*(sum, 1)) -- the
+// pass buffer is not read, no sum is written.  A needed tile: accum_fold_kernel's arithmetic,
+// resolved with n_before + 1.  16 bytes per lane, a tile row of 8 pixels a 128-byte piece.
+__global__ __launch_bounds__(TILE_BLOCK) void accum_fold_tiles_kernel(const float4* __restrict__ pass, float4* __restrict__ sum_r,
+                                                                      float4* __restrict__ sum_c, const unsigned char* __restrict__ need,
+                                                                      rtad::TileGrid t, int n_before, int resolve,
+                                                                      uint32_t* __restrict__ rgba, float4* __restrict__ radiance) {
+    const int g = __builtin_amdgcn_readfirstlane((int)blockIdx.x * (TILE_BLOCK / 64) + (int)(threadIdx.x >> 6));
+    if (g >= rtad::n_tiles(t)) return;
+    const bool nd = tile_flag(need, g) != 0;
+    if (!nd && !resolve) return;
+    int x, y;
+    if (!rtad::tile_lane(t, g, (int)(threadIdx.x & 63), x, y)) return;
+    const long long i = (long long)y * t.W + x;
+    V4 sr = ld_v4(sum_r, i), sc = ld_v4(sum_c, i);
+    int n = 1;
+    if (nd) {
+        rta::fold(sr, sc, ld_v4(pass, i));
+        sum_r[i] = make_float4(sr.x, sr.y, sr.z, sr.w);
+        sum_c[i] = make_float4(sc.x, sc.y, sc.z, sc.w);
+        n = n_before + 1;
+    }
+    if (resolve) {
+        if (rgba) rgba[i] = rta::resolve_rgba(sc, n);
+        if (radiance) {
+            const V4 m = rta::resolve_radiance(sr, n);
+            radiance[i] = make_float4(m.x, m.y, m.z, m.w);
+        }
+    }
+}
+
 extern "C" {   // (unmangled names: profiler traces are searched for them, tools/pmc_step.py)
 // Profile marker (rt_profile_marker): an empty kernel whose grid (64 x tag threads) tells a
 // rocprofv3 trace where a caller's timed region begins and ends (tools/pmc_step.py).
@@ -2773,6 +2850,35 @@ hipError_t launch_accum_fold(const float4* pass, float4* sum_r, float4* sum_c, i
     void* args[] = {&pass, &sum_r, &sum_c, &n_px, &n_before, &res, &rgba, &radiance};
     return hipExtLaunchKernel((const void*)accum_fold_kernel, dim3((unsigned)((n_px + FOLD_BLOCK - 1) / FOLD_BLOCK)), dim3(FOLD_BLOCK),
                               args, 0, st, e0, e1, 0);
+}
+
+hipError_t launch_accum_edge(const float4* sum_c, const rtad::TileGrid& t, float threshold, unsigned char* need, hipStream_t st,
+                             hipEvent_t e0, hipEvent_t e1) {
+    const int n = rtad::n_tiles(t);
+    if (n <= 0) return hipSuccess;
+    rtad::TileGrid tg = t;
+    void* args[] = {&sum_c, &tg, &threshold, &need};
+    return hipExtLaunchKernel((const void*)accum_edge_kernel, dim3((unsigned)((n + TILE_BLOCK / 64 - 1) / (TILE_BLOCK / 64))),
+                              dim3(TILE_BLOCK), args, 0, st, e0, e1, 0);
+}
+
+hipError_t launch_accum_lists(const unsigned char* need, int n_tiles, int* live, int live_cap, int* image, hipStream_t st,
+                              hipEvent_t e0, hipEvent_t e1) {
+    if (n_tiles <= 0) return hipSuccess;
+    void* args[] = {&need, &n_tiles, &live, &live_cap, &image};
+    return hipExtLaunchKernel((const void*)accum_lists_kernel, dim3((unsigned)((n_tiles + 63) / 64)), dim3(64), args, 0, st, e0, e1, 0);
+}
+
+hipError_t launch_accum_fold_tiles(const float4* pass, float4* sum_r, float4* sum_c, const unsigned char* need,
+                                   const rtad::TileGrid& t, int n_before, bool resolve, uint32_t* rgba, float4* radiance,
+                                   hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
+    const int n = rtad::n_tiles(t);
+    if (n <= 0) return hipSuccess;
+    rtad::TileGrid tg = t;
+    int res = resolve ? 1 : 0;
+    void* args[] = {&pass, &sum_r, &sum_c, &need, &tg, &n_before, &res, &rgba, &radiance};
+    return hipExtLaunchKernel((const void*)accum_fold_tiles_kernel, dim3((unsigned)((n + TILE_BLOCK / 64 - 1) / (TILE_BLOCK / 64))),
+                              dim3(TILE_BLOCK), args, 0, st, e0, e1, 0);
 }
 
 void launch_unpermute(const uint32_t* g, uint32_t* out, int W, int H, int N, int rows_max, hipStream_t st) {

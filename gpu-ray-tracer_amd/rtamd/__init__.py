@@ -45,10 +45,13 @@ SYMBOLS = [
     "rt_copy_engines_warm", "rt_scene_last_trace", "rt_query_opts_default", "rt_query",
     "rt_query_set_order", "rt_query_last",
     "rt_accum_opts_default", "rt_accumulate", "rt_accumulate_reset", "rt_accumulate_info",
+    "rt_accumulate_set_adaptive", "rt_accumulate_adaptive_info", "rt_accumulate_pass_fill", "rt_accumulate_pass_read",
+    "rt_scene_history_info",
     "rt_scene_set_shadow_hints", "rt_scene_shadow_hints_fill", "rt_scene_shadow_hint_code",
     "rt_scene_shadow_hint_counters", "rt_scene_shadow_hints_read",
 ]
 RT_QUERY_ORDER_CALLER, RT_QUERY_ORDER_SORTED = 0, 1
+RT_ADAPTIVE_THRESHOLD_DEFAULT = 8.0 / 255.0
 
 
 class RtError(RuntimeError):
@@ -186,6 +189,12 @@ def lib():
         L.rt_accumulate.argtypes = [vp, ctypes.POINTER(AccumOpts), ctypes.POINTER(ip)]
         L.rt_accumulate_reset.argtypes = [vp]
         L.rt_accumulate_info.argtypes = [vp, vp]
+    if hasattr(L, "rt_accumulate_set_adaptive"):   # (absent from libraries before adaptive refinement: A/B runs)
+        L.rt_accumulate_set_adaptive.argtypes = [vp, ip, ctypes.c_float]
+        L.rt_accumulate_adaptive_info.argtypes = [vp, vp, fp, vp, ctypes.c_int64]
+        L.rt_accumulate_pass_fill.argtypes = [vp, ctypes.c_uint32]
+        L.rt_accumulate_pass_read.argtypes = [vp, vp, ctypes.c_int64]
+        L.rt_scene_history_info.argtypes = [vp, vp]
     if hasattr(L, "rt_query_set_order"):        # (absent from libraries before the coherence sort: A/B runs)
         L.rt_query_set_order.argtypes = [vp, ip]
         L.rt_query_last.argtypes = [vp, vp, vp, vp, ctypes.c_int64]
@@ -558,6 +567,43 @@ class Scene:
         a = np.zeros(4, np.int32)
         _check(lib().rt_accumulate_info(self._h, _ptr(a)))
         return tuple(int(x) for x in a)
+
+    def set_accumulate_adaptive(self, on=True, threshold=RT_ADAPTIVE_THRESHOLD_DEFAULT):
+        """Adaptive refinement (rt_accumulate_set_adaptive): after sample 0, accumulate() traces and
+        folds further samples only for the tiles that have an edge at `threshold`; the other
+        tiles keep the 1-spp frame.  Changing the mode or the threshold drops the samples held."""
+        _check(lib().rt_accumulate_set_adaptive(self._h, 1 if on else 0, float(threshold)))
+
+    def accumulate_tiles(self):
+        """The adaptive mode's state (rt_accumulate_adaptive_info): {"mode", "threshold", "tile": (w, h),
+        "need": bool[n_ty, n_tx] or None before a mask exists, "needed": tiles needed (-1: no mask),
+        "traced": tiles the last pass's trace launch was given}."""
+        o = np.zeros(8, np.int32)
+        thr = ctypes.c_float()
+        _check(lib().rt_accumulate_adaptive_info(self._h, _ptr(o), ctypes.byref(thr), None, 0))
+        need = np.zeros((int(o[4]), int(o[3])), np.uint8)
+        r = lib().rt_accumulate_adaptive_info(self._h, _ptr(o), None, _ptr(need), need.size)
+        if r != RT_ERR_STATE:                                      # (RT_ERR_STATE: no mask yet)
+            _check(r)
+        need = need.astype(bool) if r == RT_OK else None
+        return {"mode": int(o[0]), "threshold": float(thr.value), "tile": (int(o[1]), int(o[2])), "need": need,
+                "needed": int(o[5]), "traced": int(o[6])}
+
+    def _history_info(self):
+        """Test hook: the current frame slot's scheduling-history state (rt_scene_history_info), a tuple of 12."""
+        a = np.zeros(12, np.int32)
+        _check(lib().rt_scene_history_info(self._h, _ptr(a)))
+        return tuple(int(x) for x in a)
+
+    def _accumulate_pass_fill(self, bits):
+        """Test hook: the pass buffer filled with a 32-bit pattern (rt_accumulate_pass_fill)."""
+        _check(lib().rt_accumulate_pass_fill(self._h, int(bits) & 0xffffffff))
+
+    def _accumulate_pass_read(self):
+        """Test hook: the pass buffer, (H, W, 4) float32 (rt_accumulate_pass_read)."""
+        a = np.zeros((self.height, self.width, 4), np.float32)
+        _check(lib().rt_accumulate_pass_read(self._h, _ptr(a), a.size))
+        return a
 
     def frame_work(self, spp=1, row0=0, row_step=1, compact=True, want_rgba=False):
         """What the fast kernels do for this frame (rt_frame_work): queries issued after the

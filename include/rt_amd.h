@@ -33,7 +33,9 @@ extern "C" {
  *    (still 5: additive -- rt_query_set_order / rt_query_last and the RT_QUERY_ORDER_* modes;
  *    rt_query_opts keeps its layout, the switch is scene state)
  *    (still 5: additive -- the RT_EXPORT_BVH_* values of rt_scene_export, a test hook)
- *    (still 5: additive -- rt_scene_set_shadow_hints and its test hooks) */
+ *    (still 5: additive -- rt_scene_set_shadow_hints and its test hooks)
+ *    (still 5: additive -- rt_accumulate_set_adaptive / rt_accumulate_adaptive_info and the pass
+ *    buffer's test hooks; rt_accum_opts keeps its layout, the switch is scene state) */
 #define RT_ABI_VERSION 5
 
 enum {
@@ -247,6 +249,43 @@ int rt_accumulate_reset(rt_scene* s);
 /* out4 = {samples held, W, H, restarts so far (rt_accumulate_reset, restart = 1 and the scene's
  * own changes, each counted when it dropped at least one sample)} */
 int rt_accumulate_info(const rt_scene* s, int32_t out4[4]);
+
+/* Adaptive refinement (opt-in scene state, as rt_query_set_order).  This integrator is
+ * Whitted-style: a later sample differs from sample 0 only by its sub-pixel offset, so it changes
+ * a pixel only where the image has an edge.  With the mode on, an accumulation traces sample 0
+ * everywhere, decides once which tiles have an edge, and traces and folds every later sample for
+ * those tiles only.
+ * A tile is the pixel group of a whole-frame 1-spp launch (8 x 8 pixels, clipped to the canvas).
+ * A pixel is an edge pixel when some pixel of its 8-neighbourhood inside the canvas differs from
+ * it by more than `threshold` in some channel of sample 0's radiance clamped to 1 (float32; a NaN
+ * difference flags nothing; hit ids take no part); a tile is needed when it holds an edge pixel,
+ * so a contrast across a tile border flags both tiles.  The mask is decided right after sample
+ * 0's fold and dropped with the sums at every restart.
+ * After a call that leaves n samples held, a pixel of a needed tile is rt_render(spp = n)'s pixel
+ * and a pixel of any other tile is rt_render(spp = 1)'s, both bit for bit; hit ids are sample
+ * 0's; *n_samples and rt_accumulate_info[0] are the samples the needed tiles hold.  With no
+ * needed tile later samples launch nothing and n still counts up.  Mode 0 is rt_accumulate as
+ * documented above, unchanged. */
+/* mode 0: uniform (default); 1: adaptive.  threshold >= 0, finite (ignored with mode 0).
+ * Host state, no device needed.  A call that changes mode or threshold while samples are held
+ * drops them (counted as a restart); a call that changes nothing does nothing.
+ * RT_ERR_ARG: other modes, threshold negative / NaN / inf. */
+int rt_accumulate_set_adaptive(rt_scene* s, int mode, float threshold);
+#define RT_ADAPTIVE_THRESHOLD_DEFAULT (8.0f / 255.0f)
+/* out8 = {mode, tile_w, tile_h, n_tx, n_ty, needed tiles (-1: no mask yet), tiles the last
+ * pass's trace launch was given (n_tx*n_ty for sample 0 and for a kernel that cannot run from
+ * tile lists: an unusable ordered tree, brute force over more than 64 instances), 0};
+ * threshold may be NULL.  need (may be NULL): need_cap >= n_tx*n_ty bytes, 1 = needed, copied from
+ * the device; RT_ERR_STATE if asked for before a mask exists, RT_ERR_ARG if too small. */
+int rt_accumulate_adaptive_info(const rt_scene* s, int32_t out8[8], float* threshold, uint8_t* need, int64_t need_cap);
+/* Test hooks: fill the scene's pass buffer with a 32-bit pattern / copy it out (W*H float4),
+ * after every frame in flight.  RT_ERR_STATE before the first rt_accumulate. */
+int rt_accumulate_pass_fill(rt_scene* s, uint32_t bits);
+int rt_accumulate_pass_read(rt_scene* s, float* dst, int64_t cap_floats);
+/* Test hook: the current frame slot's scheduling-history state, host state only: out12 = {parity,
+ * the history slot a pending BVH build zeroes (-1: none), capacity, frame slot, the history key's
+ * eight values (-1: none yet)}.  A refinement pass of the adaptive mode leaves parity, capacity, slot and key as they were. */
+int rt_scene_history_info(const rt_scene* s, int32_t out12[12]);
 
 /* ---- ray queries: closest hit or occlusion for caller-supplied rays ----
  * The reference has no counterpart: its cast_ray (scene.cu:42-73) is reachable only through the

@@ -243,6 +243,11 @@ inline void use_devices(renv::gpu::Scene* scene, const std::vector<int>& devices
     rtamd_detail::check(rt_scene_set_devices(scene->handle(), devices.data(), (int)devices.size(),
                                              n_ranks > 0 ? n_ranks : (int)devices.size()), "use_devices");
 }
+// Build extension (rt_accumulate_set_adaptive): progressive refinement of `scene` resamples only
+// the tiles that have an edge at `threshold`; the other tiles keep the 1-spp frame.
+inline void set_accumulate_adaptive(renv::gpu::Scene* scene, bool on = true, float threshold = RT_ADAPTIVE_THRESHOLD_DEFAULT) {
+    rtamd_detail::check(rt_accumulate_set_adaptive(scene->handle(), on ? 1 : 0, threshold), "set_accumulate_adaptive");
+}
 // raytracer.cu:91-100: one-pixel trace with the reference's event log on stdout.
 inline void debug_cast(renv::gpu::Scene* scene, int x, int y) {
     std::vector<char> buf(1 << 16);
