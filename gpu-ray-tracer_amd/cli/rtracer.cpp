@@ -3,6 +3,7 @@
 //   rtracer -c world8.json [-b] [-r] [-s] [-d DIM] [--frames N] [--spp K]
 //           [--width W --height H] [--out frame.ppm] [--debug X,Y] [--textures [ATLAS.png]]
 //           [--gpus N [--ranks R]] [--in-flight D] [--pick X,Y] [--accumulate N [--adaptive [THR]]]
+//           [--occlusion N [--radius R]]
 //
 // -c config (worldN.json), -b benchmark (one timed frame, "Time: X ms" as main.cc:210-216),
 // -r unoptimize (brute force, no BVH), -d kernel dimension (accepted; the HIP path
@@ -26,6 +27,9 @@
 // --adaptive [THR] (with --accumulate only; rt_accumulate_set_adaptive): after sample 0 only the
 // 8 x 8 tiles with a contrast above THR (default 8/255) are refined; the others keep the 1-spp
 // frame.  Prints "Adaptive: K of T tiles refined".
+// --occlusion N [--radius R] (build extension, rt_occlusion): the ambient-occlusion pass -- N
+// directions per pixel within R (default +inf: sky visibility); --out writes the visibility as a
+// grey frame the way --accumulate writes its frame.  -b prints the call's time.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -44,7 +48,7 @@ static void usage() {
                  "usage: rtracer -c CONFIG [-b] [-r] [-s] [-d DIM] [--frames N] [--spp K] [--width W --height H]\n"
                  "               [--out FILE.ppm] [--debug X,Y] [--textures [ATLAS.png]] [--gpus N [--ranks R]]\n"
                  "               [--in-flight D [--readback] [--overlap stream|half|full]] [--pick X,Y]\n"
-                 "               [--accumulate N [--adaptive [THR]]]\n");
+                 "               [--accumulate N [--adaptive [THR]]] [--occlusion N [--radius R]]\n");
 }
 
 static bool write_ppm(const char* path, const uint32_t* px, int w, int h) {
@@ -68,7 +72,8 @@ int main(int argc, char** argv) {
     bool bench = false, unopt = false, serial = false, textures = false, readback = false, adaptive = false;
     float adaptive_thr = RT_ADAPTIVE_THRESHOLD_DEFAULT;
     std::string atlas, overlap = "stream";
-    int dim = 16, frames = 1, spp = 1, width = 0, height = 0, dbg_x = -1, dbg_y = -1, pick_x = -1, pick_y = -1, gpus = 1, ranks = 0, in_flight = 0, accumulate = 0;
+    int dim = 16, frames = 1, spp = 1, width = 0, height = 0, dbg_x = -1, dbg_y = -1, pick_x = -1, pick_y = -1, gpus = 1, ranks = 0, in_flight = 0, accumulate = 0, occlusion = 0;
+    float radius = -1.0f;                                  // (< 0: not given)
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto val = [&](const char* name) -> const char* {
@@ -89,6 +94,13 @@ int main(int argc, char** argv) {
         else if (a == "--ranks") ranks = std::atoi(val("--ranks"));
         else if (a == "--in-flight") in_flight = std::atoi(val("--in-flight"));
         else if (a == "--accumulate") { accumulate = std::atoi(val("--accumulate")); if (accumulate < 1) { usage(); return 2; } }
+        else if (a == "--occlusion") { occlusion = std::atoi(val("--occlusion")); if (occlusion < 1) { usage(); return 2; } }
+        else if (a == "--radius") {
+            char* end = nullptr;
+            const char* v = val("--radius");
+            radius = std::strtof(v, &end);
+            if (end == v || *end || !(radius > 0.0f)) { usage(); return 2; }
+        }
         else if (a == "--adaptive") {
             adaptive = true;
             if (i + 1 < argc && argv[i + 1][0] != '-') {
@@ -120,6 +132,7 @@ int main(int argc, char** argv) {
     }
     if (frames < 1 || spp < 1 || gpus < 1 || ranks < 0 || in_flight < 0 || in_flight > 8) { usage(); return 2; }
     if (adaptive && accumulate < 1) { std::fprintf(stderr, "--adaptive needs --accumulate N\n"); usage(); return 2; }
+    if (radius > 0.0f && occlusion < 1) { std::fprintf(stderr, "--radius needs --occlusion N\n"); usage(); return 2; }
     // frames in flight use a stream each: HIP maps streams round-robin onto GPU_MAX_HW_QUEUES
     // hardware queues (4 by default), and streams sharing a queue serialise.
     // The HIP runtime reads it when librt_amd.so's kernels are registered, before main: set it
@@ -154,6 +167,33 @@ int main(int argc, char** argv) {
         }
         if (inst >= 0) std::printf("pick %d %d inst %d tri %d t %.9g\n", pick_x, pick_y, inst, tri, (double)t);
         else std::printf("pick %d %d miss\n", pick_x, pick_y);
+        rt_scene_free(handle);
+        return 0;
+    }
+    if (occlusion > 0) {                                   // the ambient-occlusion pass, one call
+        int32_t info[10];
+        rtamd_detail::check(rt_scene_info(handle, info), "rt_scene_info");
+        std::vector<uint32_t> frame((size_t)info[0] * info[1]);
+        rt_occlusion_opts o;
+        rt_occlusion_opts_default(&o);
+        o.samples = occlusion; o.use_bvh = unopt ? 0 : 1;
+        if (radius > 0.0f) o.radius = radius;
+        o.host_outputs = 1; o.rgba = frame.data();
+        int n = 0;
+        auto from = std::chrono::high_resolution_clock::now();
+        if (rt_occlusion(handle, &o, &n) != RT_OK) {
+            std::fprintf(stderr, "occlusion failed: %s\n", rt_last_error());
+            rt_scene_free(handle);
+            return 1;
+        }
+        auto to = std::chrono::high_resolution_clock::now();
+        if (bench) std::printf("Time: %g ms\n", std::chrono::duration<double, std::milli>(to - from).count());
+        std::printf("Occlusion: %d samples\n", n);
+        if (!out.empty() && !write_ppm(out.c_str(), frame.data(), info[0], info[1])) {
+            std::fprintf(stderr, "cannot write %s\n", out.c_str());
+            rt_scene_free(handle);
+            return 1;
+        }
         rt_scene_free(handle);
         return 0;
     }

@@ -14,6 +14,7 @@
 #include "rt_adapt.h"
 #include "rt_bvh.h"
 #include "rt_math.h"
+#include "rt_occl.h"
 #include "rt_raykey.h"
 #include "rt_scene.h"
 
@@ -190,6 +191,26 @@ struct QueryParams {
     const uint32_t* order;                      // ORD kernels: lane l of chunk c traces ray order[64 c + l] (a permutation of [0, n))
 };
 
+// The ambient-occlusion kernels' arguments (rt_occlusion): occl_surface_kernel (cam -> surf),
+// occlusion_kernel (surf, table -> count and, resolving, the outputs) and occl_rays_kernel (the
+// test hook: sample k0's rays -> rays).  Device pointers.  The tracing kernels read it in place
+// (oparams(), as qparams()).
+struct OcclParams {
+    rt::DCamera cam;
+    int W, H;
+    int map;                  // OCCL_MAP_* (rt_plan.h): which pixel a wave's lane takes
+    int n_waves;              // occlusion_plan's: waves with a pixel
+    int k0, samples;          // this launch adds samples k0 ... k0 + samples - 1
+    int resolve, n_total;     // 1: write the outputs for the n_total samples held after this launch
+    float radius, bias;
+    float any_margin, zcut_scene;               // as QueryParams'
+    const rtm::V3* table;     // [AO_MAX_SAMPLES] directions (rto::ao_direction)
+    float4* surf;             // [2 W H] (p, 1 where the primary hits else 0), (faced n, 0); zeros at a miss
+    int* count;               // [W H] occluded samples so far (not read when k0 = 0)
+    float* visibility; int* occluded; uint32_t* rgba;   // each may be null
+    float* rays;              // occl_rays_kernel: [6 W H]
+};
+
 }  // namespace rtd
 
 #include "rt_plan.h"   // the LDS layout and MODE bits; the launch plan (trace_variant_key and the rest)
@@ -246,6 +267,13 @@ hipError_t launch_accum_lists(const unsigned char* need, int n_tiles, int* live,
 hipError_t launch_accum_fold_tiles(const float4* pass, float4* sum_r, float4* sum_c, const unsigned char* need,
                                    const rtad::TileGrid& t, int n_before, bool resolve, uint32_t* rgba, float4* radiance,
                                    hipStream_t st, hipEvent_t e0, hipEvent_t e1);
+// rt_occlusion's kernels.  S: rt_query's view of the scene (camera-ray shortcuts off).
+// launch_occl_surface: the surface record of every pixel's primary hit; launch_occlusion: P.samples
+// more directions into the counts (null fn in the plan's table: a programming error, hipErrorInvalidValue);
+// launch_occl_rays: the rays of sample P.k0 as occlusion_kernel forms them, no tracing.
+hipError_t launch_occl_surface(const OcclPlan& plan, OcclParams& P, SceneView& S, hipStream_t st, hipEvent_t e0, hipEvent_t e1);
+hipError_t launch_occlusion(const OcclPlan& plan, OcclParams& P, SceneView& S, hipStream_t st, hipEvent_t e0, hipEvent_t e1);
+hipError_t launch_occl_rays(OcclParams& P, hipStream_t st);
 void launch_unpermute(const uint32_t* g, uint32_t* out, int W, int H, int N, int rows_max, hipStream_t st);
 void launch_profile_marker(int tag, hipStream_t st);
 void launch_copy_gate(const unsigned* flag, unsigned long long max_ticks, hipStream_t st);

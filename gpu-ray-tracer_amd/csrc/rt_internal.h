@@ -208,6 +208,19 @@ struct rt_scene {
             release_adaptive();
         }
     } accum;
+    // rt_occlusion: the scene-owned direction table, the surface record of every pixel's primary hit
+    // (2 float4 a pixel, built with sample 0) and the counts of occluded samples, `n` samples held;
+    // what sample 0 saw (generations, radius, bias).  Allocated on first use, freed with the scene.
+    struct Occl {
+        rtm::V3* d_table = nullptr;
+        float4* d_surf = nullptr;
+        int32_t* d_count = nullptr;
+        size_t px = 0;
+        int n = 0, restarts = 0;
+        unsigned inst_gen = 0, cam_gen = 0;
+        float radius = 0.0f, bias = 0.0f;
+        void release() { rti::dfree(d_table); rti::dfree(d_surf); rti::dfree(d_count); px = 0; n = 0; }
+    } occl;
     static constexpr int MAX_SLOTS = RT_MAX_SLOTS;
     rti::FrameSlot slots[MAX_SLOTS];             // slots[0, n_slots) are in rotation (FrameSlot)
     int n_slots = 1, cur_slot = 0;

@@ -2317,6 +2317,156 @@ __global__ __launch_bounds__(KEY_BLOCK) void ray_key_kernel(QueryParams Q, rtk::
 }
 
 // ---------------------------------------------------------------------------
+// Ambient occlusion (rt_occlusion; rt_occl.h): how much of the hemisphere above
+// every pixel's primary hit is unoccluded within a radius.  Three kernels beside the query
+// kernels, none of which touches them: the surface record once per accumulation, the occlusion
+// rays of a launch's samples, and the test hook that writes one sample's rays out.  One pixel
+// per lane, 256-thread blocks, nothing staged (the small form of query_kernel); the scene comes
+// as rt_query's (camera-ray shortcuts off).  TREE as query_kernel's.
+// ---------------------------------------------------------------------------
+typedef __attribute__((address_space(4))) const OcclParams KOP;
+__device__ __forceinline__ KOP& oparams() {                    // read in place, as qparams()
+    KOP* p = (KOP*)__builtin_amdgcn_kernarg_segment_ptr();     // the first kernel argument
+    asm volatile("" : "+s"(p));
+    return *p;
+}
+// The pixel (row-major index, or -1: none) of lane `lane` of wave g.  OCCL_MAP_ROW: pixels
+// [64 g, 64 g + 64) of the frame; OCCL_MAP_TILE: the 8 x 8 tile g (n_tx tiles a row), lane l its
+// pixel (l & 7, l >> 3), clipped to the canvas.  g is wave-uniform: its division is scalar.
+__device__ __forceinline__ long long occl_pixel(int map, int W, int H, int g, int lane) {
+    if (map == OCCL_MAP_TILE) {
+        const int n_tx = (W + 7) >> 3, ty = g / n_tx, tx = g - ty * n_tx;
+        const int x = 8 * tx + (lane & 7), y = 8 * ty + (lane >> 3);
+        return (x < W && y < H) ? (long long)y * W + x : -1;
+    }
+    const long long i = (long long)g * 64 + lane;
+    return i < (long long)W * H ? i : -1;
+}
+__device__ __forceinline__ int occl_wave() {
+    return __builtin_amdgcn_readfirstlane((int)blockIdx.x * (OCCL_BLOCK / 64) + (int)(threadIdx.x >> 6));
+}
+
+// The surface record: pixel i's primary hit as query_kernel's pixel mode finds it (camera_at's
+// sample-0 ray, the closest hit with nothing cut but the zero-axis leaves, hit_normal), then
+// p = o + t d and the normal faced to the viewer.  surf[2 i] = (p, 1), surf[2 i + 1] = (n, 0);
+// a pixel whose primary misses holds zeros.
+template <int TREE>
+__global__ __launch_bounds__(OCCL_BLOCK) void occl_surface_kernel(OcclParams P_arg, SceneView S) {
+    (void)P_arg;
+    constexpr bool FT = TREE == QT_ORDERED, BRUTE = TREE == QT_BRUTE;
+    const BvhRefs bv = stage_bvh<false, FT, false, BRUTE>(S, nullptr);
+    const int g = occl_wave();
+    if (g >= oparams().n_waves) return;                        // (wave-uniform)
+    const long long i = occl_pixel(oparams().map, oparams().W, oparams().H, g, (int)(threadIdx.x & 63));
+    const bool in = i >= 0;
+    Ray r{v3(0, 0, 0), v3(0, 0, 1)};
+    bool ok = in;
+    if (in) {
+        const int W = oparams().W, y = (int)(i / W), x = (int)(i - (long long)y * W);
+        r = camera_at(kld(oparams().cam), (float)x, (float)y);
+        ok = rtk::ray_traceable(r);
+        if (!ok) r = Ray{v3(0, 0, 0), v3(0, 0, 1)};
+    }
+    Best b;
+    b.time = INFINITY; b.inst = -1; b.tri = -1; b.u = 0.0f; b.v = 0.0f;
+    float zc = -1.0f;                                          // the zero-axis cut's per-ray slack (query_kernel)
+    if (FT && oparams().zcut_scene >= 0.0f) {
+        const float oa = fmaxf(fabsf(r.o.x), fmaxf(fabsf(r.o.y), fabsf(r.o.z)));
+        if (oa <= 0x1p64f) zc = oparams().zcut_scene + 0x1p-14f * oa;
+    }
+    WaveCounters wc{0, 0, 0, 0};
+    closest_hit<false, false, FT, false, false, BRUTE>(S, bv, ok, r, b, wc, -1.0f, INFINITY, zc);
+    if (!in) return;
+    float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), c = a;
+    if (ok && b.time < INFINITY) {
+        int mat = 0;
+        const V3 nrm = hit_normal(S, bv, b, mat);
+        (void)mat;
+        const V3 p = rto::surface_point(r.o, r.d, b.time), n = rto::faced(nrm, r.d);
+        a = make_float4(p.x, p.y, p.z, 1.0f);
+        c = make_float4(n.x, n.y, n.z, 0.0f);
+    }
+    float4* surf = oparams().surf;
+    surf[2 * i] = a; surf[2 * i + 1] = c;
+}
+
+// Samples k0 ... k0 + samples - 1 of every pixel.  The frame (origin p + bias n, t1, t2, n) is
+// formed once and stays in registers; per sample the table entry is a scalar load (k is
+// wave-uniform), the ray is rmath::Ray(origin, raw direction) as query_kernel makes a caller's,
+// and one closest_hit with the occlusion exit answers it as rt_query(any_hit = 1, tmax = radius)
+// does: accept THRESH <= t < radius, the same early-exit margin and per-ray zero-axis cut.  A ray
+// rt_query would reject counts as not occluded, and so does every sample of a pixel without a
+// primary hit.  After the loop one read-modify-write of the count (k0 = 0: the count starts at
+// zero and is not read); `resolve` (the call's last launch) writes the outputs for n_total samples.
+// No ray goes to memory.
+template <int TREE>
+__global__ __launch_bounds__(OCCL_BLOCK) void occlusion_kernel(OcclParams P_arg, SceneView S) {
+    (void)P_arg;
+    constexpr bool FT = TREE == QT_ORDERED, BRUTE = TREE == QT_BRUTE;
+    const BvhRefs bv = stage_bvh<false, FT, false, BRUTE>(S, nullptr);
+    const int g = occl_wave();
+    if (g >= oparams().n_waves) return;                        // (wave-uniform)
+    const long long i = occl_pixel(oparams().map, oparams().W, oparams().H, g, (int)(threadIdx.x & 63));
+    const bool in = i >= 0;
+    rto::Frame f = rto::make_frame(v3(0, 0, 0), v3(0, 0, 1));
+    bool live = false;
+    if (in) {
+        const float4 a = oparams().surf[2 * i], c = oparams().surf[2 * i + 1];
+        live = a.w != 0.0f;
+        f = rto::make_frame(v3(a.x, a.y, a.z), v3(c.x, c.y, c.z));
+    }
+    f.p = rto::ray_origin(f, oparams().bias);                  // every sample's origin
+    float zc = -1.0f;
+    if (FT && oparams().zcut_scene >= 0.0f) {
+        const float oa = fmaxf(fabsf(f.p.x), fmaxf(fabsf(f.p.y), fabsf(f.p.z)));
+        if (oa <= 0x1p64f) zc = oparams().zcut_scene + 0x1p-14f * oa;
+    }
+    int cnt = 0;
+    WaveCounters wc{0, 0, 0, 0};
+    const int k0 = oparams().k0, k1 = k0 + oparams().samples;
+    for (int k = k0; k < k1; k++) {
+        const V3 dk = ldc(oparams().table, k);
+        const V3 raw = rto::raw_direction(f, dk);
+        Ray r = make_ray(f.p, raw);                            // Ray ctor (geometry.h:216)
+        const bool ok = live && rtk::finite3(raw) && rtk::ray_traceable(r);
+        if (!ok) r = Ray{v3(0, 0, 0), v3(0, 0, 1)};            // nothing non-finite enters the wave's arithmetic
+        const float tm = oparams().radius;
+        float occl = -1.0f;
+        if (oparams().any_margin >= 0.0f && tm > 0.0f) occl = tm * (1.0f - oparams().any_margin);
+        Best b;
+        b.time = INFINITY; b.inst = -1; b.tri = -1; b.u = 0.0f; b.v = 0.0f;
+        closest_hit<false, false, FT, false, false, BRUTE>(S, bv, ok, r, b, wc, occl, INFINITY, zc);
+        cnt += (ok && b.time < tm) ? 1 : 0;
+    }
+    if (!in) return;
+    KOP& P = oparams();
+    if (k0 > 0) cnt += P.count[i];
+    P.count[i] = cnt;
+    if (P.resolve) {
+        const float vis = rto::visibility(cnt, P.n_total);
+        if (P.visibility) P.visibility[i] = vis;
+        if (P.occluded) P.occluded[i] = cnt;
+        if (P.rgba) P.rgba[i] = rto::grey(vis);
+    }
+}
+
+// Test hook (rt_occlusion_rays): sample k0's ray of every pixel as occlusion_kernel forms it,
+// origin and RAW direction (before the Ray constructor), zeros where the primary misses.
+__global__ __launch_bounds__(OCCL_BLOCK) void occl_rays_kernel(OcclParams P) {
+    const long long i = (long long)blockIdx.x * OCCL_BLOCK + threadIdx.x;
+    if (i >= (long long)P.W * P.H) return;
+    const float4 a = P.surf[2 * i], c = P.surf[2 * i + 1];
+    V3 o = v3(0, 0, 0), d = v3(0, 0, 0);
+    if (a.w != 0.0f) {
+        const rto::Frame f = rto::make_frame(v3(a.x, a.y, a.z), v3(c.x, c.y, c.z));
+        o = rto::ray_origin(f, P.bias);
+        d = rto::raw_direction(f, P.table[P.k0]);
+    }
+    float* ro = P.rays + 6 * i;
+    ro[0] = o.x; ro[1] = o.y; ro[2] = o.z; ro[3] = d.x; ro[4] = d.y; ro[5] = d.z;
+}
+
+// ---------------------------------------------------------------------------
 // BVH build: ropt::gpu::BVH::BVH (bvh.cu:74-91) + create_boxes (raytracer.cu:54-74)
 // in one workgroup.  Output: heap-ordered nodes[1 .. 2n-1].
 // ---------------------------------------------------------------------------
@@ -2879,6 +3029,40 @@ hipError_t launch_accum_fold_tiles(const float4* pass, float4* sum_r, float4* su
     void* args[] = {&pass, &sum_r, &sum_c, &need, &tg, &n_before, &res, &rgba, &radiance};
     return hipExtLaunchKernel((const void*)accum_fold_tiles_kernel, dim3((unsigned)((n + TILE_BLOCK / 64 - 1) / (TILE_BLOCK / 64))),
                               dim3(TILE_BLOCK), args, 0, st, e0, e1, 0);
+}
+
+// The ambient-occlusion kernels (rt_occlusion): one surface and one occlusion kernel per tree form,
+// named here once.  occlusion_plan (rt_plan.h) decides which a call gets.
+struct OcclEntry { int tree; const void* surface; const void* occlusion; };
+#define OCK(TREE) OcclEntry{TREE, (const void*)occl_surface_kernel<TREE>, (const void*)occlusion_kernel<TREE>}
+static const OcclEntry occl_kernels[] = {OCK(QT_ORDERED), OCK(QT_HEAP), OCK(QT_BRUTE)};
+#undef OCK
+static const OcclEntry* occl_entry(int tree) {
+    for (const OcclEntry& e : occl_kernels)
+        if (e.tree == tree) return &e;
+    return nullptr;
+}
+
+hipError_t launch_occl_surface(const OcclPlan& plan, OcclParams& P, SceneView& S, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
+    const OcclEntry* e = occl_entry(plan.tree);
+    if (!e) return hipErrorInvalidValue;
+    void* args[] = {&P, &S};
+    return hipExtLaunchKernel(e->surface, dim3(plan.blocks), dim3(plan.block), args, 0, st, e0, e1, 0);
+}
+
+hipError_t launch_occlusion(const OcclPlan& plan, OcclParams& P, SceneView& S, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
+    const OcclEntry* e = occl_entry(plan.tree);
+    if (!e) return hipErrorInvalidValue;
+    void* args[] = {&P, &S};
+    return hipExtLaunchKernel(e->occlusion, dim3(plan.blocks), dim3(plan.block), args, 0, st, e0, e1, 0);
+}
+
+hipError_t launch_occl_rays(OcclParams& P, hipStream_t st) {
+    const long long px = (long long)P.W * P.H;
+    if (px <= 0) return hipSuccess;
+    void* args[] = {&P};
+    return hipExtLaunchKernel((const void*)occl_rays_kernel, dim3((unsigned)((px + OCCL_BLOCK - 1) / OCCL_BLOCK)), dim3(OCCL_BLOCK),
+                              args, 0, st, nullptr, nullptr, 0);
 }
 
 void launch_unpermute(const uint32_t* g, uint32_t* out, int W, int H, int N, int rows_max, hipStream_t st) {

@@ -1,0 +1,69 @@
+// rt_occl.h — the per-pixel arithmetic of the ambient-occlusion pass (rt_occlusion), shared by
+// occl_surface_kernel / occlusion_kernel / occl_rays_kernel (rt_kernels.hip) and the host test
+// (tests/occl_host.cpp): one definition of the surface point, the facing, the tangent frame, the
+// raw direction of a sample and the resolve, as rt_accum.h is for rt_accumulate's fold.  Every
+// float step below is a single float32 + - x / (the build has no contraction), in the order
+// written; host and device agree bit for bit.  The direction table's generation is host only.
+//
+//   p  = o + t d                      per component: t x d, then + o  (rtm::at)
+//   n  = the hit's normal, each component negated when dot(n, d) > 0 (rtm::dot: ((0 + x x) + y y) + z z)
+//   s  = copysignf(1, n.z)
+//   a  = -1 / (s + n.z)               (s + n.z) is in [1, 2] or [-2, -1]: n.z = -1 gives a = 1/2, finite
+//   b  = (n.x x n.y) x a
+//   t1 = (1 + ((s x n.x) x n.x) x a,  s x b,              -(s x n.x))
+//   t2 = (b,                          s + (n.y x n.y) x a, -n.y)
+//   sample k's raw direction = (x_k t1 + y_k t2) + z_k n, per component ((x_k x t1.c) + (y_k x t2.c)) + z_k x n.c
+//   sample k's origin        = p + bias n, per component (bias x n.c) + p.c
+//   visibility = 1 - (float)count / (float)n           (correctly rounded division, then the subtraction)
+#pragma once
+
+#include <stdint.h>
+
+#include "rt_accum.h"
+
+namespace rto {
+
+using rtm::V3;
+using rtm::V4;
+
+constexpr int AO_MAX_SAMPLES = 1024;       // RT_AO_MAX_SAMPLES (rt_amd.h): the direction table's length
+
+struct Frame { V3 p, n, t1, t2; };
+
+RT_HD V3 surface_point(V3 o, V3 d, float t) { return o + t * d; }
+RT_HD V3 faced(V3 n, V3 d) { return rtm::dot(n, d) > 0.0f ? rtm::v3(-n.x, -n.y, -n.z) : n; }
+RT_HD void tangent_frame(V3 n, V3& t1, V3& t2) {
+    const float s = copysignf(1.0f, n.z);
+    const float a = -1.0f / (s + n.z);
+    const float b = (n.x * n.y) * a;
+    t1 = rtm::v3(1.0f + ((s * n.x) * n.x) * a, s * b, -(s * n.x));
+    t2 = rtm::v3(b, s + (n.y * n.y) * a, -n.y);
+}
+RT_HD Frame make_frame(V3 p, V3 n) {
+    Frame f;
+    f.p = p; f.n = n;
+    tangent_frame(n, f.t1, f.t2);
+    return f;
+}
+RT_HD V3 ray_origin(const Frame& f, float bias) { return f.p + bias * f.n; }
+RT_HD V3 raw_direction(const Frame& f, V3 dk) { return (dk.x * f.t1 + dk.y * f.t2) + dk.z * f.n; }
+
+RT_HD float visibility(int count, int n) { return 1.0f - (float)count / (float)n; }
+// visibility as an opaque grey through Color's truncation (rta::pack)
+RT_HD uint32_t grey(float vis) { return rta::pack(rtm::v4(vis, vis, vis, 1.0f)); }
+
+// Host only.  Entry k of the direction table: point k of the R2 sequence (rt::spp_offset's constants, in
+// double; k = 0 -> the pole) taken to the unit disk by (u, v) -> sqrt(u) (cos 2 pi v, sin 2 pi v)
+// and lifted to the hemisphere, z = sqrt(max(0, 1 - x^2 - y^2)): cosine-weighted.  Double
+// throughout, each component rounded to float32 once.
+inline void ao_direction(int k, float out3[3]) {
+    const double a1 = 0.7548776662466927, a2 = 0.5698402909980532;
+    double u = (double)k * a1, v = (double)k * a2;
+    u -= floor(u); v -= floor(v);
+    const double r = sqrt(u), phi = 6.283185307179586476925286766559 * v;
+    const double x = r * cos(phi), y = r * sin(phi);
+    const double zz = 1.0 - x * x - y * y;
+    out3[0] = (float)x; out3[1] = (float)y; out3[2] = (float)sqrt(zz > 0.0 ? zz : 0.0);
+}
+
+}  // namespace rto

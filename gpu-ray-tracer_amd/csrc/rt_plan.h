@@ -377,6 +377,38 @@ inline QueryKey query_plan(long long n_rays, const SceneView& S, bool any_hit, b
     return k;
 }
 
+// ---- The ambient-occlusion pass (rt_occlusion): its kernels' tree form and grid
+// The tree form is query_plan's rule; the form is the small one only (256-thread blocks, nothing
+// staged: DESIGN §3.5 found no crossover to the persistent form).  One pixel per lane; a wave takes
+// 64 consecutive pixels of the row-major frame (OCCL_MAP_ROW: runs continue into the next row) or
+// an 8 x 8 tile clipped to the canvas (OCCL_MAP_TILE).  Measured on world8_stress 1920 x 1080
+// (profiles/occlusion/bench.txt); map < 0: the default.  A call's samples go in
+// launches of at most OCCL_LAUNCH_SAMPLES directions, so that no single dispatch runs for long.
+enum : int { OCCL_MAP_ROW = 0, OCCL_MAP_TILE = 1 };
+#ifndef RT_OCCL_MAP_DEFAULT
+#define RT_OCCL_MAP_DEFAULT OCCL_MAP_TILE
+#endif
+constexpr int OCCL_BLOCK = 256;
+constexpr int OCCL_LAUNCH_SAMPLES = 64;
+struct OcclPlan {
+    int tree;                 // QT_*
+    int map;                  // OCCL_MAP_*
+    int n_waves;              // waves with a pixel: 64-pixel runs, or tiles
+    int block, blocks;        // the launch: dim3(blocks), dim3(block)
+};
+inline OcclPlan occlusion_plan(int W, int H, const SceneView& S, int map = -1) {
+    OcclPlan p{};
+    p.tree = query_plan((long long)W * H, S, true, false, 0, 0).tree;
+    p.map = map == OCCL_MAP_ROW || map == OCCL_MAP_TILE ? map : RT_OCCL_MAP_DEFAULT;
+    const long long px = (long long)W * H;
+    const long long waves = p.map == OCCL_MAP_TILE ? (long long)((W + 7) / 8) * ((H + 7) / 8) : (px + 63) / 64;
+    constexpr int BLOCK_WAVES = OCCL_BLOCK / 64;
+    p.n_waves = (int)std::min<long long>(waves, INT32_MAX);
+    p.block = OCCL_BLOCK;
+    p.blocks = (int)std::max(1ll, (waves + BLOCK_WAVES - 1) / BLOCK_WAVES);
+    return p;
+}
+
 // ---- The coherence order of a batch (rt_query_set_order): whether rt_query sorts the batch
 // by ray key (rt_raykey.h) before it traces, the key bits the sort looks at, and the scene's
 // scratch for it: keys (8 B) and ray indices (4 B), double-buffered, each buffer rounded up to

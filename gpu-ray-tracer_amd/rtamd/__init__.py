@@ -47,11 +47,14 @@ SYMBOLS = [
     "rt_accum_opts_default", "rt_accumulate", "rt_accumulate_reset", "rt_accumulate_info",
     "rt_accumulate_set_adaptive", "rt_accumulate_adaptive_info", "rt_accumulate_pass_fill", "rt_accumulate_pass_read",
     "rt_scene_history_info",
+    "rt_occlusion_opts_default", "rt_occlusion", "rt_occlusion_reset", "rt_occlusion_info", "rt_ao_direction",
+    "rt_occlusion_rays",
     "rt_scene_set_shadow_hints", "rt_scene_shadow_hints_fill", "rt_scene_shadow_hint_code",
     "rt_scene_shadow_hint_counters", "rt_scene_shadow_hints_read",
 ]
 RT_QUERY_ORDER_CALLER, RT_QUERY_ORDER_SORTED = 0, 1
 RT_ADAPTIVE_THRESHOLD_DEFAULT = 8.0 / 255.0
+RT_AO_MAX_SAMPLES, RT_AO_BIAS_DEFAULT = 1024, 1e-3
 
 
 class RtError(RuntimeError):
@@ -74,6 +77,13 @@ class AccumOpts(ctypes.Structure):
                 ("textures", ctypes.c_int), ("restart", ctypes.c_int), ("host_outputs", ctypes.c_int),
                 ("rgba", ctypes.c_void_p), ("radiance", ctypes.c_void_p), ("hit_inst", ctypes.c_void_p),
                 ("hit_tri", ctypes.c_void_p)]
+
+
+class OcclusionOpts(ctypes.Structure):
+    _fields_ = [("samples", ctypes.c_int), ("radius", ctypes.c_float), ("bias", ctypes.c_float),
+                ("use_bvh", ctypes.c_int), ("rebuild_bvh", ctypes.c_int), ("restart", ctypes.c_int),
+                ("host_outputs", ctypes.c_int),
+                ("visibility", ctypes.c_void_p), ("occluded", ctypes.c_void_p), ("rgba", ctypes.c_void_p)]
 
 
 class QueryOpts(ctypes.Structure):
@@ -195,6 +205,14 @@ def lib():
         L.rt_accumulate_pass_fill.argtypes = [vp, ctypes.c_uint32]
         L.rt_accumulate_pass_read.argtypes = [vp, vp, ctypes.c_int64]
         L.rt_scene_history_info.argtypes = [vp, vp]
+    if hasattr(L, "rt_occlusion"):              # (absent from libraries before the occlusion pass: A/B runs)
+        L.rt_occlusion_opts_default.argtypes = [ctypes.POINTER(OcclusionOpts)]
+        L.rt_occlusion_opts_default.restype = None
+        L.rt_occlusion.argtypes = [vp, ctypes.POINTER(OcclusionOpts), ctypes.POINTER(ip)]
+        L.rt_occlusion_reset.argtypes = [vp]
+        L.rt_occlusion_info.argtypes = [vp, vp]
+        L.rt_ao_direction.argtypes = [ip, vp]
+        L.rt_occlusion_rays.argtypes = [vp, ip, vp, ctypes.c_int64]
     if hasattr(L, "rt_query_set_order"):        # (absent from libraries before the coherence sort: A/B runs)
         L.rt_query_set_order.argtypes = [vp, ip]
         L.rt_query_last.argtypes = [vp, vp, vp, vp, ctypes.c_int64]
@@ -239,6 +257,13 @@ def spp_offset(k):
     dx, dy = ctypes.c_float(), ctypes.c_float()
     _check(lib().rt_spp_offset(k, ctypes.byref(dx), ctypes.byref(dy)))
     return dx.value, dy.value
+
+
+def ao_direction(k):
+    """Entry k of rt_occlusion's direction table, float32[3] (rt_ao_direction)."""
+    d = np.zeros(3, np.float32)
+    _check(lib().rt_ao_direction(int(k), _ptr(d)))
+    return d
 
 
 def profile_marker(tag, stream=None):
@@ -603,6 +628,61 @@ class Scene:
         """Test hook: the pass buffer, (H, W, 4) float32 (rt_accumulate_pass_read)."""
         a = np.zeros((self.height, self.width, 4), np.float32)
         _check(lib().rt_accumulate_pass_read(self._h, _ptr(a), a.size))
+        return a
+
+    # ---- ambient occlusion (rt_occlusion) ----
+    def _occlusion_opts(self, samples, radius, bias, restart, use_bvh, rebuild_bvh):
+        o = OcclusionOpts()
+        lib().rt_occlusion_opts_default(ctypes.byref(o))
+        o.samples, o.radius, o.bias = int(samples), float(radius), float(bias)
+        o.restart, o.use_bvh, o.rebuild_bvh = int(restart), int(use_bvh), int(rebuild_bvh)
+        return o
+
+    def occlusion(self, samples=1, radius=float("inf"), bias=RT_AO_BIAS_DEFAULT, restart=False, want=("visibility",),
+                  use_bvh=True, rebuild_bvh=True):
+        """Add `samples` occlusion directions per pixel and return the estimate over all the samples
+        held, as host numpy arrays named in `want` ("visibility" float32, "occluded" int32, "rgba"
+        uint32, each (H, W)), plus "n", their number.  The accumulation starts again by itself when
+        the camera, an instance, `radius` or `bias` changed (rt_occlusion)."""
+        W, H = self.width, self.height
+        o = self._occlusion_opts(samples, radius, bias, restart, use_bvh, rebuild_bvh)
+        o.host_outputs = 1
+        out = {}
+        for k, dt in (("visibility", np.float32), ("occluded", np.int32), ("rgba", np.uint32)):
+            if k in want:
+                out[k] = np.zeros((H, W), dt)
+                setattr(o, k, _ptr(out[k]))
+        n = ctypes.c_int(0)
+        _check(lib().rt_occlusion(self._h, ctypes.byref(o), ctypes.byref(n)))
+        out["n"] = n.value
+        return out
+
+    def occlusion_device(self, samples=1, radius=float("inf"), bias=RT_AO_BIAS_DEFAULT, restart=False, use_bvh=True,
+                         rebuild_bvh=True, visibility_ptr=None, occluded_ptr=None, rgba_ptr=None):
+        """occlusion into caller-owned DEVICE buffers (e.g. torch tensors' data_ptr()), complete on
+        return; returns the number of samples held."""
+        o = self._occlusion_opts(samples, radius, bias, restart, use_bvh, rebuild_bvh)
+        o.visibility, o.occluded, o.rgba = visibility_ptr, occluded_ptr, rgba_ptr
+        n = ctypes.c_int(0)
+        _check(lib().rt_occlusion(self._h, ctypes.byref(o), ctypes.byref(n)))
+        return n.value
+
+    def occlusion_reset(self):
+        """Drop the occlusion samples held (rt_occlusion_reset)."""
+        _check(lib().rt_occlusion_reset(self._h))
+
+    @property
+    def occlusion_info(self):
+        """(samples held, W, H, restarts so far) (rt_occlusion_info)."""
+        a = np.zeros(4, np.int32)
+        _check(lib().rt_occlusion_info(self._h, _ptr(a)))
+        return tuple(int(x) for x in a)
+
+    def _occlusion_rays(self, k):
+        """Test hook: the rays sample k traces for the current accumulation, (H, W, 6) float32:
+        origin and raw direction, zeros where the primary misses (rt_occlusion_rays)."""
+        a = np.zeros((self.height, self.width, 6), np.float32)
+        _check(lib().rt_occlusion_rays(self._h, int(k), _ptr(a), a.size))
         return a
 
     def frame_work(self, spp=1, row0=0, row_step=1, compact=True, want_rgba=False):

@@ -35,7 +35,9 @@ extern "C" {
  *    (still 5: additive -- the RT_EXPORT_BVH_* values of rt_scene_export, a test hook)
  *    (still 5: additive -- rt_scene_set_shadow_hints and its test hooks)
  *    (still 5: additive -- rt_accumulate_set_adaptive / rt_accumulate_adaptive_info and the pass
- *    buffer's test hooks; rt_accum_opts keeps its layout, the switch is scene state) */
+ *    buffer's test hooks; rt_accum_opts keeps its layout, the switch is scene state)
+ *    (still 5: additive -- rt_occlusion and its companions, rt_ao_direction; no existing entry or
+ *    struct changed) */
 #define RT_ABI_VERSION 5
 
 enum {
@@ -351,6 +353,71 @@ int rt_query_set_order(rt_scene* s, int mode);
  * (copied from the device; nothing is written if the batch was not sorted).  Each may be NULL.
  * RT_ERR_STATE before the first rt_query; RT_ERR_ARG if order_cap < n. */
 int rt_query_last(const rt_scene* s, int32_t out8[8], float bounds6[6], uint32_t* order, int64_t order_cap);
+
+/* ---- ambient occlusion (build-defined; the reference has no counterpart) ----
+ * For every pixel of the current camera: how much of the hemisphere above its primary hit is
+ * unoccluded within `radius`, estimated with cosine-weighted directions and accumulated across
+ * calls as rt_accumulate accumulates radiance: show the first samples at once, add more per redraw
+ * while nothing moves.  The result is not fed into the integrator's ambient term.
+ *
+ * Primary hit.  Pixel (x, y)'s primary hit is rt_query's pixel-mode result: the sample-0 ray
+ * camera_at(x, y) as traced, (o, d) = rays_out, its t and its normal (Isect::norm).  A pixel whose
+ * primary misses takes no part: count 0, visibility 1.
+ * Surface point and frame (float32, one rounding per operation, no contraction; the order is fixed
+ * in csrc/rt_occl.h):
+ *   p = o + t d per component (t x d, then + o);
+ *   n = the query's normal, each component negated (exactly) when dot(n, d) > 0, so it faces the viewer;
+ *   s = copysignf(1, n.z), a = -1 / (s + n.z), b = (n.x n.y) a,
+ *   t1 = (1 + ((s n.x) n.x) a, s b, -(s n.x)),  t2 = (b, s + (n.y n.y) a, -n.y)
+ *   (the branchless orthonormal basis; n.z = -1 gives a = 1/2, finite).
+ * Sample k, the global sample index, 0 <= k < RT_AO_MAX_SAMPLES, uses entry k = (x_k, y_k, z_k) of a
+ * direction table every pixel shares (no per-pixel decorrelation): point k of the R2 sequence of
+ * rt_spp_offset, (u, v) -> sqrt(u) (cos 2 pi v, sin 2 pi v) on the unit disk, z = sqrt(max(0, 1 -
+ * x^2 - y^2)), computed on the host in double and rounded to float32 (rt_ao_direction).
+ * Its occlusion ray: origin p + bias n (bias x n, then + p), raw direction (x_k t1 + y_k t2) + z_k n,
+ * made by the Ray(o, d) constructor and traced exactly as rt_query(any_hit = 1, tmax = radius)
+ * traces a caller's ray (accept THRESHOLD <= t < radius, the same early exit, the camera-ray
+ * shortcuts off); a ray rt_query would reject (non-finite, direction normalising to zero) counts
+ * as not occluded.
+ * Result after n samples: occluded[pixel] = the count of occluded samples (int32), visibility[pixel]
+ * = 1.0f - (float)count / (float)n with a correctly rounded division, rgba = visibility as an
+ * opaque grey (v, v, v, 1) through Color's truncation to bytes.
+ *
+ * The call runs on the scene's own stream after every frame in flight, rotates no frame slot,
+ * launches no trace kernel (rt_scene_last_trace and the scheduling history stay as they were) and
+ * builds the BVH at most once; it returns when the outputs are written.  The counts, the surface
+ * record (32 bytes a pixel, built with sample 0) and the table belong to the scene: allocated on
+ * first use, freed with it; if they cannot be allocated the call returns RT_ERR_HIP and the scene
+ * stays usable.  The accumulation restarts by itself (counted in rt_occlusion_info) when the
+ * camera, an instance pose, `radius` or `bias` changed since its sample 0; rt_env_set, the atlas
+ * and use_bvh restart nothing.
+ * Checked before any device work -- RT_ERR_ARG: null opts, samples < 1, radius <= 0 or NaN, bias
+ * negative or non-finite, no output requested; RT_ERR_LIMIT: the call would hold more than
+ * RT_AO_MAX_SAMPLES samples; RT_ERR_STATE: a scene split by rt_scene_set_devices; RT_ERR_NODEV: no
+ * usable device. */
+#define RT_AO_MAX_SAMPLES 1024
+#define RT_AO_BIAS_DEFAULT 1e-3f   /* world units: above the rounding of p for scenes a few hundred units across */
+typedef struct rt_occlusion_opts {
+    int samples;            /* directions to add in this call, >= 1 */
+    float radius;           /* > 0; +inf = sky visibility */
+    float bias;             /* >= 0, finite; RT_AO_BIAS_DEFAULT */
+    int use_bvh, rebuild_bvh, restart, host_outputs;   /* as rt_accum_opts */
+    float* visibility; int32_t* occluded; uint32_t* rgba;   /* W*H each, each may be NULL */
+} rt_occlusion_opts;
+/* zeros; samples = 1, radius = +inf, bias = RT_AO_BIAS_DEFAULT, use_bvh = rebuild_bvh = 1 */
+void rt_occlusion_opts_default(rt_occlusion_opts* o);
+/* *n_samples (may be NULL): the samples held after the call. */
+int rt_occlusion(rt_scene* s, const rt_occlusion_opts* opts, int* n_samples);
+/* Drop the samples held (counted as a restart if there were any).  Host state. */
+int rt_occlusion_reset(rt_scene* s);
+/* out4 = {samples held, W, H, restarts so far}.  Host state. */
+int rt_occlusion_info(const rt_scene* s, int32_t out4[4]);
+/* Entry k of the direction table.  RT_ERR_ARG: k outside [0, RT_AO_MAX_SAMPLES). */
+int rt_ao_direction(int k, float out3[3]);
+/* Test hook: the rays sample k traces for the current accumulation (its camera, poses and bias),
+ * W*H*6 floats to host memory: origin, RAW direction before the Ray constructor; zeros where the
+ * primary misses.  RT_ERR_STATE without an accumulation. */
+int rt_occlusion_rays(rt_scene* s, int k, float* dst, int64_t cap_floats);
 
 /* Frame slots (1 = default, up to 8).  The reference rebuilds its BVH inside every
  * update_scene call (raytracer.cu:103-119), so a frame owns per-frame state: BVH, work

@@ -248,6 +248,22 @@ inline void use_devices(renv::gpu::Scene* scene, const std::vector<int>& devices
 inline void set_accumulate_adaptive(renv::gpu::Scene* scene, bool on = true, float threshold = RT_ADAPTIVE_THRESHOLD_DEFAULT) {
     rtamd_detail::check(rt_accumulate_set_adaptive(scene->handle(), on ? 1 : 0, threshold), "set_accumulate_adaptive");
 }
+// Build extension (rt_occlusion): `samples` more ambient-occlusion directions per pixel of `scene`
+// within `radius`; `visibility` receives the estimate over all the samples held (W * H floats,
+// host memory), and the count of samples held is returned.
+inline int occlusion(renv::gpu::Scene* scene, std::vector<float>& visibility, int samples = 1, float radius = INFINITY,
+                     float bias = RT_AO_BIAS_DEFAULT) {
+    int32_t info[10];
+    rtamd_detail::check(rt_scene_info(scene->handle(), info), "rt_scene_info");
+    visibility.resize((size_t)info[0] * info[1]);
+    rt_occlusion_opts o;
+    rt_occlusion_opts_default(&o);
+    o.samples = samples; o.radius = radius; o.bias = bias;
+    o.host_outputs = 1; o.visibility = visibility.data();
+    int n = 0;
+    rtamd_detail::check(rt_occlusion(scene->handle(), &o, &n), "occlusion");
+    return n;
+}
 // raytracer.cu:91-100: one-pixel trace with the reference's event log on stdout.
 inline void debug_cast(renv::gpu::Scene* scene, int x, int y) {
     std::vector<char> buf(1 << 16);
