@@ -1,4 +1,4 @@
-// rt_device.h — what the host runtime (rt_runtime.cpp, rt_multi.cpp, rt_copy.cpp) and the
+// rt_device.h — what the host runtime (rt_runtime.cpp and the entry families' files) and the
 // kernel translation unit (rt_kernels.hip) share: the kernel argument structs, the launch
 // geometry the host sizes buffers and grids by, the launch plan (rt_plan.h, included below:
 // LDS layout, kernel choice, frame geometry, grid) and the launch layer's declarations.  The

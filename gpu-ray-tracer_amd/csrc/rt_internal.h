@@ -1,6 +1,8 @@
 // rt_internal.h — the scene object and what the host translation units share: rt_runtime.cpp
-// (scene, upload, frame slots, frames, most of the C ABI), rt_multi.cpp (multi-device frames)
-// and rt_copy.cpp (copy-engine entries).  Internal functions live in namespace rti: the
+// (upload, frame slots, BVH build and trace launch, rt_render), rt_build.cpp (scene creation,
+// exports, camera), rt_accumulate.cpp, rt_occlusion.cpp, rt_query.cpp (one entry family each),
+// rt_hooks.cpp (debugging, profiling and test hooks), rt_multi.cpp (multi-device frames) and
+// rt_copy.cpp (copy-engine entries).  Internal functions live in namespace rti: the
 // library's rt_* C symbols (rt_amd.h) stay its only interface.
 #pragma once
 
@@ -146,23 +148,26 @@ struct rt_scene {
     float4* d_atlas = nullptr;                   // atlas texels (float4, byte / 255)
     bool atlas_dirty = false;
     void* d_out[4] = {nullptr, nullptr, nullptr, nullptr};   // staging for host_outputs
-    // rt_query with host pointers: one pinned host image of the batch (inputs, then outputs) and
-    // its device copy; they grow and are kept, so a warm call allocates nothing
-    unsigned char* q_host = nullptr; unsigned char* q_dev = nullptr; size_t q_cap = 0;
-    // rt_query_set_order: the mode (host state), and the sorted mode's scratch for qo_rays rays
-    // (query_order_plan: keys and ray indices, double-buffered, then hipCUB's qo_temp bytes); it
-    // grows like q_dev and is kept.  q_box: the keys' quantisation box, for the poses of q_box_gen.
-    int query_order = RT_QUERY_ORDER_CALLER;
-    unsigned char* qo_dev = nullptr; long long qo_rays = 0; size_t qo_temp = 0;
-    rtk::KeyBox q_box{{0, 0, 0}, {0, 0, 0}};
-    unsigned q_box_gen = 0;
-    // the most recent rt_query (rt_query_last): its kernel and launch, whether the batch was
-    // sorted, its size, the box its keys used and the device array of its order; host state
-    rtd::QueryVariant last_query{};
-    bool has_last_query = false, last_query_sorted = false;
-    long long last_query_n = 0;
-    const uint32_t* last_query_order = nullptr;
-    std::vector<hipEvent_t> tev;     // timing=1 events, 4 per frame: bvh start/stop, trace start/stop (pool)
+    struct Query {
+        // rt_query with host pointers: one pinned host image of the batch (inputs, then outputs) and
+        // its device copy; they grow and are kept, so a warm call allocates nothing
+        unsigned char* host = nullptr; unsigned char* dev = nullptr; size_t cap = 0;
+        // rt_query_set_order: the mode (host state), and the sorted mode's scratch for qo_rays rays
+        // (query_order_plan: keys and ray indices, double-buffered, then hipCUB's qo_temp bytes); it
+        // grows like dev and is kept.  box: the keys' quantisation box, for the poses of box_gen.
+        int order = RT_QUERY_ORDER_CALLER;
+        unsigned char* qo_dev = nullptr; long long qo_rays = 0; size_t qo_temp = 0;
+        rtk::KeyBox box{{0, 0, 0}, {0, 0, 0}};
+        unsigned box_gen = 0;
+        // the most recent rt_query (rt_query_last): its kernel and launch, whether the batch was
+        // sorted, its size, the box its keys used and the device array of its order; host state
+        rtd::QueryVariant last{};
+        bool has_last = false, last_sorted = false;
+        long long last_n = 0;
+        const uint32_t* last_order = nullptr;
+        void release() { rti::dfree(dev); rti::hfree(host); rti::dfree(qo_dev); cap = 0; qo_rays = 0; qo_temp = 0; last_order = nullptr; }
+    } query;
+    std::vector<hipEvent_t> tev;    // timing=1 events, 4 per frame: bvh start/stop, trace start/stop (pool)
     size_t tev_used = 0;
     size_t d_out_px = 0;
     int n_leaf = 0;
@@ -234,6 +239,8 @@ struct rt_scene {
     struct Built { int slot = -1, n_real = 0, fdepth = 0, form = 0; } built;
     rti::FrameSlot& cur() { return slots[cur_slot]; }
     const rti::FrameSlot& cur() const { return slots[cur_slot]; }
+    // does a call with these options build the current slot's BVH?
+    bool builds_bvh(int use_bvh, int rebuild_bvh) const { return use_bvh && (rebuild_bvh || !cur().bvh_valid); }
     ~rt_scene();
 };
 
@@ -244,13 +251,67 @@ struct rt_scene {
 
 namespace rti {
 
+// What a trace launch is asked for beside the render options (each caller sets what it uses).
+struct TraceRequest {
+    hipStream_t stream = nullptr;
+    uint32_t* rgba = nullptr;
+    int* dbg = nullptr; int dbg_x = -1, dbg_y = -1;           // debug_cast's event log and its pixel
+    bool want_stats = false;                                   // the counted kernel (d_stats)
+    int occl_force = -1;                                       // shade_shortcuts
+    hipEvent_t e0 = nullptr, e1 = nullptr;                     // timestamps taken by the dispatches themselves
+    bool prof = false;                                         // the fast kernel's profiling variant (M_PROF)
+    unsigned* gdur = nullptr;                                  // per-group durations (rt_profile_groups)
+    int k0 = 0;                                                // sample base (rt_accumulate; TraceParams::k0)
+    int* geo = nullptr;                                        // out: {n_groups, gw, gh, n_gx}
+    // rt_accumulate's refinement passes (adaptive mode): trace only the groups of these live-group
+    // lists ([NQ][lists_cap], sky_kernel's form), starting from lists_work, an image of the work
+    // counters with the lists' lengths set.  No sky pre-pass, no scheduling history read or recorded.
+    // Only a kernel that runs from live lists today takes them (TraceKey::sky); *listed (out) says so,
+    // and a launch that does not traces every group as without them.  lists_n: the groups listed,
+    // when known (> 0: the grid is sized by it).
+    const int* lists = nullptr; int lists_cap = 0; const int* lists_work = nullptr; int lists_n = 0;
+    bool* listed = nullptr;
+};
+// Capacities of the per-frame layout buffers for n_groups pixel groups.
+struct Layout { int flags, sky_blocks, live_q, live; };
+// A scene view for a caller's rays, the zero-axis cut's scene term and the early-exit margin.
+struct CallerView { rtd::SceneView S; float zcut_scene, any_margin; };
+
 // rt_runtime.cpp
 int upload(rt_scene* s);          // device buffers of a finished scene on g_device (once)
 void invalidate(rt_scene* s);     // every slot's BVH is stale (instances moved)
+hipStream_t sstream(rt_scene* s);
+int begin_side_entry(rt_scene* s, int spp, bool bvh);
+int end_frame(rt_scene* s, hipStream_t st);
+int build_bvh(rt_scene* s, hipStream_t st, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
+int launch_trace(rt_scene* s, const rt_render_opts& o, const TraceRequest& q);
+rtd::SceneView view_of(const rt_scene* s, bool use_bvh);
+CallerView caller_ray_view(const rt_scene* s, bool use_bvh);
+Layout layout_of(int n_groups);
+int ensure_out_staging(rt_scene* s);
+int clear_stats(rt_scene* s, hipStream_t st);
+int read_frame_stats(rt_scene* s, rt_stats* stats);
+std::vector<rtm::Box> mesh_boxes(const rt::Scene& h);
+int warm_scene(rt_scene* s);
 // rt_multi.cpp
 int render_multi(rt_scene* s, const rt_render_opts* o, rt_stats* stats);
 void free_multi(rt_scene* s);
 void set_multi_overlap(rt_scene* s, int policy);   // the replicas of rt_scene_set_devices
 void set_multi_shadow_hints(rt_scene* s, bool on);
+
+// Mean kernel time (*ms) over `reps` runs of launch(i), which puts its work between ev[0] and
+// ev[1] on the scene's stream; with more than one run the first is left out.
+template <class F> int mean_ms(rt_scene* s, int reps, double* ms, F launch) {
+    float total = 0;
+    for (int i = 0; i < reps; i++) {
+        int r;
+        if ((r = launch(i)) != RT_OK) return r;
+        HIPCHK(hipEventSynchronize(s->ev[1]));
+        float t = 0; HIPCHK(hipEventElapsedTime(&t, s->ev[0], s->ev[1]));
+        if (i > 0 || reps == 1) total += t;
+    }
+    *ms = total / (reps > 1 ? reps - 1 : 1);
+    return RT_OK;
+}
 
 }  // namespace rti

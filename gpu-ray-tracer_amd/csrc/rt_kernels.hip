@@ -1,6 +1,6 @@
 // rt_kernels.hip — gfx950 kernels of the ray-tracing core and their launch layer (rt_device.h).
-// Device code only: the scene object, the frame slots and the C ABI are rt_runtime.cpp,
-// rt_multi.cpp and rt_copy.cpp.
+// Device code only: the scene object, the frame slots and the C ABI are rt_runtime.cpp and
+// the host files beside it (rt_build, rt_accumulate, rt_occlusion, rt_query, rt_hooks, ...).
 //
 // Hot path (BASELINE.json north_star): rtracer::gpu::update_scene
 // (src/raytracer.cu:102-120) = per-frame BVH build + the per-pixel `trace`

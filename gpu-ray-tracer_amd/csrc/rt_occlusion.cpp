@@ -1,0 +1,179 @@
+// rt_occlusion.cpp — the ambient occlusion pass (rt_occlusion): the scene-owned direction table,
+// surface record and counts, the reset / info entries and the rays' test hook.  Host code only
+// (rt_internal.h); its kernels are the occlusion kernels, reached through rt_device.h.
+#include <cmath>
+#include <cstring>
+
+#include "rt_internal.h"
+
+using namespace rtd;
+using namespace rti;
+
+namespace {
+static_assert(RT_AO_MAX_SAMPLES == rto::AO_MAX_SAMPLES, "the direction table's length");
+
+// Has anything that decides an occlusion sample changed since the accumulation's first one?
+bool occl_stale(const rt_scene* s, float radius, float bias) {
+    const rt_scene::Occl& a = s->occl;
+    return a.n > 0 && (a.inst_gen != s->inst_gen || a.cam_gen != s->cam_gen || a.radius != radius || a.bias != bias);
+}
+void occl_drop(rt_scene* s) {
+    if (s->occl.n > 0) s->occl.restarts++;
+    s->occl.n = 0;
+}
+// The scene-owned buffers for the canvas and the direction table; a failed allocation leaves none
+// of them (and no samples).
+int ensure_occl(rt_scene* s) {
+    rt_scene::Occl& a = s->occl;
+    const size_t px = std::max<size_t>(1, (size_t)s->h.cam.W * s->h.cam.H);
+    if (a.px >= px) return RT_OK;
+    a.release();
+    if (hipMalloc((void**)&a.d_table, rto::AO_MAX_SAMPLES * sizeof(rtm::V3)) != hipSuccess ||
+        hipMalloc((void**)&a.d_surf, 2 * px * sizeof(float4)) != hipSuccess ||
+        hipMalloc((void**)&a.d_count, px * sizeof(int32_t)) != hipSuccess) {
+        const std::string why = hipGetErrorString(hipGetLastError());
+        a.release();
+        return fail(RT_ERR_HIP, "rt_occlusion: no memory for the surface record and counts of " + std::to_string(px) + " pixels: " + why);
+    }
+    std::vector<rtm::V3> tab(rto::AO_MAX_SAMPLES);
+    for (int k = 0; k < rto::AO_MAX_SAMPLES; k++) rto::ao_direction(k, &tab[k].x);
+    if (hipMemcpy(a.d_table, tab.data(), tab.size() * sizeof(rtm::V3), hipMemcpyHostToDevice) != hipSuccess) {
+        const std::string why = hipGetErrorString(hipGetLastError());
+        a.release();
+        return fail(RT_ERR_HIP, "rt_occlusion: the direction table's copy: " + why);
+    }
+    a.px = px;
+    return RT_OK;
+}
+// The kernels' arguments and scene view for the current slot: the occlusion rays start on the
+// surfaces, not at the camera, so the view is the one for a caller's rays (caller_ray_view).
+void occl_launch_setup(rt_scene* s, bool use_bvh, OcclParams& P, SceneView& S, OcclPlan& plan) {
+    const rt_scene::Occl& a = s->occl;
+    const CallerView v = caller_ray_view(s, use_bvh);
+    S = v.S;
+    P = OcclParams{};
+    P.cam = s->h.d_cam; P.W = s->h.cam.W; P.H = s->h.cam.H;
+    P.radius = a.radius; P.bias = a.bias;
+    P.zcut_scene = v.zcut_scene; P.any_margin = v.any_margin;
+    P.table = a.d_table; P.surf = a.d_surf; P.count = a.d_count;
+    int map = -1;                                              // RT_OCCL_MAP (measurements): row / tile
+    if (const char* e = getenv("RT_OCCL_MAP")) map = !strcmp(e, "row") ? OCCL_MAP_ROW : !strcmp(e, "tile") ? OCCL_MAP_TILE : -1;
+    plan = occlusion_plan(P.W, P.H, S, map);
+    P.map = plan.map; P.n_waves = plan.n_waves;
+}
+}  // namespace
+
+extern "C" {
+
+void rt_occlusion_opts_default(rt_occlusion_opts* o) {
+    if (!o) return;
+    memset(o, 0, sizeof *o);
+    o->samples = 1; o->radius = INFINITY; o->bias = RT_AO_BIAS_DEFAULT; o->use_bvh = 1; o->rebuild_bvh = 1;
+}
+
+// Ambient occlusion (rt_amd.h): a side entry like rt_query.  Its kernels are the occlusion kernels,
+// not a trace kernel: the scene's last trace launch and the slots' scheduling history stay as they were.
+int rt_occlusion(rt_scene* s, const rt_occlusion_opts* o, int* n_samples) {
+    CHECK_FINISHED(s);
+    if (!o) return fail(RT_ERR_ARG, "null options");
+    if (o->samples < 1) return fail(RT_ERR_ARG, "rt_occlusion: samples >= 1 required");
+    if (!(o->radius > 0.0f)) return fail(RT_ERR_ARG, "rt_occlusion: radius > 0 required (+inf: sky visibility)");
+    if (!(o->bias >= 0.0f && std::isfinite(o->bias))) return fail(RT_ERR_ARG, "rt_occlusion: bias must be finite and >= 0");
+    if (!(o->visibility || o->occluded || o->rgba)) return fail(RT_ERR_ARG, "rt_occlusion: no output requested");
+    const bool fresh = o->restart || occl_stale(s, o->radius, o->bias);
+    if ((long long)(fresh ? 0 : s->occl.n) + o->samples > RT_AO_MAX_SAMPLES)
+        return fail(RT_ERR_LIMIT, "rt_occlusion: more than 1024 samples held (rt_occlusion_reset starts again)");
+    if (s->multi) return fail(RT_ERR_STATE, "rt_occlusion: not on a scene split by rt_scene_set_devices");
+    int r;
+    if ((r = upload(s)) != RT_OK) return r;
+    HIPCHK(hipSetDevice(s->device));
+    const size_t px = (size_t)s->h.cam.W * s->h.cam.H;
+    if (px > (size_t)INT32_MAX / 8) return fail(RT_ERR_LIMIT, "rt_occlusion: frame larger than 2^28 pixels");
+    if (fresh) occl_drop(s);
+    if ((r = ensure_occl(s)) != RT_OK) return r;
+    if (o->host_outputs && (r = ensure_out_staging(s)) != RT_OK) return r;
+    rt_scene::Occl& a = s->occl;
+    // frames in flight (any slot) first; the BVH at most once, for every sample of the call
+    if ((r = begin_side_entry(s, 1, s->builds_bvh(o->use_bvh, o->rebuild_bvh))) != RT_OK) return r;
+    hipStream_t st = sstream(s);
+    const int before = a.n;
+    if (before == 0) {                                        // what this accumulation's samples see
+        a.inst_gen = s->inst_gen; a.cam_gen = s->cam_gen; a.radius = o->radius; a.bias = o->bias;
+    }
+    OcclParams P;
+    SceneView S;
+    OcclPlan plan;
+    occl_launch_setup(s, o->use_bvh != 0, P, S, plan);
+    const bool host = o->host_outputs != 0;
+    P.visibility = !o->visibility ? nullptr : host ? (float*)s->d_out[1] : o->visibility;
+    P.occluded = !o->occluded ? nullptr : host ? (int*)s->d_out[2] : o->occluded;
+    P.rgba = !o->rgba ? nullptr : host ? (uint32_t*)s->d_out[0] : o->rgba;
+    a.n = 0;                                                  // a failed launch leaves no samples, not stale counts
+    if (px > 0) {
+        if (before == 0) HIPCHK(launch_occl_surface(plan, P, S, st, nullptr, nullptr));
+        for (int done = 0; done < o->samples; done += OCCL_LAUNCH_SAMPLES) {
+            P.k0 = before + done;
+            P.samples = std::min(OCCL_LAUNCH_SAMPLES, o->samples - done);
+            P.resolve = done + P.samples == o->samples ? 1 : 0;
+            P.n_total = before + o->samples;
+            HIPCHK(launch_occlusion(plan, P, S, st, nullptr, nullptr));
+        }
+        HIPCHK(hipGetLastError());
+    }
+    if ((r = end_frame(s, st)) != RT_OK) return r;
+    HIPCHK(hipStreamSynchronize(st));
+    a.n = before + o->samples;
+    if (host) {
+        if (o->visibility) HIPCHK(hipMemcpy(o->visibility, P.visibility, px * 4, hipMemcpyDeviceToHost));
+        if (o->occluded) HIPCHK(hipMemcpy(o->occluded, P.occluded, px * 4, hipMemcpyDeviceToHost));
+        if (o->rgba) HIPCHK(hipMemcpy(o->rgba, P.rgba, px * 4, hipMemcpyDeviceToHost));
+    }
+    if (n_samples) *n_samples = a.n;
+    return RT_OK;
+}
+
+int rt_occlusion_reset(rt_scene* s) {
+    CHECK_SCENE(s);
+    occl_drop(s);
+    return RT_OK;
+}
+
+int rt_occlusion_info(const rt_scene* s, int32_t* out4) {
+    CHECK_SCENE(s);
+    if (!out4) return fail(RT_ERR_ARG, "null argument");
+    out4[0] = s->occl.n; out4[1] = s->h.cam.W; out4[2] = s->h.cam.H; out4[3] = s->occl.restarts;
+    return RT_OK;
+}
+
+int rt_ao_direction(int k, float* out3) {
+    if (k < 0 || k >= RT_AO_MAX_SAMPLES || !out3) return fail(RT_ERR_ARG, "rt_ao_direction: 0 <= k < 1024 and a destination");
+    rto::ao_direction(k, out3);
+    return RT_OK;
+}
+
+// Test hook: the rays sample k traces, formed by occlusion_kernel's own code from the surface
+// record of the current accumulation (its camera, poses and bias), without tracing.
+int rt_occlusion_rays(rt_scene* s, int k, float* dst, int64_t cap_floats) {
+    CHECK_FINISHED(s);
+    if (!dst || k < 0 || k >= RT_AO_MAX_SAMPLES) return fail(RT_ERR_ARG, "rt_occlusion_rays: 0 <= k < 1024 and a destination");
+    const size_t px = (size_t)s->h.cam.W * s->h.cam.H;
+    if (cap_floats < (int64_t)(px * 6)) return fail(RT_ERR_ARG, "rt_occlusion_rays: buffer below W * H * 6 floats");
+    if (s->occl.n <= 0) return fail(RT_ERR_STATE, "rt_occlusion_rays: no accumulation (after rt_occlusion)");
+    int r;
+    if ((r = begin_side_entry(s, 1, false)) != RT_OK) return r;
+    if (px == 0) return RT_OK;
+    DevBuf<float> rays;
+    HIPCHK(rays.alloc(px * 6));
+    OcclParams P;
+    SceneView S;
+    OcclPlan plan;
+    occl_launch_setup(s, true, P, S, plan);
+    P.k0 = k; P.rays = rays.p;
+    HIPCHK(launch_occl_rays(P, sstream(s)));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(sstream(s)));
+    HIPCHK(hipMemcpy(dst, rays.p, px * 6 * sizeof(float), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+}  // extern "C"

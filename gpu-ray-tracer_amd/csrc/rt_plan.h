@@ -7,7 +7,7 @@
 //    rt_kernels.hip), the frame's lane mapping and group geometry (frame_geometry), its shading
 //    shortcuts (shade_shortcuts), its grid (grid_policy) and its scheduling history mode
 //    (history_mode), and which query kernel a batch of caller-supplied rays gets (query_plan,
-//    rt_query).  launch_trace and rt_query (rt_runtime.cpp) fill the kernels' parameters from
+//    rt_query).  launch_trace (rt_runtime.cpp) and rt_query (rt_query.cpp) fill them in from
 //    them; tests/test_plan_host.py and tests/test_query_host.py check them on a machine without
 //    a GPU.
 #pragma once

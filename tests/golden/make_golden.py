@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Generate the committed golden fixtures (tests/golden/*.npz).
 
-Two families:
+Three families:
 
 1. ``kat_<op>.npz`` — known-answer vectors for the math primitives on the hot
    path, produced by ``oracle/_ref/kat_ref``: the REFERENCE's own
@@ -17,6 +17,10 @@ Two families:
    tests/test_oracle.py).  ``frame_media_48x32_d9.npz`` is the same for a built scene
    (tests/integrator_cases.py), with the integrator census; tests/test_integrator_host.py
    re-renders it.
+
+3. ``abi_errors.json`` — the C ABI's answers to invalid calls (tests/abi_error_cases.py), recorded
+   from the library itself on a machine without a device, only on request:
+   ``python tests/golden/make_golden.py abi_errors``.
 
 Run in the build container (needs /root/reference for family 1):
     make -C oracle ref && python tests/golden/make_golden.py
@@ -236,7 +240,27 @@ def make_integrator_frame():
     print("frame frame_media_48x32_d9.npz", fr["stats"], fr["census"])
 
 
+def make_abi_errors():
+    """abi_errors.json: what the library answers to tests/abi_error_cases.py's calls, the code and the
+    rt_last_error text of each.  Recorded on a machine without a device, from the library as it was
+    before the code under test changed: tests/test_abi_errors.py replays it."""
+    import json
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    sys.path.insert(0, os.path.join(ROOT, "gpu-ray-tracer_amd"))
+    import abi_error_cases as ac  # noqa: E402
+    import rtamd  # noqa: E402
+    assert rtamd.device_count() == 0, "record on a machine without a device"
+    rec = ac.run(rtamd, ac.CASES + ac.CASES_NO_DEVICE)
+    with open(os.path.join(HERE, "abi_errors.json"), "w") as f:
+        f.write("[\n" + ",\n".join(" " + json.dumps(r) for r in rec) + "\n]\n")
+    for r in rec:
+        print("abi", r)
+
+
 if __name__ == "__main__":
+    if "abi_errors" in sys.argv[1:]:
+        make_abi_errors()
+        sys.exit(0)
     what = sys.argv[1:] or ["kats", "frames", "integrator"]
     if "kats" in what:
         make_kats()
