@@ -3,7 +3,7 @@
 //   rtracer -c world8.json [-b] [-r] [-s] [-d DIM] [--frames N] [--spp K]
 //           [--width W --height H] [--out frame.ppm] [--debug X,Y] [--textures [ATLAS.png]]
 //           [--gpus N [--ranks R]] [--in-flight D] [--pick X,Y] [--accumulate N [--adaptive [THR]]]
-//           [--occlusion N [--radius R]]
+//           [--occlusion N [--radius R] [--interleave] [--filter]]
 //
 // -c config (worldN.json), -b benchmark (one timed frame, "Time: X ms" as main.cc:210-216),
 // -r unoptimize (brute force, no BVH), -d kernel dimension (accepted; the HIP path
@@ -30,6 +30,9 @@
 // --occlusion N [--radius R] (build extension, rt_occlusion): the ambient-occlusion pass -- N
 // directions per pixel within R (default +inf: sky visibility); --out writes the visibility as a
 // grey frame the way --accumulate writes its frame.  -b prints the call's time.
+// --interleave (with --occlusion only; rt_occlusion_set_pattern): the pixels of a 4 x 4 block take
+// different directions (N <= 64).  --filter (with --occlusion only; rt_occlusion_set_filter, its
+// default parameters): the frame is resolved through the geometry-aware 4 x 4 filter.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -48,7 +51,7 @@ static void usage() {
                  "usage: rtracer -c CONFIG [-b] [-r] [-s] [-d DIM] [--frames N] [--spp K] [--width W --height H]\n"
                  "               [--out FILE.ppm] [--debug X,Y] [--textures [ATLAS.png]] [--gpus N [--ranks R]]\n"
                  "               [--in-flight D [--readback] [--overlap stream|half|full]] [--pick X,Y]\n"
-                 "               [--accumulate N [--adaptive [THR]]] [--occlusion N [--radius R]]\n");
+                 "               [--accumulate N [--adaptive [THR]]] [--occlusion N [--radius R] [--interleave] [--filter]]\n");
 }
 
 static bool write_ppm(const char* path, const uint32_t* px, int w, int h) {
@@ -69,7 +72,7 @@ static bool write_ppm(const char* path, const uint32_t* px, int w, int h) {
 
 int main(int argc, char** argv) {
     std::string config, out;
-    bool bench = false, unopt = false, serial = false, textures = false, readback = false, adaptive = false;
+    bool bench = false, unopt = false, serial = false, textures = false, readback = false, adaptive = false, interleave = false, filter = false;
     float adaptive_thr = RT_ADAPTIVE_THRESHOLD_DEFAULT;
     std::string atlas, overlap = "stream";
     int dim = 16, frames = 1, spp = 1, width = 0, height = 0, dbg_x = -1, dbg_y = -1, pick_x = -1, pick_y = -1, gpus = 1, ranks = 0, in_flight = 0, accumulate = 0, occlusion = 0;
@@ -109,6 +112,8 @@ int main(int argc, char** argv) {
                 if (end == argv[i] || *end) { usage(); return 2; }
             }
         }
+        else if (a == "--interleave") interleave = true;
+        else if (a == "--filter") filter = true;
         else if (a == "--readback") readback = true;
         else if (a == "--overlap") {
             overlap = val("--overlap");
@@ -133,6 +138,7 @@ int main(int argc, char** argv) {
     if (frames < 1 || spp < 1 || gpus < 1 || ranks < 0 || in_flight < 0 || in_flight > 8) { usage(); return 2; }
     if (adaptive && accumulate < 1) { std::fprintf(stderr, "--adaptive needs --accumulate N\n"); usage(); return 2; }
     if (radius > 0.0f && occlusion < 1) { std::fprintf(stderr, "--radius needs --occlusion N\n"); usage(); return 2; }
+    if ((interleave || filter) && occlusion < 1) { std::fprintf(stderr, "--interleave and --filter need --occlusion N\n"); usage(); return 2; }
     // frames in flight use a stream each: HIP maps streams round-robin onto GPU_MAX_HW_QUEUES
     // hardware queues (4 by default), and streams sharing a queue serialise.
     // The HIP runtime reads it when librt_amd.so's kernels are registered, before main: set it
@@ -179,6 +185,8 @@ int main(int argc, char** argv) {
         o.samples = occlusion; o.use_bvh = unopt ? 0 : 1;
         if (radius > 0.0f) o.radius = radius;
         o.host_outputs = 1; o.rgba = frame.data();
+        if (interleave) rtamd_detail::check(rt_occlusion_set_pattern(handle, RT_AO_PATTERN_INTERLEAVED), "rt_occlusion_set_pattern");
+        if (filter) rtamd_detail::check(rt_occlusion_set_filter(handle, 1, RT_AO_FILTER_NORMAL_DEFAULT, RT_AO_FILTER_PLANE_DEFAULT), "rt_occlusion_set_filter");
         int n = 0;
         auto from = std::chrono::high_resolution_clock::now();
         if (rt_occlusion(handle, &o, &n) != RT_OK) {

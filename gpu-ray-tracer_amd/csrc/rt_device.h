@@ -193,7 +193,9 @@ struct QueryParams {
 
 // The ambient-occlusion kernels' arguments (rt_occlusion): occl_surface_kernel (cam -> surf),
 // occlusion_kernel (surf, table -> count and, resolving, the outputs) and occl_rays_kernel (the
-// test hook: sample k0's rays -> rays).  Device pointers.  The tracing kernels read it in place
+// test hook: sample k0's rays -> rays); occlusion_il_kernel / occl_rays_il_kernel are theirs in the
+// interleaved pattern, and occl_filter_kernel (surf, count -> visibility, rgba) is the filtered
+// resolve.  Device pointers.  The tracing kernels read it in place
 // (oparams(), as qparams()).
 struct OcclParams {
     rt::DCamera cam;
@@ -209,6 +211,8 @@ struct OcclParams {
     int* count;               // [W H] occluded samples so far (not read when k0 = 0)
     float* visibility; int* occluded; uint32_t* rgba;   // each may be null
     float* rays;              // occl_rays_kernel: [6 W H]
+    int pattern;              // OCCL_PATTERN_* (rt_plan.h): which table entry a pixel's sample k uses
+    float normal_min, plane_tol;                // occl_filter_kernel's accept test (rto::filter_accept)
 };
 
 }  // namespace rtd
@@ -274,6 +278,11 @@ hipError_t launch_accum_fold_tiles(const float4* pass, float4* sum_r, float4* su
 hipError_t launch_occl_surface(const OcclPlan& plan, OcclParams& P, SceneView& S, hipStream_t st, hipEvent_t e0, hipEvent_t e1);
 hipError_t launch_occlusion(const OcclPlan& plan, OcclParams& P, SceneView& S, hipStream_t st, hipEvent_t e0, hipEvent_t e1);
 hipError_t launch_occl_rays(OcclParams& P, hipStream_t st);
+// launch_occlusion and launch_occl_rays take the plan's / P's pattern's kernel; the
+// surface record is always built under a shared-pattern plan.  launch_occl_filter: the filtered
+// resolve of P.n_total samples into P.visibility / P.rgba (each may be null), after the call's last
+// launch_occlusion, which then resolves `occluded` only.
+hipError_t launch_occl_filter(const OcclPlan& plan, OcclParams& P, hipStream_t st, hipEvent_t e0, hipEvent_t e1);
 void launch_unpermute(const uint32_t* g, uint32_t* out, int W, int H, int N, int rows_max, hipStream_t st);
 void launch_profile_marker(int tag, hipStream_t st);
 void launch_copy_gate(const unsigned* flag, unsigned long long max_ticks, hipStream_t st);

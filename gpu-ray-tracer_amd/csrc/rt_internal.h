@@ -224,7 +224,21 @@ struct rt_scene {
         int n = 0, restarts = 0;
         unsigned inst_gen = 0, cam_gen = 0;
         float radius = 0.0f, bias = 0.0f;
-        void release() { rti::dfree(d_table); rti::dfree(d_surf); rti::dfree(d_count); px = 0; n = 0; }
+        // rt_occlusion_set_pattern / _set_filter: the direction pattern (what the samples held were
+        // traced with: a change drops them) and the filtered resolve (outputs only); the lane
+        // mapping the last call used (rt_occlusion_config)
+        int pattern = RT_AO_PATTERN_SHARED, filter = 0, last_map = -1;
+        float normal_min = RT_AO_FILTER_NORMAL_DEFAULT, plane_tol = RT_AO_FILTER_PLANE_DEFAULT;
+        // rt_occlusion_filter_timing (measurements): start/stop events on occl_filter_kernel's dispatch
+        bool time_filter = false;
+        hipEvent_t ev0 = nullptr, ev1 = nullptr;
+        float filter_ms = -1.0f;
+        void release() {
+            rti::dfree(d_table); rti::dfree(d_surf); rti::dfree(d_count); px = 0; n = 0;
+            if (ev0) (void)hipEventDestroy(ev0);
+            if (ev1) (void)hipEventDestroy(ev1);
+            ev0 = ev1 = nullptr;
+        }
     } occl;
     static constexpr int MAX_SLOTS = RT_MAX_SLOTS;
     rti::FrameSlot slots[MAX_SLOTS];             // slots[0, n_slots) are in rotation (FrameSlot)

@@ -2320,7 +2320,8 @@ __global__ __launch_bounds__(KEY_BLOCK) void ray_key_kernel(QueryParams Q, rtk::
 // Ambient occlusion (rt_occlusion; rt_occl.h): how much of the hemisphere above
 // every pixel's primary hit is unoccluded within a radius.  Three kernels beside the query
 // kernels, none of which touches them: the surface record once per accumulation, the occlusion
-// rays of a launch's samples, and the test hook that writes one sample's rays out.  One pixel
+// rays of a launch's samples, and the test hook that writes one sample's rays out (the last two
+// once more for the interleaved pattern), then the filtered resolve.  One pixel
 // per lane, 256-thread blocks, nothing staged (the small form of query_kernel); the scene comes
 // as rt_query's (camera-ray shortcuts off).  TREE as query_kernel's.
 // ---------------------------------------------------------------------------
@@ -2344,6 +2345,15 @@ __device__ __forceinline__ long long occl_pixel(int map, int W, int H, int g, in
 }
 __device__ __forceinline__ int occl_wave() {
     return __builtin_amdgcn_readfirstlane((int)blockIdx.x * (OCCL_BLOCK / 64) + (int)(threadIdx.x >> 6));
+}
+// OCCL_MAP_CLASS (the interleaved pattern): wave g takes class c = g & 15 = (cx, cy) of the 32 x 32
+// region g >> 4 (n_rx regions a row), lane l the pixel (32 rx + 4 (l & 7) + cx, 32 ry + 4 (l >> 3) + cy),
+// clipped to the canvas.  g is wave-uniform: the division by the region count is scalar.
+__device__ __forceinline__ long long occl_pixel_class(int W, int H, int g, int lane) {
+    const int c = g & 15, rg = g >> 4;
+    const int n_rx = (W + 31) >> 5, ry = rg / n_rx, rx = rg - ry * n_rx;
+    const int x = 32 * rx + 4 * (lane & 7) + (c & 3), y = 32 * ry + 4 * (lane >> 3) + (c >> 2);
+    return (x < W && y < H) ? (long long)y * W + x : -1;
 }
 
 // The surface record: pixel i's primary hit as query_kernel's pixel mode finds it (camera_at's
@@ -2399,15 +2409,26 @@ __global__ __launch_bounds__(OCCL_BLOCK) void occl_surface_kernel(OcclParams P_a
 // primary hit.  After the loop one read-modify-write of the count (k0 = 0: the count starts at
 // zero and is not read); `resolve` (the call's last launch) writes the outputs for n_total samples.
 // No ray goes to memory.
-template <int TREE>
-__global__ __launch_bounds__(OCCL_BLOCK) void occlusion_kernel(OcclParams P_arg, SceneView S) {
-    (void)P_arg;
+//
+// IL: the interleaved pattern (rt_occl.h), a kernel of its own (occlusion_il_kernel) so that the
+// shared pattern's compiles to what it was.  Sample k's entry is 16 k + the pixel's class: under
+// OCCL_MAP_CLASS the class is the wave's (a scalar load as above), under the other maps it is the
+// lane's (a per-lane load; the wave's rays fan out over 16 directions).  Nothing else differs.
+template <int TREE, bool IL>
+__device__ __forceinline__ void occlusion_samples(const SceneView& S) {
     constexpr bool FT = TREE == QT_ORDERED, BRUTE = TREE == QT_BRUTE;
     const BvhRefs bv = stage_bvh<false, FT, false, BRUTE>(S, nullptr);
     const int g = occl_wave();
     if (g >= oparams().n_waves) return;                        // (wave-uniform)
-    const long long i = occl_pixel(oparams().map, oparams().W, oparams().H, g, (int)(threadIdx.x & 63));
+    const bool by_class = IL && oparams().map == OCCL_MAP_CLASS;   // (wave-uniform)
+    const long long i = by_class ? occl_pixel_class(oparams().W, oparams().H, g, (int)(threadIdx.x & 63))
+                                 : occl_pixel(oparams().map, oparams().W, oparams().H, g, (int)(threadIdx.x & 63));
     const bool in = i >= 0;
+    int cls = 0;                                               // IL: the lane's class (by_class: the wave's, g & 15)
+    if (IL && !by_class && in) {
+        const int W = oparams().W, y = (int)(i / W), x = (int)(i - (long long)y * W);
+        cls = rto::pixel_class(x, y);
+    }
     rto::Frame f = rto::make_frame(v3(0, 0, 0), v3(0, 0, 1));
     bool live = false;
     if (in) {
@@ -2425,7 +2446,10 @@ __global__ __launch_bounds__(OCCL_BLOCK) void occlusion_kernel(OcclParams P_arg,
     WaveCounters wc{0, 0, 0, 0};
     const int k0 = oparams().k0, k1 = k0 + oparams().samples;
     for (int k = k0; k < k1; k++) {
-        const V3 dk = ldc(oparams().table, k);
+        V3 dk;
+        if (!IL) dk = ldc(oparams().table, k);
+        else if (by_class) dk = ldc(oparams().table, rto::interleaved_entry(k, g & 15));
+        else dk = oparams().table[rto::interleaved_entry(k, cls)];
         const V3 raw = rto::raw_direction(f, dk);
         Ray r = make_ray(f.p, raw);                            // Ray ctor (geometry.h:216)
         const bool ok = live && rtk::finite3(raw) && rtk::ray_traceable(r);
@@ -2449,6 +2473,16 @@ __global__ __launch_bounds__(OCCL_BLOCK) void occlusion_kernel(OcclParams P_arg,
         if (P.rgba) P.rgba[i] = rto::grey(vis);
     }
 }
+template <int TREE>
+__global__ __launch_bounds__(OCCL_BLOCK) void occlusion_kernel(OcclParams P_arg, SceneView S) {
+    (void)P_arg;
+    occlusion_samples<TREE, false>(S);
+}
+template <int TREE>
+__global__ __launch_bounds__(OCCL_BLOCK) void occlusion_il_kernel(OcclParams P_arg, SceneView S) {
+    (void)P_arg;
+    occlusion_samples<TREE, true>(S);
+}
 
 // Test hook (rt_occlusion_rays): sample k0's ray of every pixel as occlusion_kernel forms it,
 // origin and RAW direction (before the Ray constructor), zeros where the primary misses.
@@ -2464,6 +2498,74 @@ __global__ __launch_bounds__(OCCL_BLOCK) void occl_rays_kernel(OcclParams P) {
     }
     float* ro = P.rays + 6 * i;
     ro[0] = o.x; ro[1] = o.y; ro[2] = o.z; ro[3] = d.x; ro[4] = d.y; ro[5] = d.z;
+}
+// The same in the interleaved pattern: pixel (x, y)'s entry 16 k0 + its class.
+__global__ __launch_bounds__(OCCL_BLOCK) void occl_rays_il_kernel(OcclParams P) {
+    const long long i = (long long)blockIdx.x * OCCL_BLOCK + threadIdx.x;
+    if (i >= (long long)P.W * P.H) return;
+    const int y = (int)(i / P.W), x = (int)(i - (long long)y * P.W);
+    const float4 a = P.surf[2 * i], c = P.surf[2 * i + 1];
+    V3 o = v3(0, 0, 0), d = v3(0, 0, 0);
+    if (a.w != 0.0f) {
+        const rto::Frame f = rto::make_frame(v3(a.x, a.y, a.z), v3(c.x, c.y, c.z));
+        o = rto::ray_origin(f, P.bias);
+        d = rto::raw_direction(f, P.table[rto::interleaved_entry(P.k0, rto::pixel_class(x, y))]);
+    }
+    float* ro = P.rays + 6 * i;
+    ro[0] = o.x; ro[1] = o.y; ro[2] = o.z; ro[3] = d.x; ro[4] = d.y; ro[5] = d.z;
+}
+
+// The filtered resolve (rt_occlusion_set_filter; rt_occl.h): visibility and rgba of every pixel from
+// the counts of the accepted taps among the 16 pixels C + (dx, dy), dx, dy in [-2, 1] -- a window
+// that holds each class of the interleaved pattern once.  One lane a pixel, a block a 32 x 8 tile
+// (OCCL_FILTER_TX x _TY).  The block stages its pixels' records and counts with the halo (35 x 11
+// entries) in LDS once, an array per field: a wave's 64 lanes are two rows of 32 consecutive
+// entries, so a tap read is two runs of consecutive dwords (no two lanes of a row on one bank).
+// A staged count < 0 means "not live": a pixel outside the canvas or without a primary hit; no tap
+// reads outside the canvas.  Reads surf and count, writes visibility and rgba only.
+__global__ __launch_bounds__(OCCL_FILTER_TX * OCCL_FILTER_TY) void occl_filter_kernel(OcclParams P) {
+    constexpr int LO = rto::AO_FILTER_LO, HI = rto::AO_FILTER_HI;
+    constexpr int SW = OCCL_FILTER_TX + LO + HI, SH = OCCL_FILTER_TY + LO + HI, SN = SW * SH;
+    __shared__ float spx[SN], spy[SN], spz[SN], snx[SN], sny[SN], snz[SN];
+    __shared__ int scnt[SN];
+    const int W = P.W, H = P.H;
+    const int x0 = (int)blockIdx.x * OCCL_FILTER_TX - LO, y0 = (int)blockIdx.y * OCCL_FILTER_TY - LO;
+    for (int e = (int)threadIdx.x; e < SN; e += OCCL_FILTER_TX * OCCL_FILTER_TY) {
+        const int sy = e / SW, sx = e - sy * SW, x = x0 + sx, y = y0 + sy;
+        float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), c = a;
+        int cnt = -1;
+        if (x >= 0 && x < W && y >= 0 && y < H) {
+            const long long i = (long long)y * W + x;
+            a = P.surf[2 * i];
+            if (a.w != 0.0f) { c = P.surf[2 * i + 1]; cnt = P.count[i]; }
+        }
+        spx[e] = a.x; spy[e] = a.y; spz[e] = a.z; snx[e] = c.x; sny[e] = c.y; snz[e] = c.z; scnt[e] = cnt;
+    }
+    __syncthreads();
+    const int tx = (int)threadIdx.x % OCCL_FILTER_TX, ty = (int)threadIdx.x / OCCL_FILTER_TX;
+    const int x = x0 + LO + tx, y = y0 + LO + ty;
+    if (x >= W || y >= H) return;
+    const int ce = (ty + LO) * SW + tx + LO;
+    float vis = 1.0f;                                          // a centre without a primary hit
+    if (scnt[ce] >= 0) {
+        const V3 pc = v3(spx[ce], spy[ce], spz[ce]), nc = v3(snx[ce], sny[ce], snz[ce]);
+        int sum = scnt[ce], m = 1;                             // the centre tap, unconditionally
+#pragma unroll
+        for (int dy = -LO; dy <= HI; dy++) {
+#pragma unroll
+            for (int dx = -LO; dx <= HI; dx++) {
+                if (dx == 0 && dy == 0) continue;
+                const int q = ce + dy * SW + dx, cq = scnt[q];
+                if (rto::filter_accept(pc, nc, v3(spx[q], spy[q], spz[q]), v3(snx[q], sny[q], snz[q]), cq >= 0, P.normal_min, P.plane_tol)) {
+                    sum += cq; m++;
+                }
+            }
+        }
+        vis = rto::filtered_visibility(sum, m, P.n_total);
+    }
+    const long long i = (long long)y * W + x;
+    if (P.visibility) P.visibility[i] = vis;
+    if (P.rgba) P.rgba[i] = rto::grey(vis);
 }
 
 // ---------------------------------------------------------------------------
@@ -3033,8 +3135,8 @@ hipError_t launch_accum_fold_tiles(const float4* pass, float4* sum_r, float4* su
 
 // The ambient-occlusion kernels (rt_occlusion): one surface and one occlusion kernel per tree form,
 // named here once.  occlusion_plan (rt_plan.h) decides which a call gets.
-struct OcclEntry { int tree; const void* surface; const void* occlusion; };
-#define OCK(TREE) OcclEntry{TREE, (const void*)occl_surface_kernel<TREE>, (const void*)occlusion_kernel<TREE>}
+struct OcclEntry { int tree; const void* surface; const void* occlusion; const void* interleaved; };
+#define OCK(TREE) OcclEntry{TREE, (const void*)occl_surface_kernel<TREE>, (const void*)occlusion_kernel<TREE>, (const void*)occlusion_il_kernel<TREE>}
 static const OcclEntry occl_kernels[] = {OCK(QT_ORDERED), OCK(QT_HEAP), OCK(QT_BRUTE)};
 #undef OCK
 static const OcclEntry* occl_entry(int tree) {
@@ -3054,14 +3156,22 @@ hipError_t launch_occlusion(const OcclPlan& plan, OcclParams& P, SceneView& S, h
     const OcclEntry* e = occl_entry(plan.tree);
     if (!e) return hipErrorInvalidValue;
     void* args[] = {&P, &S};
-    return hipExtLaunchKernel(e->occlusion, dim3(plan.blocks), dim3(plan.block), args, 0, st, e0, e1, 0);
+    return hipExtLaunchKernel(plan.pattern == OCCL_PATTERN_INTERLEAVED ? e->interleaved : e->occlusion, dim3(plan.blocks), dim3(plan.block),
+                              args, 0, st, e0, e1, 0);
+}
+
+hipError_t launch_occl_filter(const OcclPlan& plan, OcclParams& P, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
+    if ((long long)P.W * P.H <= 0) return hipSuccess;
+    void* args[] = {&P};
+    return hipExtLaunchKernel((const void*)occl_filter_kernel, dim3(plan.filter_bx, plan.filter_by), dim3(OCCL_FILTER_TX * OCCL_FILTER_TY),
+                              args, 0, st, e0, e1, 0);
 }
 
 hipError_t launch_occl_rays(OcclParams& P, hipStream_t st) {
     const long long px = (long long)P.W * P.H;
     if (px <= 0) return hipSuccess;
     void* args[] = {&P};
-    return hipExtLaunchKernel((const void*)occl_rays_kernel, dim3((unsigned)((px + OCCL_BLOCK - 1) / OCCL_BLOCK)), dim3(OCCL_BLOCK),
+    return hipExtLaunchKernel(P.pattern == OCCL_PATTERN_INTERLEAVED ? (const void*)occl_rays_il_kernel : (const void*)occl_rays_kernel, dim3((unsigned)((px + OCCL_BLOCK - 1) / OCCL_BLOCK)), dim3(OCCL_BLOCK),
                               args, 0, st, nullptr, nullptr, 0);
 }
 

@@ -4,6 +4,8 @@
 // raw direction of a sample and the resolve, as rt_accum.h is for rt_accumulate's fold.  Every
 // float step below is a single float32 + - x / (the build has no contraction), in the order
 // written; host and device agree bit for bit.  The direction table's generation is host only.
+// Further down: the interleaved pattern's entry index and the filtered resolve's accept test and
+// resolve (occlusion_il_kernel, occl_rays_il_kernel, occl_filter_kernel; tests/occl_filter_host.cpp).
 //
 //   p  = o + t d                      per component: t x d, then + o  (rtm::at)
 //   n  = the hit's normal, each component negated when dot(n, d) > 0 (rtm::dot: ((0 + x x) + y y) + z z)
@@ -51,6 +53,30 @@ RT_HD V3 raw_direction(const Frame& f, V3 dk) { return (dk.x * f.t1 + dk.y * f.t
 RT_HD float visibility(int count, int n) { return 1.0f - (float)count / (float)n; }
 // visibility as an opaque grey through Color's truncation (rta::pack)
 RT_HD uint32_t grey(float vis) { return rta::pack(rtm::v4(vis, vis, vis, 1.0f)); }
+
+// The interleaved pattern (RT_AO_PATTERN_INTERLEAVED): pixel (x, y) has class c = (x & 3) + 4 (y & 3)
+// and its sample k uses table entry 16 k + c; everything after the entry is the shared pattern's.
+// Any 4 x 4 window of pixels holds each class once, so after n samples it has used entries
+// 0 ... 16 n - 1, each exactly once.
+constexpr int AO_CLASSES = 16;
+constexpr int AO_INTERLEAVED_MAX_SAMPLES = AO_MAX_SAMPLES / AO_CLASSES;
+RT_HD int pixel_class(int x, int y) { return (x & 3) + 4 * (y & 3); }
+RT_HD int interleaved_entry(int k, int c) { return AO_CLASSES * k + c; }
+
+// The filtered resolve (rt_occlusion_set_filter): centre C = (pc, nc), tap Q = (pq, nq), both
+// surface records.  A tap is accepted when it is live, its normal is within normal_min of the
+// centre's and it lies within plane_tol of the centre's tangent plane:
+//   dot(nc, nq) >= normal_min   and   |dot(nc, e)| <= plane_tol,   e = pq - pc per component
+// (rtm::dot's order, one rounding each; a NaN accepts nothing).  The centre tap itself is accepted
+// by the caller without the test.  S: the integer sum of the m accepted taps' counts, n: samples held.
+constexpr int AO_FILTER_LO = 2, AO_FILTER_HI = 1;             // taps dx, dy in [-AO_FILTER_LO, AO_FILTER_HI]
+RT_HD bool filter_accept(V3 pc, V3 nc, V3 pq, V3 nq, bool live_q, float normal_min, float plane_tol) {
+    if (!live_q) return false;
+    if (!(rtm::dot(nc, nq) >= normal_min)) return false;
+    const V3 e = pq - pc;
+    return fabsf(rtm::dot(nc, e)) <= plane_tol;
+}
+RT_HD float filtered_visibility(int S, int m, int n) { return 1.0f - (float)S / (float)(m * n); }
 
 // Host only.  Entry k of the direction table: point k of the R2 sequence (rt::spp_offset's constants, in
 // double; k = 0 -> the pole) taken to the unit disk by (u, v) -> sqrt(u) (cos 2 pi v, sin 2 pi v)

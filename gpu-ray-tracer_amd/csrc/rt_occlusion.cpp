@@ -11,6 +11,8 @@ using namespace rti;
 
 namespace {
 static_assert(RT_AO_MAX_SAMPLES == rto::AO_MAX_SAMPLES, "the direction table's length");
+static_assert(RT_AO_INTERLEAVED_MAX_SAMPLES == rto::AO_INTERLEAVED_MAX_SAMPLES, "the interleaved pattern's samples");
+static_assert(RT_AO_PATTERN_SHARED == OCCL_PATTERN_SHARED && RT_AO_PATTERN_INTERLEAVED == OCCL_PATTERN_INTERLEAVED, "the patterns");
 
 // Has anything that decides an occlusion sample changed since the accumulation's first one?
 bool occl_stale(const rt_scene* s, float radius, float bias) {
@@ -56,11 +58,24 @@ void occl_launch_setup(rt_scene* s, bool use_bvh, OcclParams& P, SceneView& S, O
     P.radius = a.radius; P.bias = a.bias;
     P.zcut_scene = v.zcut_scene; P.any_margin = v.any_margin;
     P.table = a.d_table; P.surf = a.d_surf; P.count = a.d_count;
-    int map = -1;                                              // RT_OCCL_MAP (measurements): row / tile
-    if (const char* e = getenv("RT_OCCL_MAP")) map = !strcmp(e, "row") ? OCCL_MAP_ROW : !strcmp(e, "tile") ? OCCL_MAP_TILE : -1;
-    plan = occlusion_plan(P.W, P.H, S, map);
+    P.pattern = a.pattern; P.normal_min = a.normal_min; P.plane_tol = a.plane_tol;
+    int map = -1;                                              // RT_OCCL_MAP (measurements): row / tile / class (interleaved only)
+    if (const char* e = getenv("RT_OCCL_MAP"))
+        map = !strcmp(e, "row") ? OCCL_MAP_ROW : !strcmp(e, "tile") ? OCCL_MAP_TILE : !strcmp(e, "class") ? OCCL_MAP_CLASS : -1;
+    plan = occlusion_plan(P.W, P.H, S, map, a.pattern);
     P.map = plan.map; P.n_waves = plan.n_waves;
 }
+// The surface record is built under the shared pattern's plan whatever the pattern (occl_surface_kernel
+// knows the shared maps only; no result depends on the map).
+hipError_t launch_surface_record(const OcclPlan& plan, OcclParams P, SceneView& S, hipStream_t st) {
+    OcclPlan sp = plan;
+    if (plan.map == OCCL_MAP_CLASS) {
+        sp = occlusion_plan(P.W, P.H, S, -1, OCCL_PATTERN_SHARED);
+        P.map = sp.map; P.n_waves = sp.n_waves;
+    }
+    return launch_occl_surface(sp, P, S, st, nullptr, nullptr);
+}
+int pattern_capacity(int pattern) { return pattern == RT_AO_PATTERN_INTERLEAVED ? RT_AO_INTERLEAVED_MAX_SAMPLES : RT_AO_MAX_SAMPLES; }
 }  // namespace
 
 extern "C" {
@@ -81,8 +96,10 @@ int rt_occlusion(rt_scene* s, const rt_occlusion_opts* o, int* n_samples) {
     if (!(o->bias >= 0.0f && std::isfinite(o->bias))) return fail(RT_ERR_ARG, "rt_occlusion: bias must be finite and >= 0");
     if (!(o->visibility || o->occluded || o->rgba)) return fail(RT_ERR_ARG, "rt_occlusion: no output requested");
     const bool fresh = o->restart || occl_stale(s, o->radius, o->bias);
-    if ((long long)(fresh ? 0 : s->occl.n) + o->samples > RT_AO_MAX_SAMPLES)
-        return fail(RT_ERR_LIMIT, "rt_occlusion: more than 1024 samples held (rt_occlusion_reset starts again)");
+    if ((long long)(fresh ? 0 : s->occl.n) + o->samples > pattern_capacity(s->occl.pattern))
+        return fail(RT_ERR_LIMIT, s->occl.pattern == RT_AO_PATTERN_INTERLEAVED
+                                      ? "rt_occlusion: more than 64 samples held in the interleaved pattern (rt_occlusion_reset starts again)"
+                                      : "rt_occlusion: more than 1024 samples held (rt_occlusion_reset starts again)");
     if (s->multi) return fail(RT_ERR_STATE, "rt_occlusion: not on a scene split by rt_scene_set_devices");
     int r;
     if ((r = upload(s)) != RT_OK) return r;
@@ -108,9 +125,15 @@ int rt_occlusion(rt_scene* s, const rt_occlusion_opts* o, int* n_samples) {
     P.visibility = !o->visibility ? nullptr : host ? (float*)s->d_out[1] : o->visibility;
     P.occluded = !o->occluded ? nullptr : host ? (int*)s->d_out[2] : o->occluded;
     P.rgba = !o->rgba ? nullptr : host ? (uint32_t*)s->d_out[0] : o->rgba;
+    // the filtered resolve: the last launch resolves `occluded` only, occl_filter_kernel the other two
+    OcclParams F = P;
+    const bool filter = a.filter != 0 && (P.visibility || P.rgba);
+    if (filter) { P.visibility = nullptr; P.rgba = nullptr; }
+    a.last_map = plan.map;
     a.n = 0;                                                  // a failed launch leaves no samples, not stale counts
+    bool timed = false;
     if (px > 0) {
-        if (before == 0) HIPCHK(launch_occl_surface(plan, P, S, st, nullptr, nullptr));
+        if (before == 0) HIPCHK(launch_surface_record(plan, P, S, st));
         for (int done = 0; done < o->samples; done += OCCL_LAUNCH_SAMPLES) {
             P.k0 = before + done;
             P.samples = std::min(OCCL_LAUNCH_SAMPLES, o->samples - done);
@@ -118,15 +141,22 @@ int rt_occlusion(rt_scene* s, const rt_occlusion_opts* o, int* n_samples) {
             P.n_total = before + o->samples;
             HIPCHK(launch_occlusion(plan, P, S, st, nullptr, nullptr));
         }
+        if (filter) {
+            F.n_total = before + o->samples;
+            timed = a.time_filter;
+            if (timed && !a.ev0) { HIPCHK(hipEventCreate(&a.ev0)); HIPCHK(hipEventCreate(&a.ev1)); }
+            HIPCHK(launch_occl_filter(plan, F, st, timed ? a.ev0 : nullptr, timed ? a.ev1 : nullptr));
+        }
         HIPCHK(hipGetLastError());
     }
     if ((r = end_frame(s, st)) != RT_OK) return r;
     HIPCHK(hipStreamSynchronize(st));
     a.n = before + o->samples;
+    if (timed) HIPCHK(hipEventElapsedTime(&a.filter_ms, a.ev0, a.ev1));
     if (host) {
-        if (o->visibility) HIPCHK(hipMemcpy(o->visibility, P.visibility, px * 4, hipMemcpyDeviceToHost));
-        if (o->occluded) HIPCHK(hipMemcpy(o->occluded, P.occluded, px * 4, hipMemcpyDeviceToHost));
-        if (o->rgba) HIPCHK(hipMemcpy(o->rgba, P.rgba, px * 4, hipMemcpyDeviceToHost));
+        if (o->visibility) HIPCHK(hipMemcpy(o->visibility, F.visibility, px * 4, hipMemcpyDeviceToHost));
+        if (o->occluded) HIPCHK(hipMemcpy(o->occluded, F.occluded, px * 4, hipMemcpyDeviceToHost));
+        if (o->rgba) HIPCHK(hipMemcpy(o->rgba, F.rgba, px * 4, hipMemcpyDeviceToHost));
     }
     if (n_samples) *n_samples = a.n;
     return RT_OK;
@@ -145,6 +175,44 @@ int rt_occlusion_info(const rt_scene* s, int32_t* out4) {
     return RT_OK;
 }
 
+// The direction pattern (rt_amd.h): part of what an accumulation was started with.
+int rt_occlusion_set_pattern(rt_scene* s, int pattern) {
+    CHECK_SCENE(s);
+    if (pattern != RT_AO_PATTERN_SHARED && pattern != RT_AO_PATTERN_INTERLEAVED)
+        return fail(RT_ERR_ARG, "rt_occlusion_set_pattern: RT_AO_PATTERN_SHARED or RT_AO_PATTERN_INTERLEAVED");
+    if (pattern == s->occl.pattern) return RT_OK;
+    occl_drop(s);
+    s->occl.pattern = pattern;
+    return RT_OK;
+}
+
+// The filtered resolve (rt_amd.h): outputs only, the counts do not depend on it.
+int rt_occlusion_set_filter(rt_scene* s, int on, float normal_min, float plane_tol) {
+    CHECK_SCENE(s);
+    if (on != 0 && on != 1) return fail(RT_ERR_ARG, "rt_occlusion_set_filter: on is 0 or 1");
+    if (!(normal_min >= -1.0f && normal_min <= 1.0f)) return fail(RT_ERR_ARG, "rt_occlusion_set_filter: normal_min in [-1, 1] required");
+    if (!(plane_tol >= 0.0f && std::isfinite(plane_tol))) return fail(RT_ERR_ARG, "rt_occlusion_set_filter: plane_tol must be finite and >= 0");
+    s->occl.filter = on;
+    if (on) { s->occl.normal_min = normal_min; s->occl.plane_tol = plane_tol; }
+    return RT_OK;
+}
+
+// Measurement hook: occl_filter_kernel's own time, by start/stop events on its dispatch.
+int rt_occlusion_filter_timing(rt_scene* s, int on, float* ms) {
+    CHECK_SCENE(s);
+    s->occl.time_filter = on != 0;
+    if (ms) *ms = s->occl.filter_ms;
+    return RT_OK;
+}
+
+int rt_occlusion_config(const rt_scene* s, int32_t* out4, float* f2) {
+    CHECK_SCENE(s);
+    const rt_scene::Occl& a = s->occl;
+    if (out4) { out4[0] = a.pattern; out4[1] = a.filter; out4[2] = pattern_capacity(a.pattern); out4[3] = a.last_map; }
+    if (f2) { f2[0] = a.normal_min; f2[1] = a.plane_tol; }
+    return RT_OK;
+}
+
 int rt_ao_direction(int k, float* out3) {
     if (k < 0 || k >= RT_AO_MAX_SAMPLES || !out3) return fail(RT_ERR_ARG, "rt_ao_direction: 0 <= k < 1024 and a destination");
     rto::ao_direction(k, out3);
@@ -156,6 +224,7 @@ int rt_ao_direction(int k, float* out3) {
 int rt_occlusion_rays(rt_scene* s, int k, float* dst, int64_t cap_floats) {
     CHECK_FINISHED(s);
     if (!dst || k < 0 || k >= RT_AO_MAX_SAMPLES) return fail(RT_ERR_ARG, "rt_occlusion_rays: 0 <= k < 1024 and a destination");
+    if (k >= pattern_capacity(s->occl.pattern)) return fail(RT_ERR_ARG, "rt_occlusion_rays: 0 <= k < 64 in the interleaved pattern");
     const size_t px = (size_t)s->h.cam.W * s->h.cam.H;
     if (cap_floats < (int64_t)(px * 6)) return fail(RT_ERR_ARG, "rt_occlusion_rays: buffer below W * H * 6 floats");
     if (s->occl.n <= 0) return fail(RT_ERR_STATE, "rt_occlusion_rays: no accumulation (after rt_occlusion)");

@@ -382,30 +382,56 @@ inline QueryKey query_plan(long long n_rays, const SceneView& S, bool any_hit, b
 // staged: DESIGN §3.5 found no crossover to the persistent form).  One pixel per lane; a wave takes
 // 64 consecutive pixels of the row-major frame (OCCL_MAP_ROW: runs continue into the next row) or
 // an 8 x 8 tile clipped to the canvas (OCCL_MAP_TILE).  Measured on world8_stress 1920 x 1080
-// (profiles/occlusion/bench.txt); map < 0: the default.  A call's samples go in
+// (profiles/occlusion/bench.txt); map < 0: the pattern's default.  A call's samples go in
 // launches of at most OCCL_LAUNCH_SAMPLES directions, so that no single dispatch runs for long.
-enum : int { OCCL_MAP_ROW = 0, OCCL_MAP_TILE = 1 };
+enum : int { OCCL_MAP_ROW = 0, OCCL_MAP_TILE = 1, OCCL_MAP_CLASS = 2 };
 #ifndef RT_OCCL_MAP_DEFAULT
 #define RT_OCCL_MAP_DEFAULT OCCL_MAP_TILE
 #endif
+// The interleaved direction pattern (OCCL_PATTERN_INTERLEAVED = RT_AO_PATTERN_INTERLEAVED; rt_occl.h):
+// under OCCL_MAP_TILE a wave holds all 16 pixel classes, so the table entry is a per-lane load and
+// the wave's rays fan out over 16 directions.  OCCL_MAP_CLASS (this pattern only) gives wave g one
+// class of one 32 x 32 pixel region clipped to the canvas -- ceil(W/32) ceil(H/32) regions, 16 waves
+// a region, region = g / 16 and class = g % 16, lane l the pixel (32 rx + 4 (l & 7) + cx,
+// 32 ry + 4 (l >> 3) + cy) -- so the entry is wave-uniform again, at the price of a 4-pixel stride
+// in the surface-record reads and the count's read-modify-write.  Measured on world8_stress
+// 1920 x 1080, 16 samples (profiles/occlusion_filter/bench.txt): the class map is the
+// pattern's default, 1.03 ms against the tile map's 3.02 ms at radius +inf, 1.78 against 6.97 at
+// radius 2.  The surface record is built under the shared pattern's plan in either pattern.
+enum : int { OCCL_PATTERN_SHARED = 0, OCCL_PATTERN_INTERLEAVED = 1 };
+#ifndef RT_OCCL_MAP_INTERLEAVED_DEFAULT
+#define RT_OCCL_MAP_INTERLEAVED_DEFAULT OCCL_MAP_CLASS
+#endif
 constexpr int OCCL_BLOCK = 256;
 constexpr int OCCL_LAUNCH_SAMPLES = 64;
+// The filtered resolve (occl_filter_kernel): one lane a pixel, a block a 32 x 8 pixel tile whose
+// records and counts, with the taps' halo (2 to the left and above, 1 to the right and below),
+// are staged in LDS once, an array per field.
+constexpr int OCCL_FILTER_TX = 32, OCCL_FILTER_TY = 8;
 struct OcclPlan {
     int tree;                 // QT_*
     int map;                  // OCCL_MAP_*
-    int n_waves;              // waves with a pixel: 64-pixel runs, or tiles
+    int n_waves;              // waves with a pixel: 64-pixel runs, tiles, or 16 a 32 x 32 region
     int block, blocks;        // the launch: dim3(blocks), dim3(block)
+    int pattern;              // OCCL_PATTERN_*
+    int filter_bx, filter_by; // occl_filter_kernel's grid: dim3(filter_bx, filter_by), OCCL_FILTER_TX * OCCL_FILTER_TY threads
 };
-inline OcclPlan occlusion_plan(int W, int H, const SceneView& S, int map = -1) {
+inline OcclPlan occlusion_plan(int W, int H, const SceneView& S, int map = -1, int pattern = OCCL_PATTERN_SHARED) {
     OcclPlan p{};
     p.tree = query_plan((long long)W * H, S, true, false, 0, 0).tree;
-    p.map = map == OCCL_MAP_ROW || map == OCCL_MAP_TILE ? map : RT_OCCL_MAP_DEFAULT;
+    p.pattern = pattern == OCCL_PATTERN_INTERLEAVED ? OCCL_PATTERN_INTERLEAVED : OCCL_PATTERN_SHARED;
+    const bool il = p.pattern == OCCL_PATTERN_INTERLEAVED;
+    p.map = map == OCCL_MAP_ROW || map == OCCL_MAP_TILE || (il && map == OCCL_MAP_CLASS) ? map
+            : il ? RT_OCCL_MAP_INTERLEAVED_DEFAULT : RT_OCCL_MAP_DEFAULT;
     const long long px = (long long)W * H;
-    const long long waves = p.map == OCCL_MAP_TILE ? (long long)((W + 7) / 8) * ((H + 7) / 8) : (px + 63) / 64;
+    const long long waves = p.map == OCCL_MAP_CLASS ? 16ll * ((W + 31) / 32) * ((H + 31) / 32)
+                            : p.map == OCCL_MAP_TILE ? (long long)((W + 7) / 8) * ((H + 7) / 8) : (px + 63) / 64;
     constexpr int BLOCK_WAVES = OCCL_BLOCK / 64;
     p.n_waves = (int)std::min<long long>(waves, INT32_MAX);
     p.block = OCCL_BLOCK;
     p.blocks = (int)std::max(1ll, (waves + BLOCK_WAVES - 1) / BLOCK_WAVES);
+    p.filter_bx = std::max(1, (W + OCCL_FILTER_TX - 1) / OCCL_FILTER_TX);
+    p.filter_by = std::max(1, (H + OCCL_FILTER_TY - 1) / OCCL_FILTER_TY);
     return p;
 }
 

@@ -48,13 +48,19 @@ SYMBOLS = [
     "rt_accumulate_set_adaptive", "rt_accumulate_adaptive_info", "rt_accumulate_pass_fill", "rt_accumulate_pass_read",
     "rt_scene_history_info",
     "rt_occlusion_opts_default", "rt_occlusion", "rt_occlusion_reset", "rt_occlusion_info", "rt_ao_direction",
-    "rt_occlusion_rays",
+    "rt_occlusion_rays", "rt_occlusion_set_pattern", "rt_occlusion_set_filter", "rt_occlusion_config",
+    "rt_occlusion_filter_timing",
     "rt_scene_set_shadow_hints", "rt_scene_shadow_hints_fill", "rt_scene_shadow_hint_code",
     "rt_scene_shadow_hint_counters", "rt_scene_shadow_hints_read",
 ]
 RT_QUERY_ORDER_CALLER, RT_QUERY_ORDER_SORTED = 0, 1
 RT_ADAPTIVE_THRESHOLD_DEFAULT = 8.0 / 255.0
 RT_AO_MAX_SAMPLES, RT_AO_BIAS_DEFAULT = 1024, 1e-3
+RT_AO_PATTERN_SHARED, RT_AO_PATTERN_INTERLEAVED = 0, 1
+RT_AO_INTERLEAVED_MAX_SAMPLES = RT_AO_MAX_SAMPLES // 16
+RT_AO_FILTER_NORMAL_DEFAULT, RT_AO_FILTER_PLANE_DEFAULT = 0.9, 1e-2
+AO_PATTERNS = {"shared": RT_AO_PATTERN_SHARED, "interleaved": RT_AO_PATTERN_INTERLEAVED}
+OCCL_MAPS = {-1: None, 0: "row", 1: "tile", 2: "class"}     # rt_occlusion_config's out4[3]
 
 
 class RtError(RuntimeError):
@@ -213,6 +219,11 @@ def lib():
         L.rt_occlusion_info.argtypes = [vp, vp]
         L.rt_ao_direction.argtypes = [ip, vp]
         L.rt_occlusion_rays.argtypes = [vp, ip, vp, ctypes.c_int64]
+    if hasattr(L, "rt_occlusion_set_pattern"):  # (absent from libraries before the interleaved pattern: A/B runs)
+        L.rt_occlusion_set_pattern.argtypes = [vp, ip]
+        L.rt_occlusion_set_filter.argtypes = [vp, ip, ctypes.c_float, ctypes.c_float]
+        L.rt_occlusion_config.argtypes = [vp, vp, vp]
+        L.rt_occlusion_filter_timing.argtypes = [vp, ip, ctypes.POINTER(ctypes.c_float)]
     if hasattr(L, "rt_query_set_order"):        # (absent from libraries before the coherence sort: A/B runs)
         L.rt_query_set_order.argtypes = [vp, ip]
         L.rt_query_last.argtypes = [vp, vp, vp, vp, ctypes.c_int64]
@@ -677,6 +688,35 @@ class Scene:
         a = np.zeros(4, np.int32)
         _check(lib().rt_occlusion_info(self._h, _ptr(a)))
         return tuple(int(x) for x in a)
+
+    def set_occlusion_pattern(self, pattern):
+        """"shared" (every pixel's sample k uses table entry k) or "interleaved" (entry 16 k + the
+        pixel's class (x & 3) + 4 (y & 3); at most 64 samples).  A change drops the samples held
+        (rt_occlusion_set_pattern)."""
+        _check(lib().rt_occlusion_set_pattern(self._h, AO_PATTERNS[pattern] if isinstance(pattern, str) else int(pattern)))
+
+    def set_occlusion_filter(self, on=True, normal_min=RT_AO_FILTER_NORMAL_DEFAULT, plane_tol=RT_AO_FILTER_PLANE_DEFAULT):
+        """The filtered resolve on or off: visibility and rgba averaged over the taps of a 4 x 4
+        window that lie on the centre's surface; the counts stay raw and nothing restarts
+        (rt_occlusion_set_filter)."""
+        _check(lib().rt_occlusion_set_filter(self._h, int(on), float(normal_min), float(plane_tol)))
+
+    @property
+    def occlusion_config(self):
+        """{"pattern": "shared" | "interleaved", "filter": bool, "capacity": samples the pattern can
+        hold, "map": "row" | "tile" | "class" of the last call or None, "normal_min", "plane_tol"}
+        (rt_occlusion_config)."""
+        a, f = np.zeros(4, np.int32), np.zeros(2, np.float32)
+        _check(lib().rt_occlusion_config(self._h, _ptr(a), _ptr(f)))
+        return {"pattern": "interleaved" if a[0] == RT_AO_PATTERN_INTERLEAVED else "shared", "filter": bool(a[1]),
+                "capacity": int(a[2]), "map": OCCL_MAPS[int(a[3])], "normal_min": float(f[0]), "plane_tol": float(f[1])}
+
+    def filter_timing(self, on=True):
+        """Measurement hook: time occl_filter_kernel's dispatch of later filtered calls with start/stop
+        events (or stop); returns the last timed dispatch's ms, < 0: none yet (rt_occlusion_filter_timing)."""
+        ms = ctypes.c_float(-1.0)
+        _check(lib().rt_occlusion_filter_timing(self._h, int(on), ctypes.byref(ms)))
+        return ms.value
 
     def _occlusion_rays(self, k):
         """Test hook: the rays sample k traces for the current accumulation, (H, W, 6) float32:

@@ -37,7 +37,9 @@ extern "C" {
  *    (still 5: additive -- rt_accumulate_set_adaptive / rt_accumulate_adaptive_info and the pass
  *    buffer's test hooks; rt_accum_opts keeps its layout, the switch is scene state)
  *    (still 5: additive -- rt_occlusion and its companions, rt_ao_direction; no existing entry or
- *    struct changed) */
+ *    struct changed)
+ *    (still 5: additive -- rt_occlusion_set_pattern / rt_occlusion_set_filter / rt_occlusion_config
+ *    and the measurement hook rt_occlusion_filter_timing; rt_occlusion_opts keeps its layout, both switches are scene state) */
 #define RT_ABI_VERSION 5
 
 enum {
@@ -418,6 +420,51 @@ int rt_ao_direction(int k, float out3[3]);
  * W*H*6 floats to host memory: origin, RAW direction before the Ray constructor; zeros where the
  * primary misses.  RT_ERR_STATE without an accumulation. */
 int rt_occlusion_rays(rt_scene* s, int k, float* dst, int64_t cap_floats);
+
+/* ---- ambient occlusion: interleaved directions and a geometry-aware filter (still ABI 5: additive) ----
+ * Two opt-in pieces of scene state, host state both (no device needed).  With the pattern shared
+ * and the filter off -- the defaults -- rt_occlusion writes every byte as described above.
+ *
+ * Direction pattern.  RT_AO_PATTERN_SHARED: every pixel's sample k uses table entry k (above): an
+ * image of n samples is n shadow layers, n + 1 grey levels.  RT_AO_PATTERN_INTERLEAVED: pixel
+ * (x, y) has class c = (x & 3) + 4 (y & 3) and its sample k uses entry 16 k + c of the same
+ * table; origin, raw direction, the Ray constructor, the accept rule, the rejected-ray rule and
+ * the count are as above with that entry in place of entry k (no new float arithmetic).  After n
+ * samples any 4 x 4 window of pixels has used entries 0 ... 16 n - 1 between its pixels, each
+ * exactly once.  The pattern holds at most RT_AO_INTERLEAVED_MAX_SAMPLES samples: a call that
+ * would hold more returns RT_ERR_LIMIT, checked with the arguments; rt_occlusion_rays(s, k, ...)
+ * exports entry 16 k + c per pixel and accepts 0 <= k < RT_AO_INTERLEAVED_MAX_SAMPLES.  The
+ * pattern reaches rt_occlusion and rt_occlusion_rays only and is part of what an accumulation was
+ * started with: a call that changes it while samples are held drops them (one restart, as
+ * rt_accumulate_set_adaptive); a call that changes nothing does nothing.  RT_ERR_ARG: any other
+ * value.  A split scene may set it (rt_occlusion refuses split scenes).
+ *
+ * Filtered resolve.  The counts do not depend on it, so setting it restarts nothing; the next
+ * rt_occlusion call's outputs follow the new setting.  With the filter on, after a call that
+ * leaves n samples held: occluded[pixel] is the raw count, unchanged.  A pixel is live when it has
+ * a primary hit.  For a live centre C with surface record (p_C, n_C) the taps are the 16 pixels
+ * Q = C + (dx, dy), dx, dy in {-2, -1, 0, 1}, that lie inside the canvas (any such window holds
+ * each class once).  Tap Q is accepted when Q is live, dot(n_C, n_Q) >= normal_min and
+ * fabsf(dot(n_C, e)) <= plane_tol with e = p_Q - p_C per component: float32, one rounding per
+ * operation, dot as ((0 + x x) + y y) + z z; a NaN accepts nothing.  The centre tap is accepted
+ * unconditionally.  With S the integer sum of the accepted taps' counts and m their number:
+ * visibility = 1.0f - (float)S / (float)(m * n), rgba = its grey as above.  A centre without a
+ * primary hit has visibility 1.  The filter works with either pattern.
+ * RT_ERR_ARG: on outside {0, 1}; normal_min NaN or outside [-1, 1]; plane_tol negative, NaN or
+ * infinite (validated, then ignored, with on = 0). */
+enum { RT_AO_PATTERN_SHARED = 0, RT_AO_PATTERN_INTERLEAVED = 1 };
+#define RT_AO_INTERLEAVED_MAX_SAMPLES (RT_AO_MAX_SAMPLES / 16)   /* 64 */
+#define RT_AO_FILTER_NORMAL_DEFAULT 0.9f
+#define RT_AO_FILTER_PLANE_DEFAULT  1e-2f  /* world units: far above the rounding of p, far below a cube's edge */
+int rt_occlusion_set_pattern(rt_scene* s, int pattern);
+int rt_occlusion_set_filter(rt_scene* s, int on, float normal_min, float plane_tol);
+/* out4 = {pattern, filter on, samples the pattern can hold, OCCL_MAP_* the last call used (-1: none yet;
+ * 0 row, 1 tile, 2 class: the lane-to-pixel mapping, on which no result depends)};
+ * f2 = {normal_min, plane_tol}; either may be NULL.  Host state. */
+int rt_occlusion_config(const rt_scene* s, int32_t out4[4], float f2[2]);
+/* Measurement hook: with `on`, later filtered calls take start/stop events on occl_filter_kernel's
+ * dispatch; *ms (may be NULL): the last timed dispatch's milliseconds, < 0: none yet.  Host state. */
+int rt_occlusion_filter_timing(rt_scene* s, int on, float* ms);
 
 /* Frame slots (1 = default, up to 8).  The reference rebuilds its BVH inside every
  * update_scene call (raytracer.cu:103-119), so a frame owns per-frame state: BVH, work

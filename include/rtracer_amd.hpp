@@ -264,6 +264,16 @@ inline int occlusion(renv::gpu::Scene* scene, std::vector<float>& visibility, in
     rtamd_detail::check(rt_occlusion(scene->handle(), &o, &n), "occlusion");
     return n;
 }
+// Build extensions (rt_occlusion_set_pattern / rt_occlusion_set_filter): the direction pattern of
+// occlusion()'s samples (RT_AO_PATTERN_*; a change drops the samples held) and the filtered
+// resolve of its visibility (taps of a 4 x 4 window on the centre's surface).
+inline void set_occlusion_pattern(renv::gpu::Scene* scene, int pattern) {
+    rtamd_detail::check(rt_occlusion_set_pattern(scene->handle(), pattern), "set_occlusion_pattern");
+}
+inline void set_occlusion_filter(renv::gpu::Scene* scene, bool on = true, float normal_min = RT_AO_FILTER_NORMAL_DEFAULT,
+                                 float plane_tol = RT_AO_FILTER_PLANE_DEFAULT) {
+    rtamd_detail::check(rt_occlusion_set_filter(scene->handle(), on ? 1 : 0, normal_min, plane_tol), "set_occlusion_filter");
+}
 // raytracer.cu:91-100: one-pixel trace with the reference's event log on stdout.
 inline void debug_cast(renv::gpu::Scene* scene, int x, int y) {
     std::vector<char> buf(1 << 16);

@@ -12,7 +12,16 @@ per result:
   - occlusion rays per second of both (rays = samples x pixels with a primary hit);
   - the fused pass under both lane mappings (RT_OCCL_MAP = row / tile);
   - the fused pass continuing an accumulation (16 more samples, no surface record).
-Usage: python tools/occlusion_bench.py [scene] [W] [H] [calls] [samples]"""
+Then the interleaved pattern and the filtered resolve (section "filter"), same protocol:
+  - the shared pattern, and the interleaved pattern under both of its lane mappings (RT_OCCL_MAP =
+    tile / class): `class` counts as faster only when its median is below `tile`'s by more than the
+    larger of the two spreads, at both radii;
+  - a call with the filter on against the same call with it off (visibility and rgba written), and
+    occl_filter_kernel's own time by start/stop events on its dispatch (rt_occlusion_filter_timing);
+  - a quality table: the mean absolute difference of `visibility`, over the pixels with a primary
+    hit, from the shared pattern's 1024-sample frame at the same radius, for shared n = 4, 16, 64,
+    interleaved n = 4, interleaved n = 4 + filter, shared n = 4 + filter (a record, no threshold).
+Usage: python tools/occlusion_bench.py [scene] [W] [H] [calls] [samples] [all|base|filter]"""
 import json
 import os
 import sys
@@ -29,6 +38,8 @@ scene = sys.argv[1] if len(sys.argv) > 1 else "world8_stress"
 W, H = (int(sys.argv[2]), int(sys.argv[3])) if len(sys.argv) > 3 else (1920, 1080)
 calls = int(sys.argv[4]) if len(sys.argv) > 4 else 30
 K = int(sys.argv[5]) if len(sys.argv) > 5 else 16
+SECTIONS = sys.argv[6] if len(sys.argv) > 6 else "all"
+assert SECTIONS in ("all", "base", "filter"), SECTIONS
 REPS, WARM = 5, 3
 rtamd.set_device(0)
 s = rtamd.Scene.load_json(os.path.join(ROOT, "scenes", scene + ".json"), W, H)
@@ -64,7 +75,7 @@ occ = torch.empty((H, W), dtype=torch.int32, device="cuda")
 flags = torch.empty(n_px, dtype=torch.uint8, device="cuda")
 torch.cuda.synchronize()
 
-for radius in (float("inf"), 2.0):
+for radius in (float("inf"), 2.0) if SECTIONS != "filter" else ():
     rname = "inf" if radius == float("inf") else radius
     tmax = torch.full((n_px,), radius, dtype=torch.float32, device="cuda")
 
@@ -119,3 +130,79 @@ for radius in (float("inf"), 2.0):
     fused()                                                        # 16 held; one block of calls stays under the limit
     out(what="continuing (no surface record)", radius=rname, fused=summary(medians(more, reps=1)))
     del origins, dirs
+
+# ---- the interleaved pattern and the filtered resolve ----
+rgba = torch.empty((H, W), dtype=torch.int32, device="cuda")
+torch.cuda.synchronize()
+decision = []
+for radius in (float("inf"), 2.0) if SECTIONS != "base" else ():
+    rname = "inf" if radius == float("inf") else radius
+
+    def call(samples=K):
+        return s.occlusion_device(samples=samples, radius=radius, restart=True, visibility_ptr=vis.data_ptr(), occluded_ptr=occ.data_ptr(),
+                                  rgba_ptr=rgba.data_ptr())
+
+    def frame(samples):
+        call(samples)
+        return vis.cpu().numpy().copy()
+
+    s.set_occlusion_pattern("shared")
+    s.set_occlusion_filter(False)
+    shared = summary(medians(call))
+    out(what="pattern", radius=rname, pattern="shared", filter=False, outputs="visibility, occluded, rgba", fused=shared)
+    s.set_occlusion_pattern("interleaved")
+    res, count = {}, None
+    for m in ("tile", "class"):
+        os.environ["RT_OCCL_MAP"] = m
+        call()
+        assert s.occlusion_config["map"] == m
+        c = occ.cpu().numpy().copy()
+        assert count is None or np.array_equal(c, count), m       # no result depends on the map
+        count = c
+        res[m] = summary(medians(call))
+        out(what="pattern", radius=rname, pattern="interleaved", map=m, filter=False, fused=res[m],
+            per_sample_over_shared=round(res[m]["median_ms"] / shared["median_ms"], 3))
+    del os.environ["RT_OCCL_MAP"]
+    margin = max(res["tile"]["spread_ms"], res["class"]["spread_ms"])
+    decision.append(res["class"]["median_ms"] < res["tile"]["median_ms"] - margin)
+    out(what="interleaved map", radius=rname, class_is_faster=bool(decision[-1]), margin_ms=margin)
+
+    # the filter: the whole call on / off (the build's default map), and the kernel alone
+    for pattern in ("shared", "interleaved"):
+        s.set_occlusion_pattern(pattern)
+        s.set_occlusion_filter(False)
+        off = summary(medians(call))
+        s.set_occlusion_filter(True)
+        on = summary(medians(call))
+        s.filter_timing(True)
+        ks = []
+        for _ in range(REPS):
+            t = []
+            for _ in range(calls):
+                call()
+                t.append(s.filter_timing(True))
+            ks.append(sorted(t)[len(t) // 2])
+        s.filter_timing(False)
+        s.set_occlusion_filter(False)
+        out(what="filter", radius=rname, pattern=pattern, map=s.occlusion_config["map"], call_filter_off=off, call_filter_on=on,
+            occl_filter_kernel=summary(ks))
+
+    # quality: mean |visibility - the shared pattern's 1024-sample frame| over the hit pixels
+    s.set_occlusion_pattern("shared")
+    ref = frame(1024)
+    hit = s.query(pixels=np.stack(np.mgrid[0:H, 0:W][::-1], axis=-1).reshape(-1, 2).astype(np.int32), want=("hit",))["hit"].reshape(H, W) != 0
+    table = {}
+    for name, pattern, n, filt in (("shared n=4", "shared", 4, False), ("shared n=16", "shared", 16, False), ("shared n=64", "shared", 64, False),
+                                   ("interleaved n=4", "interleaved", 4, False), ("interleaved n=4 + filter", "interleaved", 4, True),
+                                   ("shared n=4 + filter", "shared", 4, True)):
+        s.set_occlusion_pattern(pattern)
+        s.set_occlusion_filter(filt)
+        v = frame(n)
+        table[name] = round(float(np.abs(v[hit] - ref[hit]).mean()), 5)
+        levels = len(np.unique(v[hit]))
+        table[name + " (grey levels)"] = levels
+    s.set_occlusion_pattern("shared")
+    s.set_occlusion_filter(False)
+    out(what="quality: mean |visibility - shared n=1024| over hit pixels", radius=rname, hit_pixels=int(hit.sum()), table=table)
+if decision:
+    out(what="interleaved map decision", class_becomes_default=bool(all(decision)), per_radius=[bool(d) for d in decision])
