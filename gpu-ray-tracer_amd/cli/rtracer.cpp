@@ -3,7 +3,7 @@
 //   rtracer -c world8.json [-b] [-r] [-s] [-d DIM] [--frames N] [--spp K]
 //           [--width W --height H] [--out frame.ppm] [--debug X,Y] [--textures [ATLAS.png]]
 //           [--gpus N [--ranks R]] [--in-flight D] [--pick X,Y] [--accumulate N [--adaptive [THR]]]
-//           [--occlusion N [--radius R] [--interleave] [--filter]]
+//           [--occlusion N [--radius R] [--interleave] [--filter] [--history [M] [--pan D]]]
 //
 // -c config (worldN.json), -b benchmark (one timed frame, "Time: X ms" as main.cc:210-216),
 // -r unoptimize (brute force, no BVH), -d kernel dimension (accepted; the HIP path
@@ -33,6 +33,11 @@
 // --interleave (with --occlusion only; rt_occlusion_set_pattern): the pixels of a 4 x 4 block take
 // different directions (N <= 64).  --filter (with --occlusion only; rt_occlusion_set_filter, its
 // default parameters): the frame is resolved through the geometry-aware 4 x 4 filter.
+// --history [M] (with --occlusion only; rt_occlusion_set_history, at most M samples carried, default
+// 32): --frames calls of N samples each, the camera translated by (D, 0, 0) (--pan D, default 0.05;
+// rt_camera_translate) before every call but the first, so that every call after the first is a
+// move that keeps the samples by reprojection; prints the moves and the sample cursor after each
+// call, and --out writes the last frame.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -51,7 +56,8 @@ static void usage() {
                  "usage: rtracer -c CONFIG [-b] [-r] [-s] [-d DIM] [--frames N] [--spp K] [--width W --height H]\n"
                  "               [--out FILE.ppm] [--debug X,Y] [--textures [ATLAS.png]] [--gpus N [--ranks R]]\n"
                  "               [--in-flight D [--readback] [--overlap stream|half|full]] [--pick X,Y]\n"
-                 "               [--accumulate N [--adaptive [THR]]] [--occlusion N [--radius R] [--interleave] [--filter]]\n");
+                 "               [--accumulate N [--adaptive [THR]]] [--occlusion N [--radius R] [--interleave] [--filter]\n"
+                 "               [--history [M] [--pan D]]]\n");
 }
 
 static bool write_ppm(const char* path, const uint32_t* px, int w, int h) {
@@ -72,7 +78,9 @@ static bool write_ppm(const char* path, const uint32_t* px, int w, int h) {
 
 int main(int argc, char** argv) {
     std::string config, out;
-    bool bench = false, unopt = false, serial = false, textures = false, readback = false, adaptive = false, interleave = false, filter = false;
+    bool bench = false, unopt = false, serial = false, textures = false, readback = false, adaptive = false, interleave = false, filter = false, history = false, pan_given = false;
+    int max_history = RT_AO_HISTORY_DEFAULT;
+    float pan = 0.05f;
     float adaptive_thr = RT_ADAPTIVE_THRESHOLD_DEFAULT;
     std::string atlas, overlap = "stream";
     int dim = 16, frames = 1, spp = 1, width = 0, height = 0, dbg_x = -1, dbg_y = -1, pick_x = -1, pick_y = -1, gpus = 1, ranks = 0, in_flight = 0, accumulate = 0, occlusion = 0;
@@ -114,6 +122,21 @@ int main(int argc, char** argv) {
         }
         else if (a == "--interleave") interleave = true;
         else if (a == "--filter") filter = true;
+        else if (a == "--history") {
+            history = true;
+            if (i + 1 < argc && argv[i + 1][0] != '-') {
+                char* end = nullptr;
+                max_history = (int)std::strtol(argv[++i], &end, 10);
+                if (end == argv[i] || *end) { usage(); return 2; }
+            }
+        }
+        else if (a == "--pan") {
+            char* end = nullptr;
+            const char* v = val("--pan");
+            pan = std::strtof(v, &end);
+            pan_given = true;
+            if (end == v || *end) { usage(); return 2; }
+        }
         else if (a == "--readback") readback = true;
         else if (a == "--overlap") {
             overlap = val("--overlap");
@@ -139,6 +162,8 @@ int main(int argc, char** argv) {
     if (adaptive && accumulate < 1) { std::fprintf(stderr, "--adaptive needs --accumulate N\n"); usage(); return 2; }
     if (radius > 0.0f && occlusion < 1) { std::fprintf(stderr, "--radius needs --occlusion N\n"); usage(); return 2; }
     if ((interleave || filter) && occlusion < 1) { std::fprintf(stderr, "--interleave and --filter need --occlusion N\n"); usage(); return 2; }
+    if (history && occlusion < 1) { std::fprintf(stderr, "--history needs --occlusion N\n"); usage(); return 2; }
+    if (pan_given && !history) { std::fprintf(stderr, "--pan needs --history\n"); usage(); return 2; }
     // frames in flight use a stream each: HIP maps streams round-robin onto GPU_MAX_HW_QUEUES
     // hardware queues (4 by default), and streams sharing a queue serialise.
     // The HIP runtime reads it when librt_amd.so's kernels are registered, before main: set it
@@ -187,16 +212,30 @@ int main(int argc, char** argv) {
         o.host_outputs = 1; o.rgba = frame.data();
         if (interleave) rtamd_detail::check(rt_occlusion_set_pattern(handle, RT_AO_PATTERN_INTERLEAVED), "rt_occlusion_set_pattern");
         if (filter) rtamd_detail::check(rt_occlusion_set_filter(handle, 1, RT_AO_FILTER_NORMAL_DEFAULT, RT_AO_FILTER_PLANE_DEFAULT), "rt_occlusion_set_filter");
-        int n = 0;
-        auto from = std::chrono::high_resolution_clock::now();
-        if (rt_occlusion(handle, &o, &n) != RT_OK) {
-            std::fprintf(stderr, "occlusion failed: %s\n", rt_last_error());
+        if (history && rt_occlusion_set_history(handle, 1, max_history, RT_AO_FILTER_NORMAL_DEFAULT, RT_AO_FILTER_PLANE_DEFAULT) != RT_OK) {
+            std::fprintf(stderr, "--history: %s\n", rt_last_error());
             rt_scene_free(handle);
             return 1;
         }
-        auto to = std::chrono::high_resolution_clock::now();
-        if (bench) std::printf("Time: %g ms\n", std::chrono::duration<double, std::milli>(to - from).count());
-        std::printf("Occlusion: %d samples\n", n);
+        int n = 0;
+        for (int call = 0; call < (history ? frames : 1); call++) {   // with history: a pan, every call after the first a move
+            const float step[3] = {pan, 0.0f, 0.0f};
+            if (call > 0) rtamd_detail::check(rt_camera_translate(handle, step), "rt_camera_translate");
+            auto from = std::chrono::high_resolution_clock::now();
+            if (rt_occlusion(handle, &o, &n) != RT_OK) {
+                std::fprintf(stderr, "occlusion failed: %s\n", rt_last_error());
+                rt_scene_free(handle);
+                return 1;
+            }
+            auto to = std::chrono::high_resolution_clock::now();
+            if (bench) std::printf("Time: %g ms\n", std::chrono::duration<double, std::milli>(to - from).count());
+            std::printf("Occlusion: %d samples\n", n);
+            if (history) {
+                int32_t h[8];
+                rtamd_detail::check(rt_occlusion_history_info(handle, h, nullptr), "rt_occlusion_history_info");
+                std::printf("History: moves %d cursor %d\n", h[2], h[3]);
+            }
+        }
         if (!out.empty() && !write_ppm(out.c_str(), frame.data(), info[0], info[1])) {
             std::fprintf(stderr, "cannot write %s\n", out.c_str());
             rt_scene_free(handle);

@@ -208,11 +208,25 @@ struct OcclParams {
     float any_margin, zcut_scene;               // as QueryParams'
     const rtm::V3* table;     // [AO_MAX_SAMPLES] directions (rto::ao_direction)
     float4* surf;             // [2 W H] (p, 1 where the primary hits else 0), (faced n, 0); zeros at a miss
-    int* count;               // [W H] occluded samples so far (not read when k0 = 0)
+    int* count;               // [W H] occluded samples so far (not read when k0 = 0, unless `accumulate`)
     float* visibility; int* occluded; uint32_t* rgba;   // each may be null
     float* rays;              // occl_rays_kernel: [6 W H]
     int pattern;              // OCCL_PATTERN_* (rt_plan.h): which table entry a pixel's sample k uses
     float normal_min, plane_tol;                // occl_filter_kernel's accept test (rto::filter_accept)
+    int accumulate;           // 1: the counts are read and added to even when k0 = 0 (a seeded or wrapped accumulation)
+    const int* weight;        // [W H] history weights n_h (occl_resolve_kernel, occl_filter_kernel<true>); else unused
+};
+// occl_reproject_kernel's arguments (rt_occlusion_set_history; rto::reproject, rto::history_seed):
+// the seed of every pixel of the new frame (surf -> count, weight) from the previous frame's
+// record, counts and weights, seen through the previous camera.  Device pointers.
+struct OcclReprojParams {
+    rt::DCamera prev_cam;
+    int W, H;
+    int n_prev, max_history;  // the samples the previous frame took since its own move; the cap
+    float normal_min, plane_tol;                // the history's accept test (rto::filter_accept)
+    const float4* surf;       // [2 W H] the new frame's surface record
+    const float4* prev_surf; const int* prev_count; const int* prev_weight;
+    int* count; int* weight;  // [W H] each, written for every pixel
 };
 
 }  // namespace rtd
@@ -283,6 +297,13 @@ hipError_t launch_occl_rays(OcclParams& P, hipStream_t st);
 // resolve of P.n_total samples into P.visibility / P.rgba (each may be null), after the call's last
 // launch_occlusion, which then resolves `occluded` only.
 hipError_t launch_occl_filter(const OcclPlan& plan, OcclParams& P, hipStream_t st, hipEvent_t e0, hipEvent_t e1);
+// History across camera moves.  launch_occl_reproject: every pixel's seed from the
+// previous frame; launch_occl_resolve: the unfiltered outputs of P.n_total samples since the move
+// over the per-pixel totals P.weight + P.n_total; launch_occl_filter_history: launch_occl_filter
+// with those totals as the denominators.  The counting launches then run with resolve = 0.
+hipError_t launch_occl_reproject(OcclReprojParams& R, hipStream_t st, hipEvent_t e0, hipEvent_t e1);
+hipError_t launch_occl_resolve(OcclParams& P, hipStream_t st, hipEvent_t e0, hipEvent_t e1);
+hipError_t launch_occl_filter_history(const OcclPlan& plan, OcclParams& P, hipStream_t st, hipEvent_t e0, hipEvent_t e1);
 void launch_unpermute(const uint32_t* g, uint32_t* out, int W, int H, int N, int rows_max, hipStream_t st);
 void launch_profile_marker(int tag, hipStream_t st);
 void launch_copy_gate(const unsigned* flag, unsigned long long max_ticks, hipStream_t st);

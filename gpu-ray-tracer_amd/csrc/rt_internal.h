@@ -233,11 +233,41 @@ struct rt_scene {
         bool time_filter = false;
         hipEvent_t ev0 = nullptr, ev1 = nullptr;
         float filter_ms = -1.0f;
+        // rt_occlusion_set_history: the settings; the camera of the accumulation held;
+        // the sample cursor (samples traced since the last drop, across moves), the moves so far and
+        // whether a move since the last drop has seeded the weights.  d_weight: the history weights
+        // n_h of the accumulation held (zeros before a move); d_prev_*: the frame a move left, the
+        // pointers swapped with the current ones at a move.  Allocated on first use with history on
+        // (hist_px: the pixels they hold).
+        int hist_on = 0, max_history = RT_AO_HISTORY_DEFAULT, moves = 0;
+        long long cursor = 0;
+        bool weighted = false;
+        float hist_normal_min = RT_AO_FILTER_NORMAL_DEFAULT, hist_plane_tol = RT_AO_FILTER_PLANE_DEFAULT;
+        rt::DCamera acc_cam{};
+        int32_t* d_weight = nullptr;
+        float4* d_prev_surf = nullptr;
+        int32_t *d_prev_count = nullptr, *d_prev_weight = nullptr;
+        size_t hist_px = 0;
+        // rt_occlusion_history_timing (measurements): events on the reproject and resolve dispatches
+        bool time_history = false;
+        hipEvent_t hev[4] = {nullptr, nullptr, nullptr, nullptr};
+        float reproject_ms = -1.0f, resolve_ms = -1.0f;
+        void drop_history() { cursor = 0; weighted = false; }
+        void release_history() {
+            rti::dfree(d_weight); rti::dfree(d_prev_surf); rti::dfree(d_prev_count); rti::dfree(d_prev_weight);
+            hist_px = 0;
+        }
         void release() {
             rti::dfree(d_table); rti::dfree(d_surf); rti::dfree(d_count); px = 0; n = 0;
+            release_history();
+            drop_history();
             if (ev0) (void)hipEventDestroy(ev0);
             if (ev1) (void)hipEventDestroy(ev1);
             ev0 = ev1 = nullptr;
+            for (hipEvent_t& e : hev) {
+                if (e) (void)hipEventDestroy(e);
+                e = nullptr;
+            }
         }
     } occl;
     static constexpr int MAX_SLOTS = RT_MAX_SLOTS;

@@ -2464,7 +2464,7 @@ __device__ __forceinline__ void occlusion_samples(const SceneView& S) {
     }
     if (!in) return;
     KOP& P = oparams();
-    if (k0 > 0) cnt += P.count[i];
+    if (k0 > 0 || P.accumulate) cnt += P.count[i];             // (accumulate: seeded counts, or k0 = 0 after the table's wrap)
     P.count[i] = cnt;
     if (P.resolve) {
         const float vis = rto::visibility(cnt, P.n_total);
@@ -2523,23 +2523,32 @@ __global__ __launch_bounds__(OCCL_BLOCK) void occl_rays_il_kernel(OcclParams P) 
 // entries, so a tap read is two runs of consecutive dwords (no two lanes of a row on one bank).
 // A staged count < 0 means "not live": a pixel outside the canvas or without a primary hit; no tap
 // reads outside the canvas.  Reads surf and count, writes visibility and rgba only.
+// HIST (history across camera moves): the history weights n_h are staged as
+// well, and the denominator is the integer sum of the accepted taps' n_h + n_total in place of
+// m n_total.  A form of its own, so that the plain one compiles to what it was.
+template <bool HIST>
 __global__ __launch_bounds__(OCCL_FILTER_TX * OCCL_FILTER_TY) void occl_filter_kernel(OcclParams P) {
     constexpr int LO = rto::AO_FILTER_LO, HI = rto::AO_FILTER_HI;
     constexpr int SW = OCCL_FILTER_TX + LO + HI, SH = OCCL_FILTER_TY + LO + HI, SN = SW * SH;
     __shared__ float spx[SN], spy[SN], spz[SN], snx[SN], sny[SN], snz[SN];
     __shared__ int scnt[SN];
+    __shared__ int swgt[HIST ? SN : 1];
     const int W = P.W, H = P.H;
     const int x0 = (int)blockIdx.x * OCCL_FILTER_TX - LO, y0 = (int)blockIdx.y * OCCL_FILTER_TY - LO;
     for (int e = (int)threadIdx.x; e < SN; e += OCCL_FILTER_TX * OCCL_FILTER_TY) {
         const int sy = e / SW, sx = e - sy * SW, x = x0 + sx, y = y0 + sy;
         float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), c = a;
-        int cnt = -1;
+        int cnt = -1, wgt = 0;
         if (x >= 0 && x < W && y >= 0 && y < H) {
             const long long i = (long long)y * W + x;
             a = P.surf[2 * i];
-            if (a.w != 0.0f) { c = P.surf[2 * i + 1]; cnt = P.count[i]; }
+            if (a.w != 0.0f) {
+                c = P.surf[2 * i + 1]; cnt = P.count[i];
+                if (HIST) wgt = P.weight[i];
+            }
         }
         spx[e] = a.x; spy[e] = a.y; spz[e] = a.z; snx[e] = c.x; sny[e] = c.y; snz[e] = c.z; scnt[e] = cnt;
+        if (HIST) swgt[e] = wgt;
     }
     __syncthreads();
     const int tx = (int)threadIdx.x % OCCL_FILTER_TX, ty = (int)threadIdx.x / OCCL_FILTER_TX;
@@ -2550,6 +2559,7 @@ __global__ __launch_bounds__(OCCL_FILTER_TX * OCCL_FILTER_TY) void occl_filter_k
     if (scnt[ce] >= 0) {
         const V3 pc = v3(spx[ce], spy[ce], spz[ce]), nc = v3(snx[ce], sny[ce], snz[ce]);
         int sum = scnt[ce], m = 1;                             // the centre tap, unconditionally
+        int wsum = HIST ? swgt[ce] : 0;
 #pragma unroll
         for (int dy = -LO; dy <= HI; dy++) {
 #pragma unroll
@@ -2558,13 +2568,54 @@ __global__ __launch_bounds__(OCCL_FILTER_TX * OCCL_FILTER_TY) void occl_filter_k
                 const int q = ce + dy * SW + dx, cq = scnt[q];
                 if (rto::filter_accept(pc, nc, v3(spx[q], spy[q], spz[q]), v3(snx[q], sny[q], snz[q]), cq >= 0, P.normal_min, P.plane_tol)) {
                     sum += cq; m++;
+                    if (HIST) wsum += swgt[q];
                 }
             }
         }
-        vis = rto::filtered_visibility(sum, m, P.n_total);
+        vis = HIST ? rto::filtered_visibility_total(sum, wsum + m * P.n_total) : rto::filtered_visibility(sum, m, P.n_total);
     }
     const long long i = (long long)y * W + x;
     if (P.visibility) P.visibility[i] = vis;
+    if (P.rgba) P.rgba[i] = rto::grey(vis);
+}
+
+// History across camera moves (rt_occlusion_set_history; rt_occl.h).  The seed:
+// one lane a pixel of the NEW frame under the 8 x 8 tile map, so that a wave's sources fall into
+// one small neighbourhood of the previous frame.  A lane reads its record (32 B), reprojects its
+// point through the previous camera, gathers the source's record (32 B), count and weight and
+// writes its seeded count and weight -- zeros without a primary hit or an accepted source.  The
+// source index is inside the canvas by rto::reproject's float comparisons (and clamped once more
+// in integers before it addresses memory).  No LDS, no atomics.
+__global__ __launch_bounds__(OCCL_BLOCK) void occl_reproject_kernel(OcclReprojParams R) {
+    const int W = R.W, H = R.H;
+    const int g = occl_wave();
+    if (g >= ((W + 7) >> 3) * ((H + 7) >> 3)) return;          // (wave-uniform)
+    const long long i = occl_pixel(OCCL_MAP_TILE, W, H, g, (int)(threadIdx.x & 63));
+    if (i < 0) return;
+    int c_h = 0, n_h = 0;
+    const float4 a = R.surf[2 * i];
+    if (a.w != 0.0f) {
+        const float4 c = R.surf[2 * i + 1];
+        const V3 p = v3(a.x, a.y, a.z), n = v3(c.x, c.y, c.z);
+        int qx = 0, qy = 0;
+        if (rto::reproject(p, R.prev_cam, qx, qy) && qx < W && qy < H) {
+            const long long q = (long long)qy * W + qx;
+            const float4 aq = R.prev_surf[2 * q], cq = R.prev_surf[2 * q + 1];
+            if (rto::filter_accept(p, n, v3(aq.x, aq.y, aq.z), v3(cq.x, cq.y, cq.z), aq.w != 0.0f, R.normal_min, R.plane_tol))
+                rto::history_seed(R.prev_count[q], R.prev_weight[q] + R.n_prev, R.max_history, c_h, n_h);
+        }
+    }
+    R.count[i] = c_h; R.weight[i] = n_h;
+}
+// The unfiltered outputs with per-pixel totals: n_total samples since the move over weight + n_total.
+// A pixel without a primary hit holds count 0: visibility 1.
+__global__ __launch_bounds__(OCCL_BLOCK) void occl_resolve_kernel(OcclParams P) {
+    const long long i = (long long)blockIdx.x * OCCL_BLOCK + threadIdx.x;
+    if (i >= (long long)P.W * P.H) return;
+    const int cnt = P.count[i];
+    const float vis = rto::visibility(cnt, P.weight[i] + P.n_total);
+    if (P.visibility) P.visibility[i] = vis;
+    if (P.occluded) P.occluded[i] = cnt;
     if (P.rgba) P.rgba[i] = rto::grey(vis);
 }
 
@@ -3163,7 +3214,30 @@ hipError_t launch_occlusion(const OcclPlan& plan, OcclParams& P, SceneView& S, h
 hipError_t launch_occl_filter(const OcclPlan& plan, OcclParams& P, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
     if ((long long)P.W * P.H <= 0) return hipSuccess;
     void* args[] = {&P};
-    return hipExtLaunchKernel((const void*)occl_filter_kernel, dim3(plan.filter_bx, plan.filter_by), dim3(OCCL_FILTER_TX * OCCL_FILTER_TY),
+    return hipExtLaunchKernel((const void*)occl_filter_kernel<false>, dim3(plan.filter_bx, plan.filter_by), dim3(OCCL_FILTER_TX * OCCL_FILTER_TY),
+                              args, 0, st, e0, e1, 0);
+}
+
+hipError_t launch_occl_filter_history(const OcclPlan& plan, OcclParams& P, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
+    if ((long long)P.W * P.H <= 0) return hipSuccess;
+    void* args[] = {&P};
+    return hipExtLaunchKernel((const void*)occl_filter_kernel<true>, dim3(plan.filter_bx, plan.filter_by), dim3(OCCL_FILTER_TX * OCCL_FILTER_TY),
+                              args, 0, st, e0, e1, 0);
+}
+
+hipError_t launch_occl_reproject(OcclReprojParams& R, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
+    if ((long long)R.W * R.H <= 0) return hipSuccess;
+    const long long waves = (long long)((R.W + 7) / 8) * ((R.H + 7) / 8);
+    void* args[] = {&R};
+    return hipExtLaunchKernel((const void*)occl_reproject_kernel, dim3((unsigned)((waves + OCCL_BLOCK / 64 - 1) / (OCCL_BLOCK / 64))),
+                              dim3(OCCL_BLOCK), args, 0, st, e0, e1, 0);
+}
+
+hipError_t launch_occl_resolve(OcclParams& P, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
+    const long long px = (long long)P.W * P.H;
+    if (px <= 0) return hipSuccess;
+    void* args[] = {&P};
+    return hipExtLaunchKernel((const void*)occl_resolve_kernel, dim3((unsigned)((px + OCCL_BLOCK - 1) / OCCL_BLOCK)), dim3(OCCL_BLOCK),
                               args, 0, st, e0, e1, 0);
 }
 

@@ -78,6 +78,38 @@ RT_HD bool filter_accept(V3 pc, V3 nc, V3 pq, V3 nq, bool live_q, float normal_m
 }
 RT_HD float filtered_visibility(int S, int m, int n) { return 1.0f - (float)S / (float)(m * n); }
 
+// History across camera moves (rt_occlusion_set_history): a new pixel with the live record (p, n)
+// looks its surface point up in the frame of the previous camera C (DCamera's fields), the
+// inverse of camera_at:
+//   v  = p - C.pos per component;   a = dot(v, C.f), sx = dot(v, C.r), sy = dot(v, C.u)
+//   gx = (C.near_ x sx) / a,  gy = (C.near_ x sy) / a             (no history unless a > 0)
+//   cx = gx x C.unit + 0.5f x C.W,  cy = 0.5f x C.H - gy x C.unit
+//   fx = floorf(cx + 0.5f), fy = floorf(cy + 0.5f)                (sample 0's ray of pixel x passes through cx = x)
+// and the source pixel is ((int)fx, (int)fy) when 0 <= fx < C.W and 0 <= fy < C.H, compared in
+// float before any conversion: a NaN rejects.  The caller accepts the source with filter_accept
+// (the new pixel is the centre).
+template <class CAM>
+RT_HD bool reproject(V3 p, const CAM& C, int& qx, int& qy) {
+    const V3 v = p - C.pos;
+    const float a = rtm::dot(v, C.f), sx = rtm::dot(v, C.r), sy = rtm::dot(v, C.u);
+    if (!(a > 0.0f)) return false;
+    const float gx = (C.near_ * sx) / a, gy = (C.near_ * sy) / a;
+    const float cx = gx * C.unit + 0.5f * C.W, cy = 0.5f * C.H - gy * C.unit;
+    const float fx = floorf(cx + 0.5f), fy = floorf(cy + 0.5f);
+    if (!(fx >= 0.0f && fx < C.W && fy >= 0.0f && fy < C.H)) return false;
+    qx = (int)fx; qy = (int)fy;
+    return true;
+}
+// The seed a pixel takes from its accepted source: c of the source's T = n_h + n samples were
+// occluded.  Up to max_history samples are carried as they are; more are scaled down to
+// max_history, the count rounded to nearest (int32, truncating divisions; c x max_history < 2^22).
+RT_HD void history_seed(int c, int T, int max_history, int& c_h, int& n_h) {
+    if (T <= max_history) { c_h = c; n_h = T; }
+    else { n_h = max_history; c_h = (c * max_history + T / 2) / T; }
+}
+// The filtered resolve with per-pixel totals: S as above, N the integer sum of the accepted taps' n_h + n.
+RT_HD float filtered_visibility_total(int S, int N) { return 1.0f - (float)S / (float)N; }
+
 // Host only.  Entry k of the direction table: point k of the R2 sequence (rt::spp_offset's constants, in
 // double; k = 0 -> the pole) taken to the unit disk by (u, v) -> sqrt(u) (cos 2 pi v, sin 2 pi v)
 // and lifted to the hemisphere, z = sqrt(max(0, 1 - x^2 - y^2)): cosine-weighted.  Double

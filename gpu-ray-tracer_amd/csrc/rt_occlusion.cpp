@@ -1,5 +1,6 @@
 // rt_occlusion.cpp — the ambient occlusion pass (rt_occlusion): the scene-owned direction table,
-// surface record and counts, the reset / info entries and the rays' test hook.  Host code only
+// surface record and counts, the reset / info entries and the rays' test hook; the history across
+// camera moves (rt_occlusion_set_history): the previous frame's buffers, the move.  Host code only
 // (rt_internal.h); its kernels are the occlusion kernels, reached through rt_device.h.
 #include <cmath>
 #include <cstring>
@@ -22,6 +23,14 @@ bool occl_stale(const rt_scene* s, float radius, float bias) {
 void occl_drop(rt_scene* s) {
     if (s->occl.n > 0) s->occl.restarts++;
     s->occl.n = 0;
+    s->occl.drop_history();
+}
+// With history on: does this call find samples held whose camera alone changed?  It moves them
+// (reprojection) where occl_stale alone would drop them.
+bool occl_moves(const rt_scene* s, const rt_occlusion_opts* o) {
+    const rt_scene::Occl& a = s->occl;
+    return a.hist_on && !o->restart && a.n > 0 && a.cam_gen != s->cam_gen && a.inst_gen == s->inst_gen && a.radius == o->radius &&
+           a.bias == o->bias && a.acc_cam.W == s->h.d_cam.W && a.acc_cam.H == s->h.d_cam.H;
 }
 // The scene-owned buffers for the canvas and the direction table; a failed allocation leaves none
 // of them (and no samples).
@@ -47,6 +56,23 @@ int ensure_occl(rt_scene* s) {
     a.px = px;
     return RT_OK;
 }
+// The history's buffers beside them: the weights of the accumulation held and the previous frame's
+// record, counts and weights.  A failed allocation leaves none of the set.
+int ensure_occl_history(rt_scene* s) {
+    rt_scene::Occl& a = s->occl;
+    if (a.hist_px >= a.px) return RT_OK;
+    a.release_history();
+    if (hipMalloc((void**)&a.d_weight, a.px * sizeof(int32_t)) != hipSuccess ||
+        hipMalloc((void**)&a.d_prev_surf, 2 * a.px * sizeof(float4)) != hipSuccess ||
+        hipMalloc((void**)&a.d_prev_count, a.px * sizeof(int32_t)) != hipSuccess ||
+        hipMalloc((void**)&a.d_prev_weight, a.px * sizeof(int32_t)) != hipSuccess) {
+        const std::string why = hipGetErrorString(hipGetLastError());
+        a.release_history();
+        return fail(RT_ERR_HIP, "rt_occlusion: no memory for the history of " + std::to_string(a.px) + " pixels: " + why);
+    }
+    a.hist_px = a.px;
+    return RT_OK;
+}
 // The kernels' arguments and scene view for the current slot: the occlusion rays start on the
 // surfaces, not at the camera, so the view is the one for a caller's rays (caller_ray_view).
 void occl_launch_setup(rt_scene* s, bool use_bvh, OcclParams& P, SceneView& S, OcclPlan& plan) {
@@ -59,6 +85,7 @@ void occl_launch_setup(rt_scene* s, bool use_bvh, OcclParams& P, SceneView& S, O
     P.zcut_scene = v.zcut_scene; P.any_margin = v.any_margin;
     P.table = a.d_table; P.surf = a.d_surf; P.count = a.d_count;
     P.pattern = a.pattern; P.normal_min = a.normal_min; P.plane_tol = a.plane_tol;
+    P.weight = a.d_weight;
     int map = -1;                                              // RT_OCCL_MAP (measurements): row / tile / class (interleaved only)
     if (const char* e = getenv("RT_OCCL_MAP"))
         map = !strcmp(e, "row") ? OCCL_MAP_ROW : !strcmp(e, "tile") ? OCCL_MAP_TILE : !strcmp(e, "class") ? OCCL_MAP_CLASS : -1;
@@ -95,8 +122,9 @@ int rt_occlusion(rt_scene* s, const rt_occlusion_opts* o, int* n_samples) {
     if (!(o->radius > 0.0f)) return fail(RT_ERR_ARG, "rt_occlusion: radius > 0 required (+inf: sky visibility)");
     if (!(o->bias >= 0.0f && std::isfinite(o->bias))) return fail(RT_ERR_ARG, "rt_occlusion: bias must be finite and >= 0");
     if (!(o->visibility || o->occluded || o->rgba)) return fail(RT_ERR_ARG, "rt_occlusion: no output requested");
-    const bool fresh = o->restart || occl_stale(s, o->radius, o->bias);
-    if ((long long)(fresh ? 0 : s->occl.n) + o->samples > pattern_capacity(s->occl.pattern))
+    const bool move = occl_moves(s, o);                       // history on: only the camera changed
+    const bool fresh = !move && (o->restart || occl_stale(s, o->radius, o->bias));
+    if ((long long)(fresh || move ? 0 : s->occl.n) + o->samples > pattern_capacity(s->occl.pattern))
         return fail(RT_ERR_LIMIT, s->occl.pattern == RT_AO_PATTERN_INTERLEAVED
                                       ? "rt_occlusion: more than 64 samples held in the interleaved pattern (rt_occlusion_reset starts again)"
                                       : "rt_occlusion: more than 1024 samples held (rt_occlusion_reset starts again)");
@@ -108,15 +136,25 @@ int rt_occlusion(rt_scene* s, const rt_occlusion_opts* o, int* n_samples) {
     if (px > (size_t)INT32_MAX / 8) return fail(RT_ERR_LIMIT, "rt_occlusion: frame larger than 2^28 pixels");
     if (fresh) occl_drop(s);
     if ((r = ensure_occl(s)) != RT_OK) return r;
+    if (s->occl.hist_on && (r = ensure_occl_history(s)) != RT_OK) return r;
     if (o->host_outputs && (r = ensure_out_staging(s)) != RT_OK) return r;
     rt_scene::Occl& a = s->occl;
     // frames in flight (any slot) first; the BVH at most once, for every sample of the call
     if ((r = begin_side_entry(s, 1, s->builds_bvh(o->use_bvh, o->rebuild_bvh))) != RT_OK) return r;
     hipStream_t st = sstream(s);
-    const int before = a.n;
-    if (before == 0) {                                        // what this accumulation's samples see
-        a.inst_gen = s->inst_gen; a.cam_gen = s->cam_gen; a.radius = o->radius; a.bias = o->bias;
+    const int cap = pattern_capacity(a.pattern);
+    const int before = move ? 0 : a.n;                        // samples held since the last move or drop
+    const long long cursor = a.hist_on ? a.cursor : before;   // this call's first sample is number `cursor`
+    const int n_prev = a.n;                                   // a move: the samples of the frame being left
+    const rt::DCamera prev_cam = a.acc_cam;
+    if (before == 0 && !move) {                               // what this accumulation's samples see
+        a.inst_gen = s->inst_gen; a.radius = o->radius; a.bias = o->bias;
     }
+    if (before == 0) { a.cam_gen = s->cam_gen; a.acc_cam = s->h.d_cam; }
+    if (move) {                                               // the accumulation being left becomes the previous frame
+        std::swap(a.d_surf, a.d_prev_surf); std::swap(a.d_count, a.d_prev_count); std::swap(a.d_weight, a.d_prev_weight);
+    }
+    const bool weighted = a.hist_on && (a.weighted || move);  // per-pixel totals: a move since the last drop
     OcclParams P;
     SceneView S;
     OcclPlan plan;
@@ -125,34 +163,74 @@ int rt_occlusion(rt_scene* s, const rt_occlusion_opts* o, int* n_samples) {
     P.visibility = !o->visibility ? nullptr : host ? (float*)s->d_out[1] : o->visibility;
     P.occluded = !o->occluded ? nullptr : host ? (int*)s->d_out[2] : o->occluded;
     P.rgba = !o->rgba ? nullptr : host ? (uint32_t*)s->d_out[0] : o->rgba;
-    // the filtered resolve: the last launch resolves `occluded` only, occl_filter_kernel the other two
+    // the filtered resolve: the last launch resolves `occluded` only, occl_filter_kernel the other two;
+    // with per-pixel totals no counting launch resolves: occl_resolve_kernel / occl_filter_kernel<true> do
     OcclParams F = P;
     const bool filter = a.filter != 0 && (P.visibility || P.rgba);
-    if (filter) { P.visibility = nullptr; P.rgba = nullptr; }
+    if (filter || weighted) { P.visibility = nullptr; P.rgba = nullptr; }
     a.last_map = plan.map;
     a.n = 0;                                                  // a failed launch leaves no samples, not stale counts
-    bool timed = false;
+    a.drop_history();
+    const bool held = a.hist_on && n_prev > 0;                // ... and, with history, counts as a restart (taken back below)
+    if (held) a.restarts++;
+    bool timed = false, timed_h = false, timed_r = false;
     if (px > 0) {
+        if (a.time_history && !a.hev[0])
+            for (hipEvent_t& e : a.hev) HIPCHK(hipEventCreate(&e));
         if (before == 0) HIPCHK(launch_surface_record(plan, P, S, st));
-        for (int done = 0; done < o->samples; done += OCCL_LAUNCH_SAMPLES) {
-            P.k0 = before + done;
-            P.samples = std::min(OCCL_LAUNCH_SAMPLES, o->samples - done);
-            P.resolve = done + P.samples == o->samples ? 1 : 0;
+        if (move) {                                           // every pixel's seed from the frame just left
+            OcclReprojParams R{};
+            R.prev_cam = prev_cam; R.W = P.W; R.H = P.H; R.n_prev = n_prev; R.max_history = a.max_history;
+            R.normal_min = a.hist_normal_min; R.plane_tol = a.hist_plane_tol;
+            R.surf = a.d_surf; R.prev_surf = a.d_prev_surf; R.prev_count = a.d_prev_count; R.prev_weight = a.d_prev_weight;
+            R.count = a.d_count; R.weight = a.d_weight;
+            timed_r = a.time_history;
+            HIPCHK(launch_occl_reproject(R, st, timed_r ? a.hev[0] : nullptr, timed_r ? a.hev[1] : nullptr));
+        } else if (a.hist_on && before == 0) {
+            HIPCHK(hipMemsetAsync(a.d_weight, 0, px * sizeof(int32_t), st));   // no move yet: every n_h is 0
+        }
+        // sample number K uses the pattern's index K mod capacity: launches of at most
+        // OCCL_LAUNCH_SAMPLES, none across the table's wrap (at most one: the limit above)
+        for (int done = 0; done < o->samples;) {
+            P.k0 = (int)((cursor + done) % cap);
+            P.samples = std::min(std::min(OCCL_LAUNCH_SAMPLES, o->samples - done), cap - P.k0);
+            done += P.samples;
+            P.accumulate = (move || before + done - P.samples > 0) ? 1 : 0;
+            P.resolve = (done == o->samples && !weighted) ? 1 : 0;
             P.n_total = before + o->samples;
             HIPCHK(launch_occlusion(plan, P, S, st, nullptr, nullptr));
         }
-        if (filter) {
-            F.n_total = before + o->samples;
-            timed = a.time_filter;
+        F.n_total = before + o->samples;
+        if (weighted && (F.occluded || !filter)) {
+            OcclParams E = F;
+            if (filter) { E.visibility = nullptr; E.rgba = nullptr; }
+            timed_h = a.time_history && !filter;
+            HIPCHK(launch_occl_resolve(E, st, timed_h ? a.hev[2] : nullptr, timed_h ? a.hev[3] : nullptr));
+        }
+        if (filter) {                                         // (a dispatch takes one pair of events: the history's first)
+            timed_h = weighted && a.time_history;
+            timed = a.time_filter && !timed_h;
             if (timed && !a.ev0) { HIPCHK(hipEventCreate(&a.ev0)); HIPCHK(hipEventCreate(&a.ev1)); }
-            HIPCHK(launch_occl_filter(plan, F, st, timed ? a.ev0 : nullptr, timed ? a.ev1 : nullptr));
+            hipEvent_t e0 = timed_h ? a.hev[2] : timed ? a.ev0 : nullptr, e1 = timed_h ? a.hev[3] : timed ? a.ev1 : nullptr;
+            HIPCHK(weighted ? launch_occl_filter_history(plan, F, st, e0, e1) : launch_occl_filter(plan, F, st, e0, e1));
         }
         HIPCHK(hipGetLastError());
     }
     if ((r = end_frame(s, st)) != RT_OK) return r;
     HIPCHK(hipStreamSynchronize(st));
     a.n = before + o->samples;
+    if (held) a.restarts--;
+    if (a.hist_on) {
+        a.cursor = cursor + o->samples;
+        a.weighted = weighted;
+        if (move) a.moves++;
+    }
     if (timed) HIPCHK(hipEventElapsedTime(&a.filter_ms, a.ev0, a.ev1));
+    if (timed_r) HIPCHK(hipEventElapsedTime(&a.reproject_ms, a.hev[0], a.hev[1]));
+    if (timed_h) {
+        HIPCHK(hipEventElapsedTime(&a.resolve_ms, a.hev[2], a.hev[3]));
+        if (filter && a.time_filter) a.filter_ms = a.resolve_ms;
+    }
     if (host) {
         if (o->visibility) HIPCHK(hipMemcpy(o->visibility, F.visibility, px * 4, hipMemcpyDeviceToHost));
         if (o->occluded) HIPCHK(hipMemcpy(o->occluded, F.occluded, px * 4, hipMemcpyDeviceToHost));
@@ -194,6 +272,54 @@ int rt_occlusion_set_filter(rt_scene* s, int on, float normal_min, float plane_t
     if (!(plane_tol >= 0.0f && std::isfinite(plane_tol))) return fail(RT_ERR_ARG, "rt_occlusion_set_filter: plane_tol must be finite and >= 0");
     s->occl.filter = on;
     if (on) { s->occl.normal_min = normal_min; s->occl.plane_tol = plane_tol; }
+    return RT_OK;
+}
+
+// History across camera moves (rt_amd.h): part of what an accumulation was started with, the two
+// thresholds excepted (they are read at the next move).
+int rt_occlusion_set_history(rt_scene* s, int on, int max_history, float normal_min, float plane_tol) {
+    CHECK_SCENE(s);
+    if (on != 0 && on != 1) return fail(RT_ERR_ARG, "rt_occlusion_set_history: on is 0 or 1");
+    if (max_history < 1 || max_history > RT_AO_MAX_SAMPLES) return fail(RT_ERR_ARG, "rt_occlusion_set_history: 1 <= max_history <= 1024 required");
+    if (!(normal_min >= -1.0f && normal_min <= 1.0f)) return fail(RT_ERR_ARG, "rt_occlusion_set_history: normal_min in [-1, 1] required");
+    if (!(plane_tol >= 0.0f && std::isfinite(plane_tol))) return fail(RT_ERR_ARG, "rt_occlusion_set_history: plane_tol must be finite and >= 0");
+    rt_scene::Occl& a = s->occl;
+    if (on != a.hist_on || max_history != a.max_history) occl_drop(s);
+    a.hist_on = on; a.max_history = max_history;
+    a.hist_normal_min = normal_min; a.hist_plane_tol = plane_tol;
+    return RT_OK;
+}
+
+int rt_occlusion_history_info(const rt_scene* s, int32_t* out8, float* f2) {
+    CHECK_SCENE(s);
+    const rt_scene::Occl& a = s->occl;
+    if (out8) {
+        out8[0] = a.hist_on; out8[1] = a.max_history; out8[2] = a.moves;
+        out8[3] = (int32_t)std::min<long long>(a.cursor, INT32_MAX);
+        out8[4] = a.n; out8[5] = a.weighted ? 1 : 0; out8[6] = 0; out8[7] = 0;
+    }
+    if (f2) { f2[0] = a.hist_normal_min; f2[1] = a.hist_plane_tol; }
+    return RT_OK;
+}
+
+// Test hook: the history weights of the accumulation held (zeros while no move has seeded them).
+int rt_occlusion_history_weights(rt_scene* s, int32_t* dst, int64_t cap) {
+    CHECK_FINISHED(s);
+    const size_t px = (size_t)s->h.cam.W * s->h.cam.H;
+    if (!dst || cap < (int64_t)px) return fail(RT_ERR_ARG, "rt_occlusion_history_weights: a destination of W * H int32");
+    if (s->occl.n <= 0) return fail(RT_ERR_STATE, "rt_occlusion_history_weights: no accumulation (after rt_occlusion)");
+    if (!s->occl.weighted || px == 0) { memset(dst, 0, px * sizeof(int32_t)); return RT_OK; }
+    HIPCHK(hipSetDevice(s->device));                          // (rt_occlusion returned after its stream's sync)
+    HIPCHK(hipMemcpy(dst, s->occl.d_weight, px * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+// Measurement hook: the times of occl_reproject_kernel and of the kernel that resolves with
+// per-pixel totals (occl_resolve_kernel, or occl_filter_kernel<true>), by events on their dispatches.
+int rt_occlusion_history_timing(rt_scene* s, int on, float* ms2) {
+    CHECK_SCENE(s);
+    s->occl.time_history = on != 0;
+    if (ms2) { ms2[0] = s->occl.reproject_ms; ms2[1] = s->occl.resolve_ms; }
     return RT_OK;
 }
 

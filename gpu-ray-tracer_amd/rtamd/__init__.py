@@ -50,6 +50,7 @@ SYMBOLS = [
     "rt_occlusion_opts_default", "rt_occlusion", "rt_occlusion_reset", "rt_occlusion_info", "rt_ao_direction",
     "rt_occlusion_rays", "rt_occlusion_set_pattern", "rt_occlusion_set_filter", "rt_occlusion_config",
     "rt_occlusion_filter_timing",
+    "rt_occlusion_set_history", "rt_occlusion_history_info", "rt_occlusion_history_weights", "rt_occlusion_history_timing",
     "rt_scene_set_shadow_hints", "rt_scene_shadow_hints_fill", "rt_scene_shadow_hint_code",
     "rt_scene_shadow_hint_counters", "rt_scene_shadow_hints_read",
 ]
@@ -59,6 +60,7 @@ RT_AO_MAX_SAMPLES, RT_AO_BIAS_DEFAULT = 1024, 1e-3
 RT_AO_PATTERN_SHARED, RT_AO_PATTERN_INTERLEAVED = 0, 1
 RT_AO_INTERLEAVED_MAX_SAMPLES = RT_AO_MAX_SAMPLES // 16
 RT_AO_FILTER_NORMAL_DEFAULT, RT_AO_FILTER_PLANE_DEFAULT = 0.9, 1e-2
+RT_AO_HISTORY_DEFAULT = 32
 AO_PATTERNS = {"shared": RT_AO_PATTERN_SHARED, "interleaved": RT_AO_PATTERN_INTERLEAVED}
 OCCL_MAPS = {-1: None, 0: "row", 1: "tile", 2: "class"}     # rt_occlusion_config's out4[3]
 
@@ -224,6 +226,11 @@ def lib():
         L.rt_occlusion_set_filter.argtypes = [vp, ip, ctypes.c_float, ctypes.c_float]
         L.rt_occlusion_config.argtypes = [vp, vp, vp]
         L.rt_occlusion_filter_timing.argtypes = [vp, ip, ctypes.POINTER(ctypes.c_float)]
+    if hasattr(L, "rt_occlusion_set_history"):  # (absent from libraries before the history: A/B runs)
+        L.rt_occlusion_set_history.argtypes = [vp, ip, ip, ctypes.c_float, ctypes.c_float]
+        L.rt_occlusion_history_info.argtypes = [vp, vp, vp]
+        L.rt_occlusion_history_weights.argtypes = [vp, vp, ctypes.c_int64]
+        L.rt_occlusion_history_timing.argtypes = [vp, ip, vp]
     if hasattr(L, "rt_query_set_order"):        # (absent from libraries before the coherence sort: A/B runs)
         L.rt_query_set_order.argtypes = [vp, ip]
         L.rt_query_last.argtypes = [vp, vp, vp, vp, ctypes.c_int64]
@@ -717,6 +724,38 @@ class Scene:
         ms = ctypes.c_float(-1.0)
         _check(lib().rt_occlusion_filter_timing(self._h, int(on), ctypes.byref(ms)))
         return ms.value
+
+    def set_occlusion_history(self, on=True, max_history=RT_AO_HISTORY_DEFAULT, normal_min=RT_AO_FILTER_NORMAL_DEFAULT,
+                              plane_tol=RT_AO_FILTER_PLANE_DEFAULT):
+        """Keep the samples across camera moves: a call that finds only the camera changed seeds every
+        pixel from the previous frame by reprojection (at most max_history samples carried) instead
+        of starting again.  A change of `on` or `max_history` drops the samples held
+        (rt_occlusion_set_history)."""
+        _check(lib().rt_occlusion_set_history(self._h, int(on), int(max_history), float(normal_min), float(plane_tol)))
+
+    @property
+    def occlusion_history(self):
+        """{"on", "max_history", "moves", "cursor": samples traced since the last drop, "n": samples
+        since the last move or drop, "weighted": a move since the last drop, "normal_min", "plane_tol"}
+        (rt_occlusion_history_info)."""
+        a, f = np.zeros(8, np.int32), np.zeros(2, np.float32)
+        _check(lib().rt_occlusion_history_info(self._h, _ptr(a), _ptr(f)))
+        return {"on": bool(a[0]), "max_history": int(a[1]), "moves": int(a[2]), "cursor": int(a[3]), "n": int(a[4]),
+                "weighted": bool(a[5]), "normal_min": float(f[0]), "plane_tol": float(f[1])}
+
+    def _occlusion_history_weights(self):
+        """Test hook: the per-pixel history weight n_h, (H, W) int32 (rt_occlusion_history_weights)."""
+        a = np.zeros((self.height, self.width), np.int32)
+        _check(lib().rt_occlusion_history_weights(self._h, _ptr(a), a.size))
+        return a
+
+    def history_timing(self, on=True):
+        """Measurement hook: time the reproject and the per-pixel resolve dispatches of later calls
+        by events; returns their last (reproject ms, resolve ms), < 0: none yet
+        (rt_occlusion_history_timing)."""
+        ms = np.full(2, -1.0, np.float32)
+        _check(lib().rt_occlusion_history_timing(self._h, int(on), _ptr(ms)))
+        return float(ms[0]), float(ms[1])
 
     def _occlusion_rays(self, k):
         """Test hook: the rays sample k traces for the current accumulation, (H, W, 6) float32:

@@ -39,7 +39,9 @@ extern "C" {
  *    (still 5: additive -- rt_occlusion and its companions, rt_ao_direction; no existing entry or
  *    struct changed)
  *    (still 5: additive -- rt_occlusion_set_pattern / rt_occlusion_set_filter / rt_occlusion_config
- *    and the measurement hook rt_occlusion_filter_timing; rt_occlusion_opts keeps its layout, both switches are scene state) */
+ *    and the measurement hook rt_occlusion_filter_timing; rt_occlusion_opts keeps its layout, both switches are scene state)
+ *    (still 5: additive -- rt_occlusion_set_history / rt_occlusion_history_info, the test hook
+ *    rt_occlusion_history_weights and the measurement hook rt_occlusion_history_timing; scene state) */
 #define RT_ABI_VERSION 5
 
 enum {
@@ -465,6 +467,71 @@ int rt_occlusion_config(const rt_scene* s, int32_t out4[4], float f2[2]);
 /* Measurement hook: with `on`, later filtered calls take start/stop events on occl_filter_kernel's
  * dispatch; *ms (may be NULL): the last timed dispatch's milliseconds, < 0: none yet.  Host state. */
 int rt_occlusion_filter_timing(rt_scene* s, int on, float* ms);
+
+/* ---- ambient occlusion: samples kept across camera moves by reprojection (still ABI 5: additive) ----
+ * Ambient occlusion belongs to the surface point, not to the view: what a point collected under
+ * the previous camera is still valid under the next.  Opt-in scene state, host state only (no
+ * device needed), off by default; with it off rt_occlusion writes every byte as described above,
+ * and with it on and no move yet every output byte equals what history off writes.
+ *
+ * rt_occlusion_set_history.  RT_ERR_ARG: on outside {0, 1}; max_history outside [1,
+ * RT_AO_MAX_SAMPLES]; normal_min NaN or outside [-1, 1]; plane_tol negative, NaN or infinite
+ * (validated with on = 0 too).  A call that changes `on` or `max_history` while samples are held
+ * drops them (one restart, as rt_occlusion_set_pattern); a change of the two thresholds alone
+ * drops nothing and applies at the next move; a call that changes nothing does nothing.  A split
+ * scene may set it.
+ *
+ * Move.  With history on, an rt_occlusion call without `restart` that finds samples held and only
+ * the camera changed since they were started (instance poses, radius, bias and pattern as they
+ * were) does not drop them, it moves them: the buffers of the accumulation being left (surface
+ * record, counts, history weights, camera) become the previous frame, a new surface record is
+ * built for the current camera, every pixel is seeded from the previous frame (below) and the
+ * call's samples are added.  A move is no restart: it is counted in `moves`, and
+ * rt_occlusion_info[0] and *n_samples become the samples traced since the move.  Every camera
+ * entry counts as a change, so rt_camera_set to the same pose is a move.  Everything else --
+ * restart = 1, rt_occlusion_reset, an instance, radius, bias or pattern change, a failed launch --
+ * drops history, weights and cursor together, as a restart.
+ *
+ * Sample cursor.  K counts the samples traced since the last drop, across moves.  Sample number K
+ * uses the pattern's sample index k = K mod capacity(pattern) (entry k shared, entry 16 k + c
+ * interleaved): a moved pixel takes new directions, and k stays the same for every pixel.
+ * RT_ERR_LIMIT, checked with the arguments: the samples since the last move or drop plus the
+ * call's may not exceed the capacity, so a call wraps the table at most once.
+ * rt_occlusion_rays(s, k, ...) keeps its meaning: k is a sample index of the pattern.
+ *
+ * Reprojection (float32, one rounding per operation, no contraction, dot as above; fixed in
+ * csrc/rt_occl.h).  For a new pixel with a live record (p, n) and the previous camera C' = (pos,
+ * r, u, f, near, unit, W, H):
+ *   v = p - pos per component;  a = dot(v, f), sx = dot(v, r), sy = dot(v, u);  no history unless a > 0;
+ *   gx = (near x sx) / a, gy = (near x sy) / a;
+ *   cx = gx x unit + 0.5f x W, cy = 0.5f x H - gy x unit        (the inverse of camera_at);
+ *   fx = floorf(cx + 0.5f), fy = floorf(cy + 0.5f);
+ *   no history unless fx >= 0, fx < W, fy >= 0 and fy < H, compared in float (a NaN rejects);
+ *   the source is pixel q = ((int)fx, (int)fy) of the previous frame, accepted when q is live,
+ *   dot(n, n_q) >= normal_min and fabsf(dot(n, p_q - p)) <= plane_tol: the filter's accept test
+ *   with the history's thresholds and the new pixel as the centre.
+ * Seed.  With c = the source's count and T = its history weight + the samples of the previous
+ * frame: T <= max_history gives (c_h, n_h) = (c, T); otherwise n_h = max_history and c_h =
+ * (c x max_history + T / 2) / T in int32 with truncating divisions.  A pixel without an accepted
+ * source or without a primary hit gets (0, 0).
+ * Resolve.  After a call that leaves n samples since the move: occluded[i] = c_h + the occluded
+ * samples since the move; visibility[i] = 1.0f - (float)occluded / (float)(n_h + n), 1 without a
+ * primary hit; rgba its grey.  With the filter on, S is the sum of the accepted taps' counts as
+ * above and the denominator is the integer sum N of the accepted taps' (n_h + n), the centre
+ * included: visibility = 1.0f - (float)S / (float)N.  Before any move every n_h is 0. */
+#define RT_AO_HISTORY_DEFAULT 32
+int rt_occlusion_set_history(rt_scene* s, int on, int max_history, float normal_min, float plane_tol);
+/* out8 = {on, max_history, moves so far, cursor K, samples since the last move or drop
+ *         (= rt_occlusion_info[0]), 1 if history weights are in use (a move since the last drop), 0, 0};
+ * f2 = {normal_min, plane_tol}; either may be NULL.  Host state. */
+int rt_occlusion_history_info(const rt_scene* s, int32_t out8[8], float f2[2]);
+/* Test hook: the per-pixel history weight n_h, W*H int32 to host memory; RT_ERR_STATE without an
+ * accumulation, RT_ERR_ARG if cap is too small. */
+int rt_occlusion_history_weights(rt_scene* s, int32_t* dst, int64_t cap);
+/* Measurement hook: with `on`, later calls take start/stop events on the dispatches of
+ * occl_reproject_kernel (a move) and of the resolve with per-pixel totals (occl_resolve_kernel, or
+ * the filter's history form); ms2 (may be NULL) = their last timed milliseconds, < 0: none yet. */
+int rt_occlusion_history_timing(rt_scene* s, int on, float ms2[2]);
 
 /* Frame slots (1 = default, up to 8).  The reference rebuilds its BVH inside every
  * update_scene call (raytracer.cu:103-119), so a frame owns per-frame state: BVH, work

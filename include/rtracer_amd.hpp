@@ -274,6 +274,12 @@ inline void set_occlusion_filter(renv::gpu::Scene* scene, bool on = true, float 
                                  float plane_tol = RT_AO_FILTER_PLANE_DEFAULT) {
     rtamd_detail::check(rt_occlusion_set_filter(scene->handle(), on ? 1 : 0, normal_min, plane_tol), "set_occlusion_filter");
 }
+// Build extension (rt_occlusion_set_history): keep occlusion()'s samples across camera moves by
+// reprojection, at most `max_history` of them a pixel; off by default.
+inline void set_occlusion_history(renv::gpu::Scene* scene, bool on = true, int max_history = RT_AO_HISTORY_DEFAULT,
+                                  float normal_min = RT_AO_FILTER_NORMAL_DEFAULT, float plane_tol = RT_AO_FILTER_PLANE_DEFAULT) {
+    rtamd_detail::check(rt_occlusion_set_history(scene->handle(), on ? 1 : 0, max_history, normal_min, plane_tol), "set_occlusion_history");
+}
 // raytracer.cu:91-100: one-pixel trace with the reference's event log on stdout.
 inline void debug_cast(renv::gpu::Scene* scene, int x, int y) {
     std::vector<char> buf(1 << 16);

@@ -21,7 +21,18 @@ Then the interleaved pattern and the filtered resolve (section "filt
   - a quality table: the mean absolute difference of `visibility`, over the pixels with a primary
     hit, from the shared pattern's 1024-sample frame at the same radius, for shared n = 4, 16, 64,
     interleaved n = 4, interleaved n = 4 + filter, shared n = 4 + filter (a record, no threshold).
-Usage: python tools/occlusion_bench.py [scene] [W] [H] [calls] [samples] [all|base|filter]"""
+Then, on request only (section "history", or --history anywhere on the line), the
+interactive setting of 3.9 under a moving camera: 32 poses, each the last one translated by
+(0.05, 0, 0) through rt_camera_translate, 4 interleaved samples a pose through the filter, radius
++inf, device outputs.  History off (a restart a pose: what a library before the history does, and
+the only leg such a library runs) and on (every pose after the first a move):
+  - per pose the call's time, the median over `calls` repetitions of the whole path, and the
+    median of those over the moving poses 2 .. 32;
+  - occl_reproject_kernel's and the resolving kernel's own times by events on their dispatches
+    (rt_occlusion_history_timing), medians over the moving poses of further repetitions;
+  - the mean |visibility - the shared pattern's unfiltered 1024-sample frame at that pose| over
+    the pixels with a primary hit, at poses 1, 2, 4, 8, 16 and 32 (a record, no threshold).
+Usage: python tools/occlusion_bench.py [scene] [W] [H] [calls] [samples] [all|base|filter|history] [--history]"""
 import json
 import os
 import sys
@@ -34,12 +45,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "gpu-ray-tracer_amd"))
 import rtamd  # noqa: E402
 
-scene = sys.argv[1] if len(sys.argv) > 1 else "world8_stress"
-W, H = (int(sys.argv[2]), int(sys.argv[3])) if len(sys.argv) > 3 else (1920, 1080)
-calls = int(sys.argv[4]) if len(sys.argv) > 4 else 30
-K = int(sys.argv[5]) if len(sys.argv) > 5 else 16
-SECTIONS = sys.argv[6] if len(sys.argv) > 6 else "all"
-assert SECTIONS in ("all", "base", "filter"), SECTIONS
+HISTORY_FLAG = "--history" in sys.argv
+argv = [a for a in sys.argv if a != "--history"]
+scene = argv[1] if len(argv) > 1 else "world8_stress"
+W, H = (int(argv[2]), int(argv[3])) if len(argv) > 3 else (1920, 1080)
+calls = int(argv[4]) if len(argv) > 4 else 30
+K = int(argv[5]) if len(argv) > 5 else 16
+SECTIONS = "history" if HISTORY_FLAG else argv[6] if len(argv) > 6 else "all"
+assert SECTIONS in ("all", "base", "filter", "history"), SECTIONS
 REPS, WARM = 5, 3
 rtamd.set_device(0)
 s = rtamd.Scene.load_json(os.path.join(ROOT, "scenes", scene + ".json"), W, H)
@@ -75,7 +88,7 @@ occ = torch.empty((H, W), dtype=torch.int32, device="cuda")
 flags = torch.empty(n_px, dtype=torch.uint8, device="cuda")
 torch.cuda.synchronize()
 
-for radius in (float("inf"), 2.0) if SECTIONS != "filter" else ():
+for radius in (float("inf"), 2.0) if SECTIONS in ("all", "base") else ():
     rname = "inf" if radius == float("inf") else radius
     tmax = torch.full((n_px,), radius, dtype=torch.float32, device="cuda")
 
@@ -135,7 +148,7 @@ for radius in (float("inf"), 2.0) if SECTIONS != "filter" else ():
 rgba = torch.empty((H, W), dtype=torch.int32, device="cuda")
 torch.cuda.synchronize()
 decision = []
-for radius in (float("inf"), 2.0) if SECTIONS != "base" else ():
+for radius in (float("inf"), 2.0) if SECTIONS in ("all", "filter") else ():
     rname = "inf" if radius == float("inf") else radius
 
     def call(samples=K):
@@ -206,3 +219,85 @@ for radius in (float("inf"), 2.0) if SECTIONS != "base" else ():
     out(what="quality: mean |visibility - shared n=1024| over hit pixels", radius=rname, hit_pixels=int(hit.sum()), table=table)
 if decision:
     out(what="interleaved map decision", class_becomes_default=bool(all(decision)), per_radius=[bool(d) for d in decision])
+
+
+# ---- history across camera moves ----
+def history_leg():
+    POSES, STEP, N, MARKS = 32, (0.05, 0.0, 0.0), 4, (1, 2, 4, 8, 16, 32)
+    has = hasattr(rtamd.lib(), "rt_occlusion_set_history")
+    p0, q0 = s.camera()
+    pixels = np.stack(np.mgrid[0:H, 0:W][::-1], axis=-1).reshape(-1, 2).astype(np.int32)
+
+    def path():
+        """The poses in order, the camera set for each."""
+        s.set_camera(p0, q0)
+        for i in range(1, POSES + 1):
+            if i > 1:
+                s.translate_camera(STEP)
+            yield i
+
+    s.set_occlusion_pattern("shared")
+    s.set_occlusion_filter(False)
+    refs, hits = {}, {}
+    for i in path():
+        if i in MARKS:
+            s.occlusion_device(samples=1024, restart=True, visibility_ptr=vis.data_ptr())
+            refs[i] = vis.cpu().numpy().copy()
+            hits[i] = s.query(pixels=pixels, want=("hit",))["hit"].reshape(H, W) != 0
+    s.set_occlusion_pattern("interleaved")
+    s.set_occlusion_filter(True)
+    for mode in ("off", "on") if has else ("off",):
+        if has:
+            s.set_occlusion_history(mode == "on")
+        times = [[] for _ in range(POSES)]
+        err = {}
+        for r in range(WARM + calls):
+            s.occlusion_reset()
+            for i in path():
+                t0 = time.perf_counter()
+                s.occlusion_device(samples=N, visibility_ptr=vis.data_ptr(), occluded_ptr=occ.data_ptr(), rgba_ptr=rgba.data_ptr())
+                dt = time.perf_counter() - t0
+                if r >= WARM:
+                    times[i - 1].append(dt * 1e3)
+                if r == 0 and i in MARKS:
+                    err[str(i)] = round(float(np.abs(vis.cpu().numpy()[hits[i]] - refs[i][hits[i]]).mean()), 5)
+        per_pose = [round(sorted(t)[len(t) // 2], 4) for t in times]
+        moving = sorted(per_pose[1:])
+        kern = {}
+        if mode == "on":
+            rp, rs = [], []
+            s.history_timing(True)
+            for r in range(REPS):
+                s.occlusion_reset()
+                for i in path():
+                    s.occlusion_device(samples=N, visibility_ptr=vis.data_ptr(), occluded_ptr=occ.data_ptr(), rgba_ptr=rgba.data_ptr())
+                    if i > 1:
+                        a, b = s.history_timing(True)
+                        rp.append(a)
+                        rs.append(b)
+            s.history_timing(False)
+            kern = dict(occl_reproject_kernel_ms=round(sorted(rp)[len(rp) // 2], 4), resolving_filter_kernel_ms=round(sorted(rs)[len(rs) // 2], 4),
+                        moves=s.occlusion_history["moves"])
+        else:
+            s.filter_timing(True)
+            fs = []
+            for r in range(REPS):
+                for i in path():
+                    s.occlusion_device(samples=N, visibility_ptr=vis.data_ptr(), occluded_ptr=occ.data_ptr(), rgba_ptr=rgba.data_ptr())
+                    fs.append(s.filter_timing(True))
+            s.filter_timing(False)
+            kern = dict(occl_filter_kernel_ms=round(sorted(fs)[len(fs) // 2], 4))
+        print(json.dumps(dict(scene=scene, W=W, H=H, what="history", history=mode, poses=POSES, step=STEP, samples_per_pose=N,
+                              pattern="interleaved", filter=True, radius="inf", repetitions=calls, call_ms_per_pose=per_pose,
+                              call_ms_pose_1=per_pose[0], call_ms_moving_median=moving[len(moving) // 2],
+                              call_ms_moving_min=moving[0], call_ms_moving_max=moving[-1],
+                              mean_abs_error_vs_1024=err, **kern)), flush=True)
+    if has:
+        s.set_occlusion_history(False)
+    s.set_occlusion_filter(False)
+    s.set_occlusion_pattern("shared")
+    s.set_camera(p0, q0)
+
+
+if SECTIONS == "history":
+    history_leg()
