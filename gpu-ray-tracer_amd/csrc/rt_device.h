@@ -116,6 +116,11 @@ struct SceneView {           // read-only scene data (HBM, L2-resident)
     // table of HINT_SLOTS entries per instance, then its counters (hint_bytes).  Null: off.
     // Last, so that no field the kernels read in place moves (the kernarg-layout record).
     int* hint;
+    // Nearer child first (closest_hit; rt_plan.h: NF_*): the counters' block (the hint counters'
+    // stripes, bound whether or not the hints are on; null: not counted) and the mode.  After `hint`,
+    // for the same reason.
+    unsigned long long* nf_ctr;
+    int near_first, nf_pad;
 };
 
 struct TraceParams {

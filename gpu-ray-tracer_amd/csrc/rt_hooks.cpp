@@ -203,6 +203,28 @@ int rt_scene_shadow_hint_counters(rt_scene* s, uint64_t* out4) {
     return RT_OK;
 }
 
+int rt_scene_set_near_first(rt_scene* s, int mode) {
+    CHECK_SCENE(s);
+    if (mode != NF_OFF && mode != NF_ON && mode != NF_PROFILE) return fail(RT_ERR_ARG, "near-first mode: 0, 1 or 2");
+    s->near_first = mode;
+    if (s->multi) set_multi_near_first(s, mode);
+    return RT_OK;
+}
+
+int rt_scene_near_first_counters(rt_scene* s, uint64_t* out3) {
+    int r;
+    if ((r = hints_quiesce(s)) != RT_OK) return r;
+    if (!out3) return fail(RT_ERR_ARG, "null argument");
+    std::fill(out3, out3 + NF_COUNTERS, 0);
+    if (!s->d_hint) return RT_OK;
+    static_assert(NF_COUNTER0 >= HINT_COUNTERS && NF_COUNTER0 + NF_COUNTERS <= HINT_STRIPE_WORDS, "one stripe holds both sets");
+    uint64_t c[HINT_STRIPES * HINT_STRIPE_WORDS];
+    HIPCHK(hipMemcpy(c, s->d_hint + hint_table_ints((int)s->h.d_insts.size()), sizeof c, hipMemcpyDeviceToHost));
+    for (int k = 0; k < HINT_STRIPES; k++)
+        for (int i = 0; i < NF_COUNTERS; i++) out3[i] += c[k * HINT_STRIPE_WORDS + NF_COUNTER0 + i];
+    return RT_OK;
+}
+
 // Profiling aid (tools/group_profile.py, not on the product path): per-group durations
 // (100 MHz ticks) of the fast frame kernel over rows row0, row0 + row_step, ... (compact),
 // as bench.py's rank row0 of row_step renders them.  `reps` frames, each with the per-frame

@@ -122,6 +122,12 @@ struct FrameSlot {
 #endif
 
 inline bool hints_default() { const char* e = getenv("RT_SHADOW_HINTS"); return !e || atoi(e) != 0; }
+// RT_NEAR_FIRST in the environment: 0 off (the A/B arm), 2 the profiling variant too; default on
+inline int near_first_default() {
+    const char* e = getenv("RT_NEAR_FIRST");
+    const int m = e ? atoi(e) : rtd::NF_ON;
+    return m == rtd::NF_OFF || m == rtd::NF_PROFILE ? m : rtd::NF_ON;
+}
 
 struct rt_scene {
     rt::Scene h;
@@ -143,6 +149,7 @@ struct rt_scene {
     // null for scenes of the grid-wide BVH build.  shadow_hints: rt_scene_set_shadow_hints.
     int* d_hint = nullptr;
     bool shadow_hints = hints_default();         // (RT_SHADOW_HINTS=0 in the environment: off, the A/B arm)
+    int near_first = near_first_default();       // rtd::NF_* (rt_plan.h): rt_scene_set_near_first
     uint32_t* d_canvas = nullptr;
     int* d_dbg = nullptr;
     float4* d_atlas = nullptr;                   // atlas texels (float4, byte / 255)
@@ -342,6 +349,7 @@ int render_multi(rt_scene* s, const rt_render_opts* o, rt_stats* stats);
 void free_multi(rt_scene* s);
 void set_multi_overlap(rt_scene* s, int policy);   // the replicas of rt_scene_set_devices
 void set_multi_shadow_hints(rt_scene* s, bool on);
+void set_multi_near_first(rt_scene* s, int mode);
 
 // Mean kernel time (*ms) over `reps` runs of launch(i), which puts its work between ev[0] and
 // ev[1] on the scene's stream; with more than one run the first is left out.

@@ -287,7 +287,8 @@ struct Best { float time; int inst, tri; float u, v; };     // closest accepted 
 // steps, leaf visits, triangle-loop iterations -- SIMD work regardless of active lanes).
 struct WaveCounters { unsigned long long rays, nodes, leaves, tris, wq, wpair, wleaf, wtri, cyc_q, cyc_leaf, cyc_all, cyc_sample, cyc_post, wbary, lbary, live,
                       cyc_light, cyc_normal, cyc_park,      // PROF: light step, hit normal, parking
-                      hint;                                 // occluder hints: the wave's three counts (HINT_FIELD_BITS each)
+                      hint,                                 // occluder hints: the wave's three counts (HINT_FIELD_BITS each)
+                      nf;                                   // near-first: the wave's three counts (NF_FIELD_BITS each)
                       unsigned long long* pc; };            // PROF: this wave's occupancy counters in LDS
 
 __device__ __forceinline__ int uni(int x) { return __builtin_amdgcn_readfirstlane(x); }   // value known wave-uniform
@@ -395,9 +396,15 @@ __device__ __forceinline__ void axis_step(const TriAx& x, const Ray& mr, V3 inv,
 // distance minus the pruning slack M (closest_hit).  A triangle whose plane crossing is
 // certainly below it lies outside the box, so its inside test is skipped.
 // AXIS: the axis-plane triangle path (S.tri_ax, pre.inv set; identity rotations only).
-template <bool STATS, bool AXIS = false, bool PROF = false>
+// NEAR, `nf` (wave-uniform): a leaf visit of a near-first walk (closest_hit).  While the
+// lane has accepted nothing in this leaf, the plane tests compare against the entry best widened by
+// NF_W (nf_pass_bound, rt_math.h: `t_best` holds that comparand; the entry best itself stays in
+// b.time), a triangle is still accepted only below the entry best, and one that passes the inside
+// test within NF_W of it (nf_near_tie) sets `flag`: the result could depend on the order in which
+// the leaves were met.  After the first accept t_best is the accepted time, as without NEAR.
+template <bool STATS, bool AXIS = false, bool PROF = false, bool NEAR = false>
 __device__ __forceinline__ bool cast_local(const SceneView& S, const BvhRefs& bv, int ti, const Ray& r, Best& b,
-                                           const DirPre& pre, WaveCounters& wc, float t_lo) {
+                                           const DirPre& pre, WaveCounters& wc, float t_lo, bool nf, int& flag) {
     int mesh_id;
     const Pose ip = inst_pose(S, bv, ti, mesh_id);
     mesh_id = uni(mesh_id);
@@ -422,6 +429,15 @@ __device__ __forceinline__ bool cast_local(const SceneView& S, const BvhRefs& bv
     }
     int best = -1;
     float bu = 0.0f, bv_ = 0.0f, t_best = b.time;
+    if (NEAR && nf) t_best = nf_pass_bound(b.time);
+    // the accept of a triangle that passed the inside test at `time` (< t_best)
+    auto accept = [&](float time) {
+        if (NEAR && nf && best < 0) {
+            if (nf_near_tie(time, b.time)) flag = 1;
+            return time < b.time;
+        }
+        return true;
+    };
     if (AXIS) {
         // Axis-plane path (fast kernel, identity rotations): exact plane time from the
         // per-query reciprocal (axis_plane_t), then the exact in-plane reject (TriAx);
@@ -461,7 +477,7 @@ __device__ __forceinline__ bool cast_local(const SceneView& S, const BvhRefs& bv
                 const TriRest q = ld_rest(S.tris, t);
                 if (pass) {
                     float time, u, v;
-                    if (tri_inside_t(h.a, q.b, q.c, q.area, q.inv_area, mr, tt, time, u, v)) {
+                    if (tri_inside_t(h.a, q.b, q.c, q.area, q.inv_area, mr, tt, time, u, v) && accept(time)) {
                         t_best = time; best = t; bu = u; bv_ = v;
                     }
                 }
@@ -482,7 +498,7 @@ __device__ __forceinline__ bool cast_local(const SceneView& S, const BvhRefs& bv
         }
         if (!pass) continue;
         const TriRest q = ld_rest(S.tris, t);
-        if (tri_inside_f(h.a, q.b, q.c, q.area, q.inv_area, mr, t_best, denom, num, time, u, v)) {
+        if (tri_inside_f(h.a, q.b, q.c, q.area, q.inv_area, mr, t_best, denom, num, time, u, v) && accept(time)) {
             t_best = time; best = t; bu = u; bv_ = v;
         }
     }
@@ -490,6 +506,12 @@ __device__ __forceinline__ bool cast_local(const SceneView& S, const BvhRefs& bv
     b.time = (t_best * scale) * dir_len;                      // fix_isect, then cast_local
     b.inst = ti; b.tri = best; b.u = bu; b.v = bv_;
     return true;
+}
+template <bool STATS, bool AXIS = false, bool PROF = false>
+__device__ __forceinline__ bool cast_local(const SceneView& S, const BvhRefs& bv, int ti, const Ray& r, Best& b,
+                                           const DirPre& pre, WaveCounters& wc, float t_lo) {
+    int flag = 0;
+    return cast_local<STATS, AXIS, PROF, false>(S, bv, ti, r, b, pre, wc, t_lo, false, flag);
 }
 
 // World-space normal of the accepted hit (trimesh.cu:58-65, hitable.cu:20-23, scene.cu:35-37).
@@ -598,14 +620,29 @@ __device__ __forceinline__ bool ft_root_hit(const SceneView& S, const BvhRefs& b
 // lane's b.tri is replaced by the code of the leaf visit that occluded it (nothing reads a shadow
 // hit's triangle in an opaque scene), and after the walk lane 0 stores at most one word to *hslot:
 // the code of a lane the walk occluded and the seed did not, or 0 when a seed decided no lane.
+//
+// Nearer child first (NEAR: the hinted kernels and their profiling twin; `nf_in`, wave-uniform: this
+// query walks near-first -- no shadow lane, pruning on).  At a step where
+// some lane hits each child, the lanes that hit both vote with the entry bounds the step already
+// has: B is visited first when more of them enter B first (ties and empty votes: A first).  The
+// two children then change places before the step's one set of arms: a pending internal A is
+// pushed as B is, a pending leaf A as NF_LEAF_A + its parent, popped as the "that child alone" form
+// (bonly 4), and two leaves reach the leaf site B first.  A step that hits one child or none runs
+// what it ran, after one scalar test.  The order can only matter between near-tied leaves:
+// cast_local flags the lane that meets one, and a walk that ends with a flagged lane puts every
+// lane's Best back to "no hit" and runs again from the root in DFS order (nf off), so the result
+// is the DFS walk's bit for bit.  wc.nf: the wave's near-first queries, reruns and swapped steps
+// (NF_FIELD_BITS each).
+constexpr int NF_LEAF_A = 1 << 30;                            // stack entry -2 - (NF_LEAF_A + node): pending leaf A of node
 __device__ __forceinline__ int lane_id_fresh();               // (defined with the launch-parameter helpers below)
 template <bool NOLEAF, bool STATS, bool FT = false, bool AXIS = false, bool PROF = false, bool BRUTE = false,
-          bool HINT = false>
+          bool HINT = false, bool NEAR = false>
 __device__ __forceinline__ bool closest_hit(const SceneView& S, const BvhRefs& bv, bool active_in, const Ray& r,
                                             Best& b, WaveCounters& wc, float occl_t = -1.0f,
                                             float lim = INFINITY, float zcut = -1.0f, int seed = 0,
-                                            int* hslot = nullptr) {
+                                            int* hslot = nullptr, bool nf_in = false) {
     static_assert(!HINT || (FT && !STATS && !PROF && !BRUTE && !NOLEAF), "hints: the fast kernels' ordered walk");
+    static_assert(!NEAR || (FT && !STATS && !BRUTE && !NOLEAF), "near-first: the fast kernels' ordered walk");
     const bool prune = !STATS && S.prune_abs >= 0.0f;
     float im = 0.0f;                                           // max_a |1/d_a| (set below)
     auto slack = [&](float t) { return (S.prune_abs + 0x1p-14f * fabsf(t)) * im + 0x1p-14f * fabsf(t); };
@@ -689,20 +726,29 @@ __device__ __forceinline__ bool closest_hit(const SceneView& S, const BvhRefs& b
         // bonly: 1 a popped leaf B of `node`; 2 / 3 (HINT) the seed, leaf A / B of `node`.  The seed's
         // iteration is the only one whose next node is the root (next == 0), and everything it adds sits
         // on the popped-leaf and leaf-visit paths: a descending step runs what it ran without hints.
+        // (NEAR) 4: a popped pending leaf A of `node`.
         int node = 0, sp = 0, stk = 0, bonly = 0;
         if (HINT && seed > 0) { node = hint_node(seed); bonly = 2 + hint_side(seed); }
-        auto push = [&](int e) { asm("v_writelane_b32 %0, %1, m0" : "+v"(stk) : "s"(e), "{m0}"(sp)); sp++; };
+        unsigned nf = NEAR && nf_in;                           // (uniform, 0 / 1) this walk orders by the vote
+        int flag = 0;                                          // the lane met a near-tie between leaves (cast_local)
+        int nsw = 0, nrr = 0;                                  // (uniform) swapped steps, reruns
+        // (the entry through readfirstlane: a no-op where the compiler knows it uniform, which it does in
+        // every kernel but the profiling variant once that orders its walk)
+        auto push = [&](int e) { asm("v_writelane_b32 %0, %1, m0" : "+v"(stk) : "s"(uni(e)), "{m0}"(sp)); sp++; };
         for (;;) {
             const float4* rec = bv.fnode + 4 * node;
             if (PROF) wc.wpair++;
             const float2 rf = *reinterpret_cast<const float2*>(rec + 3);
-            const int ra = uni(__float_as_int(rf.x)), rb = uni(__float_as_int(rf.y));
+            int ra = uni(__float_as_int(rf.x)), rb = uni(__float_as_int(rf.y));
             float ta, tb;
             pair_hit_tt2c(rec, r, ri, ct, ta, tb);
             float lt = QNAN, t2 = QNAN;                        // leaf entry bounds (NaN: missed)
             int linst = -1, inst2 = -1, next = -1;             // their instances, the next node (uniform; -1: pop)
             int lcode = 0;                                     // hint_code of leaf `linst` (HINT)
             if (bonly) {                                       // popped: leaf B of this node
+                if (NEAR && bonly == 4) {                      // a pending leaf A: that child alone
+                    lt = ta; linst = -1 - ra; lcode = hint_code(node, 0);
+                } else
                 if (HINT && bonly > 1) {                       // the seed: that child alone if it is a leaf, then the root
                     next = 0;
                     const int rs = bonly == 2 ? ra : rb;
@@ -713,9 +759,21 @@ __device__ __forceinline__ bool closest_hit(const SceneView& S, const BvhRefs& b
                 bonly = 0;
             } else {
                 const unsigned hA = any_lane(__ballot(ta <= ct)), hB = any_lane(__ballot(tb <= ct));
+                int sw = 0;                                    // NF_LEAF_A: the children changed places for this step
+                if (NEAR && (nf & hA & hB)) {                  // the vote of the lanes that hit both children
+                    const unsigned long long both = __ballot(ta <= ct && tb <= ct);
+                    if (__popcll(__ballot(tb < ta) & both) > __popcll(__ballot(ta < tb) & both)) {
+                        // more of them enter B first: B plays A from here on (a pending leaf "B" is then leaf
+                        // A of the node; lcode names the other side, and nothing reads it: no shadow lane)
+                        const int rs = ra; ra = rb; rb = rs;
+                        const float ts = ta; ta = tb; tb = ts;
+                        sw = NF_LEAF_A;
+                        nsw++;
+                    }
+                }
                 if (ra >= 0 && hA) {                           // descend into A, B after A's subtree
                     next = ra;
-                    if (hB) push(rb >= 0 ? rb : -2 - node);
+                    if (hB) push(rb >= 0 ? rb : -2 - node - sw);
                 } else {
                     if (hA) { lt = ta; linst = -1 - ra; lcode = hint_code(node, 0); }   // leaf A (ra < 0 here)
                     if (hB) {
@@ -736,7 +794,7 @@ __device__ __forceinline__ bool closest_hit(const SceneView& S, const BvhRefs& b
                         }
                         const unsigned long long cl0 = PROF ? __builtin_amdgcn_s_memtime() : 0;
                         if (PROF) { wc.wleaf++; wc.leaves += __popcll(__ballot(lh)); }
-                        if (lh && cast_local<false, AXIS, PROF>(S, bv, linst, r, b, pre, wc, t_low(lt)))
+                        if (lh && cast_local<false, AXIS, PROF, NEAR>(S, bv, linst, r, b, pre, wc, t_low(lt), nf != 0, flag))
                             if (b.time <= occl_t) {            // occluded: this lane is done
                                 ct = QNAN;
                                 if (HINT) b.tri = lcode;
@@ -754,12 +812,25 @@ __device__ __forceinline__ bool closest_hit(const SceneView& S, const BvhRefs& b
                 }
             }
             if (next >= 0) { node = next; continue; }
-            if (sp == 0) break;
+            if (sp == 0) {
+                if (!(NEAR && nf && __ballot(flag != 0))) break;
+                // a near-tie between leaves: every lane starts clean, in DFS order
+                nf = 0; nrr = 1;
+                b.time = INFINITY; b.inst = -1; b.tri = -1; b.u = 0.0f; b.v = 0.0f;
+                ct = !active_in ? QNAN : prune ? cut() : INFINITY;
+                node = 0;
+                continue;
+            }
             sp--;                                              // an internal node, or leaf B of node -2 - e
             const int e = __builtin_amdgcn_readlane(stk, sp);
-            if (e < 0) { node = -2 - e; bonly = 1; }
+            if (e < 0) {
+                node = -2 - e; bonly = 1;
+                if (NEAR && node >= NF_LEAF_A) { node -= NF_LEAF_A; bonly = 4; }
+            }
             else node = e;
         }
+        if (NEAR && nf_in)
+            wc.nf += 1ull + ((unsigned long long)nrr << NF_FIELD_BITS) + ((unsigned long long)nsw << 2 * NF_FIELD_BITS);
         if (HINT && hslot) {                                   // (uniform) at most one word, not waited for
             // A lane the seed visit occluded holds the seed as its code; a lane the walk occluded holds
             // another (the walk's visit of the seed's leaf decides what the seed visit decided).
@@ -904,8 +975,10 @@ __device__ __forceinline__ KTP& kparams() {
 #endif
 typedef __attribute__((address_space(4))) const SceneView KSV;
 static_assert(sizeof(TraceParams) % alignof(SceneView) == 0, "SceneView follows TraceParams in the kernarg segment");
-static_assert(sizeof(TraceParams) == 400 && sizeof(SceneView) == 136 && offsetof(SceneView, hint) == 128,
-              "kernarg layout (the kernels read it in place; the hint table after the 128 bytes every variant had)");
+static_assert(sizeof(TraceParams) == 400 && sizeof(SceneView) == 152 && offsetof(SceneView, hint) == 128 &&
+                  offsetof(SceneView, nf_ctr) == 136,
+              "kernarg layout (the kernels read it in place; the hint table after the 128 bytes every variant had, "
+              "the near-first fields after it)");
 __device__ __forceinline__ SceneView kscene() {
     const __attribute__((address_space(4))) char* p =
         (const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr();
@@ -1034,6 +1107,8 @@ __device__ __forceinline__ V4 trace_sample(const SceneView& S, const BvhRefs& bv
     constexpr bool NN = PARK;                                   // is_nn parked across the queries
     // occluder hints (closest_hit): the fast, fully parked or unparked, lockstep (NS = 0) kernels
     constexpr bool HINT = FT && OPQ && !STATS && !PROF && !BRUTE && !PART;
+    // nearer child first (closest_hit): the same kernels, and their profiling twin on request
+    constexpr bool NEAR = FT && OPQ && !STATS && !BRUTE && !PART;
     int hkey = -1;                                              // hint_key of the wave's last normal hit (uniform)
     KTP& P0 = kparams();
     Frame cur;
@@ -1238,8 +1313,15 @@ __device__ __forceinline__ V4 trace_sample(const SceneView& S, const BvhRefs& bv
         const bool qa = st == ST_WAIT_NORMAL || (st == ST_WAIT_SHADOW && max_t >= 0.0f);
         const unsigned long long prof_p0 = wc.wpair, prof_l0 = wc.wleaf;
         if (HINT && seed != 0 && !hint_node_ok(seed, SV().n_real)) seed = 0;   // any table contents: a record of this tree, or none
-        const bool hit = closest_hit<false, STATS, FT, AXIS, PROF, BRUTE, HINT>(SV(), bv, qa, q, b, wc, occl, lim, -1.0f,
-                                                                               seed, hslot);
+        // Near-first: a wave query with an active lane, none of them a shadow lane (the host clears
+        // the mode where the pruning claim does not hold; the profiling variant wants NF_PROFILE).
+        bool nfq = false;
+        if (NEAR) {
+            const int nm = SV().near_first;
+            if (PROF ? nm == NF_PROFILE : nm != NF_OFF) nfq = __ballot(qa) && !__ballot(st == ST_WAIT_SHADOW && qa);
+        }
+        const bool hit = closest_hit<false, STATS, FT, AXIS, PROF, BRUTE, HINT, NEAR>(SV(), bv, qa, q, b, wc, occl, lim,
+                                                                                     -1.0f, seed, hslot, nfq);
         if (HINT) {                                            // a normal query's first hit keys the wave's shadow queries
             const unsigned long long hm = __ballot(hit && st == ST_WAIT_NORMAL);
             if (hm) {
@@ -1797,6 +1879,14 @@ __global__ __launch_bounds__(TRACE_BLOCK_P) void trace_kernel(TraceParams P_arg,
             const unsigned long long v = (wc.hint >> i * HINT_FIELD_BITS) & ((1ull << HINT_FIELD_BITS) - 1);
             if (v) atomicAdd(&hc[i], v);
         }
+    }
+    if (wc.nf && lane == 0) {                                  // near-first: the wave's counts, in the same stripes
+        unsigned long long* const nc = SV().nf_ctr;
+        if (nc)
+            for (int i = 0; i < NF_COUNTERS; i++) {
+                const unsigned long long v = (wc.nf >> i * NF_FIELD_BITS) & (i == 2 ? ~0ull : (1ull << NF_FIELD_BITS) - 1);
+                if (v) atomicAdd(&nc[(blockIdx.x % HINT_STRIPES) * HINT_STRIPE_WORDS + NF_COUNTER0 + i], v);
+            }
     }
     if (CYC && P.stats && lane == 0) {
         if (wc.rays) atomicAdd(&P.stats[0], wc.rays);

@@ -414,6 +414,17 @@ RT_HD bool tri_inside_f(V3 a, V3 b, V3 c, float area, float inv_area, const Ray&
     return tri_inside_t(a, b, c, area, inv_area, r, t, time, u, v);
 }
 
+// Near-first walks (rt_kernels.hip: closest_hit, cast_local).  A leaf is entered with the
+// lane's best t_entry, a time converted from another leaf's: (t * scale) * dir_len, within 6 u of t
+// (u = 2^-24: scale and dir_len are within an ulp of 1, and two roundings).  NF_W = 16 u.
+//   nf_pass_bound: the comparand of the plane tests until the lane accepts something in this leaf;
+//   nf_near_tie:   a triangle that passed the inside test at `time` (< nf_pass_bound) could win or
+//                  lose against t_entry depending on the order the two leaves are met in.
+// +inf stays +inf and ties with nothing.
+constexpr float NF_W = 0x1p-20f;
+RT_HD float nf_pass_bound(float t_entry) { return t_entry * (1.0f + NF_W); }
+RT_HD bool nf_near_tie(float time, float t_entry) { return time >= t_entry * (1.0f - NF_W); }
+
 // Axis-plane triangles (every cube face): the three vertices share coordinate `ax`
 // exactly and the stored plane normal pn is exactly +-e_ax (two +-0 components).  Then
 // the reference's plane arithmetic collapses without rounding: dot(r.d, pn) = +0 + ... =

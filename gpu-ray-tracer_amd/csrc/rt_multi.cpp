@@ -158,6 +158,7 @@ int setup_multi(rt_scene* s, MultiDev* m, Rccl* R) {
         rp->h = s->h; rp->finished = true;
         rp->h.atlas_rgba.clear();
         rp->overlap = s->overlap;
+        rp->near_first = s->near_first;                        // (a mode set before the split holds on the replicas)
         rp->ranks_per_device = m->per_dev;
         m->reps.push_back(rp);
         m->inst_gen.push_back(0);
@@ -211,6 +212,9 @@ int setup_multi(rt_scene* s, MultiDev* m, Rccl* R) {
 
 void rti::set_multi_overlap(rt_scene* s, int policy) {
     for (rt_scene* rp : s->multi->reps) rp->overlap = policy;
+}
+void rti::set_multi_near_first(rt_scene* s, int mode) {
+    for (rt_scene* rp : s->multi->reps) rp->near_first = mode;
 }
 void rti::set_multi_shadow_hints(rt_scene* s, bool on) {
     for (rt_scene* rp : s->multi->reps) rp->shadow_hints = on;

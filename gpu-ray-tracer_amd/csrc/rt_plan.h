@@ -248,6 +248,12 @@ __host__ __device__ inline bool hint_node_ok(int code, int n_real) { return code
 __host__ __device__ inline size_t hint_table_ints(int n_inst) { return (size_t)n_inst * HINT_SLOTS; }
 // the counters: HINT_STRIPES copies, one 64-byte line each (a block adds to copy block % HINT_STRIPES; the host sums)
 constexpr int HINT_STRIPES = 64, HINT_STRIPE_WORDS = 8;
+// ---- Nearer child first in closest-hit queries (SceneView::near_first)
+// Three counters, in words NF_COUNTER0 .. +2 of each stripe above: wave queries walked near-first,
+// those run again in DFS order, pair steps that swapped.
+constexpr int NF_COUNTERS = 3, NF_COUNTER0 = 3;
+constexpr int NF_FIELD_BITS = 21;       // a wave's three counts in one 64-bit scalar (the swaps take the top 22)
+enum : int { NF_OFF = 0, NF_ON = 1, NF_PROFILE = 2 };   // NF_PROFILE: the profiling variant orders its walk too
 inline size_t hint_bytes(int n_inst) {
     return hint_table_ints(n_inst) * sizeof(int) + (size_t)HINT_STRIPES * HINT_STRIPE_WORDS * sizeof(unsigned long long);
 }

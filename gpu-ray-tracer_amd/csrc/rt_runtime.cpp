@@ -587,6 +587,7 @@ SceneView rti::view_of(const rt_scene* s, bool use_bvh) {
     v.prune_abs = prune_slack(s, std::max(std::fabs(cp.x), std::max(std::fabs(cp.y), std::fabs(cp.z))));
     v.tri_ax = (v.ident_all && !s->h.d_tris.empty()) ? s->d_tri_ax : nullptr;
     v.hint = nullptr;                                          // (launch_trace binds the table)
+    v.nf_ctr = nullptr; v.near_first = NF_OFF; v.nf_pad = 0;   // (and the near-first mode and counters)
     return v;
 }
 
@@ -631,6 +632,9 @@ int rti::launch_trace(rt_scene* s, const rt_render_opts& o, const TraceRequest& 
     }
     SceneView S = view_of(s, o.use_bvh != 0);
     S.hint = s->shadow_hints ? s->d_hint : nullptr;
+    // nearer child first: only where the pruning claim holds (closest_hit); counted in the hint block's stripes
+    S.near_first = S.prune_abs >= 0.0f ? s->near_first : NF_OFF;
+    S.nf_ctr = s->d_hint ? reinterpret_cast<unsigned long long*>(s->d_hint + hint_table_ints(S.n_inst)) : nullptr;
     P.lanes_per_px = g.lanes_per_px; P.px_per_wave = g.px_per_wave; P.gw = g.gw; P.gh = g.gh;
     P.l_shift = g.l_shift; P.gw_shift = g.gw_shift; P.n_gx = g.n_gx; P.n_groups = g.n_groups;
     if (q.geo) { q.geo[0] = g.n_groups; q.geo[1] = g.gw; q.geo[2] = g.gh; q.geo[3] = g.n_gx; }

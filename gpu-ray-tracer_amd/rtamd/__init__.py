@@ -53,7 +53,9 @@ SYMBOLS = [
     "rt_occlusion_set_history", "rt_occlusion_history_info", "rt_occlusion_history_weights", "rt_occlusion_history_timing",
     "rt_scene_set_shadow_hints", "rt_scene_shadow_hints_fill", "rt_scene_shadow_hint_code",
     "rt_scene_shadow_hint_counters", "rt_scene_shadow_hints_read",
+    "rt_scene_set_near_first", "rt_scene_near_first_counters",
 ]
+RT_NEAR_FIRST_OFF, RT_NEAR_FIRST_ON, RT_NEAR_FIRST_PROFILE = 0, 1, 2
 RT_QUERY_ORDER_CALLER, RT_QUERY_ORDER_SORTED = 0, 1
 RT_ADAPTIVE_THRESHOLD_DEFAULT = 8.0 / 255.0
 RT_AO_MAX_SAMPLES, RT_AO_BIAS_DEFAULT = 1024, 1e-3
@@ -198,6 +200,9 @@ def lib():
         L.rt_scene_shadow_hint_code.argtypes = [vp, ip, ctypes.POINTER(ctypes.c_int32)]
         L.rt_scene_shadow_hint_counters.argtypes = [vp, vp]
         L.rt_scene_shadow_hints_read.argtypes = [vp, vp, ctypes.c_int64]
+    if hasattr(L, "rt_scene_set_near_first"):   # (absent from libraries before nearer-child-first: A/B runs)
+        L.rt_scene_set_near_first.argtypes = [vp, ip]
+        L.rt_scene_near_first_counters.argtypes = [vp, vp]
     L.rt_query_opts_default.argtypes = [ctypes.POINTER(QueryOpts)]
     L.rt_query_opts_default.restype = None
     L.rt_query.argtypes = [vp, ctypes.POINTER(QueryOpts), ctypes.POINTER(Stats)]
@@ -911,6 +916,18 @@ class Scene:
         v = np.zeros(4, np.uint64)
         _check(lib().rt_scene_shadow_hint_counters(self._h, _ptr(v)))
         return dict(zip(("queries", "seeded", "ended", "entries"), [int(x) for x in v]))
+
+    def set_near_first(self, mode):
+        """Nearer child first in closest-hit queries: 0 off, 1 on (default), 2 on and in the
+        profiling variant too; the frame is the same either way (rt_scene_set_near_first)."""
+        _check(lib().rt_scene_set_near_first(self._h, int(mode)))
+
+    def near_first_counters(self):
+        """Counters since the last shadow_hints_fill: wave queries walked near-first, those walked
+        again in the fixed order, pair steps that swapped."""
+        v = np.zeros(3, np.uint64)
+        _check(lib().rt_scene_near_first_counters(self._h, _ptr(v)))
+        return dict(zip(("queries", "reruns", "swaps"), [int(x) for x in v]))
 
     def set_devices(self, devices, n_ranks=None):
         """Split every whole frame row-cyclically over `devices` from this process (n_ranks

@@ -34,6 +34,7 @@ extern "C" {
  *    rt_query_opts keeps its layout, the switch is scene state)
  *    (still 5: additive -- the RT_EXPORT_BVH_* values of rt_scene_export, a test hook)
  *    (still 5: additive -- rt_scene_set_shadow_hints and its test hooks)
+ *    (still 5: additive -- rt_scene_set_near_first and its counters)
  *    (still 5: additive -- rt_accumulate_set_adaptive / rt_accumulate_adaptive_info and the pass
  *    buffer's test hooks; rt_accum_opts keeps its layout, the switch is scene state)
  *    (still 5: additive -- rt_occlusion and its companions, rt_ao_direction; no existing entry or
@@ -645,6 +646,20 @@ int rt_scene_shadow_hints_fill(rt_scene* s, int32_t value);
 int rt_scene_shadow_hints_read(rt_scene* s, int32_t* dst, int64_t cap);
 int rt_scene_shadow_hint_code(rt_scene* s, int inst, int32_t* code);
 int rt_scene_shadow_hint_counters(rt_scene* s, uint64_t out4[4]);
+
+/* Nearer child first in closest-hit queries: the fast frames of all-opaque
+ * scenes whose boxes provably hold their triangles visit, at a step where both children are hit,
+ * the child more lanes enter first; a query whose result could depend on that order is detected
+ * and walked again in the fixed order, so a frame is the same with the switch on or off.
+ * mode 0: off; 1: on (the default; RT_NEAR_FIRST=0 in the environment: off); 2: on, and the
+ * profiling variant (rt_frame_work, rt_profile_groups) orders its walk too -- its counts are the
+ * fixed order's otherwise.  A scene split by rt_scene_set_devices switches its replicas too, and
+ * replicas made later take the scene's mode.
+ * rt_scene_near_first_counters (test hook) reads the counters accumulated since the last
+ * rt_scene_shadow_hints_fill: wave queries walked near-first, those walked again in the fixed
+ * order, pair steps that swapped; all 0 for a scene without a hint table. */
+int rt_scene_set_near_first(rt_scene* s, int mode);
+int rt_scene_near_first_counters(rt_scene* s, uint64_t out3[3]);
 
 /* Profiling hook: launches an empty marker kernel of `tag` (1..64) workgroups on `stream` (a
  * hipStream_t; NULL = the default stream), so a rocprofv3 kernel or counter trace can find the
