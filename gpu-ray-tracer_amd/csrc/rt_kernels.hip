@@ -633,21 +633,34 @@ __device__ __forceinline__ bool ft_root_hit(const SceneView& S, const BvhRefs& b
 // lane's Best back to "no hit" and runs again from the root in DFS order (nf off), so the result
 // is the DFS walk's bit for bit.  wc.nf: the wave's near-first queries, reruns and swapped steps
 // (NF_FIELD_BITS each).
+//
+// Query kind (KIND).  The live lanes of an NS = 0 kernel run in lockstep, so a
+// wave query there is all normal lanes or all shadow lanes, and the two features belong to one kind
+// each: the caller picks the walk once per wave query, and neither kind carries the other's code.
+//  QK_ANY     neither feature (every kernel outside the class, and the caller-ray queries);
+//  QK_SHADOW  hints, with the occlusion exit and `lim`; no vote, no swap, no pending leaf A, no
+//             near-tie flag and no rerun.  A normal lane in it (occl_t < 0, lim = inf) walks in DFS order;
+//  QK_NORMAL  near-first (`nf_in` still a run-time value: the rerun and the switch need it); no seed,
+//             no occlusion exit, `occl_t` and `lim` not read (the cut is the closest hit's alone);
+//  QK_NEAR    near-first with the occlusion exit and `lim`, no hints: the profiling twin's one walk.
+enum QueryKind { QK_ANY = 0, QK_SHADOW, QK_NORMAL, QK_NEAR };
 constexpr int NF_LEAF_A = 1 << 30;                            // stack entry -2 - (NF_LEAF_A + node): pending leaf A of node
 __device__ __forceinline__ int lane_id_fresh();               // (defined with the launch-parameter helpers below)
 template <bool NOLEAF, bool STATS, bool FT = false, bool AXIS = false, bool PROF = false, bool BRUTE = false,
-          bool HINT = false, bool NEAR = false>
+          int KIND = QK_ANY>
 __device__ __forceinline__ bool closest_hit(const SceneView& S, const BvhRefs& bv, bool active_in, const Ray& r,
                                             Best& b, WaveCounters& wc, float occl_t = -1.0f,
                                             float lim = INFINITY, float zcut = -1.0f, int seed = 0,
                                             int* hslot = nullptr, bool nf_in = false) {
+    constexpr bool HINT = KIND == QK_SHADOW, NEAR = KIND == QK_NORMAL || KIND == QK_NEAR;
+    constexpr bool OCCL = KIND != QK_NORMAL;                   // the occlusion exit and `lim` are compiled in
     static_assert(!HINT || (FT && !STATS && !PROF && !BRUTE && !NOLEAF), "hints: the fast kernels' ordered walk");
     static_assert(!NEAR || (FT && !STATS && !BRUTE && !NOLEAF), "near-first: the fast kernels' ordered walk");
     const bool prune = !STATS && S.prune_abs >= 0.0f;
     float im = 0.0f;                                           // max_a |1/d_a| (set below)
     auto slack = [&](float t) { return (S.prune_abs + 0x1p-14f * fabsf(t)) * im + 0x1p-14f * fabsf(t); };
     auto cut = [&]() {
-        const float c = fminf(b.time, lim);
+        const float c = OCCL ? fminf(b.time, lim) : b.time;
         return c + slack(c);
     };
     bool active = active_in;
@@ -795,7 +808,7 @@ __device__ __forceinline__ bool closest_hit(const SceneView& S, const BvhRefs& b
                         const unsigned long long cl0 = PROF ? __builtin_amdgcn_s_memtime() : 0;
                         if (PROF) { wc.wleaf++; wc.leaves += __popcll(__ballot(lh)); }
                         if (lh && cast_local<false, AXIS, PROF, NEAR>(S, bv, linst, r, b, pre, wc, t_low(lt), nf != 0, flag))
-                            if (b.time <= occl_t) {            // occluded: this lane is done
+                            if (OCCL && b.time <= occl_t) {    // occluded: this lane is done
                                 ct = QNAN;
                                 if (HINT) b.tri = lcode;
                             }
@@ -1315,13 +1328,22 @@ __device__ __forceinline__ V4 trace_sample(const SceneView& S, const BvhRefs& bv
         if (HINT && seed != 0 && !hint_node_ok(seed, SV().n_real)) seed = 0;   // any table contents: a record of this tree, or none
         // Near-first: a wave query with an active lane, none of them a shadow lane (the host clears
         // the mode where the pruning claim does not hold; the profiling variant wants NF_PROFILE).
+        const bool shq = NEAR && __ballot(st == ST_WAIT_SHADOW && qa);   // (uniform) a shadow wave query
         bool nfq = false;
         if (NEAR) {
             const int nm = SV().near_first;
-            if (PROF ? nm == NF_PROFILE : nm != NF_OFF) nfq = __ballot(qa) && !__ballot(st == ST_WAIT_SHADOW && qa);
+            if (PROF ? nm == NF_PROFILE : nm != NF_OFF) nfq = __ballot(qa) && !shq;
         }
-        const bool hit = closest_hit<false, STATS, FT, AXIS, PROF, BRUTE, HINT, NEAR>(SV(), bv, qa, q, b, wc, occl, lim,
-                                                                                     -1.0f, seed, hslot, nfq);
+        // One walk per query kind (closest_hit): any shadow lane sends the wave to the shadow walk.
+        bool hit;
+        if constexpr (HINT) {
+            if (shq) hit = closest_hit<false, STATS, FT, AXIS, PROF, BRUTE, QK_SHADOW>(SV(), bv, qa, q, b, wc, occl, lim,
+                                                                                     -1.0f, seed, hslot);
+            else hit = closest_hit<false, STATS, FT, AXIS, PROF, BRUTE, QK_NORMAL>(SV(), bv, qa, q, b, wc, -1.0f, INFINITY,
+                                                                                   -1.0f, 0, nullptr, nfq);
+        } else
+            hit = closest_hit<false, STATS, FT, AXIS, PROF, BRUTE, NEAR ? QK_NEAR : QK_ANY>(SV(), bv, qa, q, b, wc, occl, lim,
+                                                                                            -1.0f, 0, nullptr, nfq);
         if (HINT) {                                            // a normal query's first hit keys the wave's shadow queries
             const unsigned long long hm = __ballot(hit && st == ST_WAIT_NORMAL);
             if (hm) {

@@ -20,11 +20,20 @@ st = [i for i, l in enumerate(lines) if re.match(r'^_Z\S*' + pat + r'\S*:', l)][
 en = [i for i in range(st, len(lines)) if lines[i].startswith('.Lfunc_end')][0]
 depth, per = 0, collections.Counter()
 n_inst = 0
-for l in lines[st:en]:
-    m = re.match(r'^\.L(BB\d+_\d+):(.*)', l)
+for i in range(st, en):
+    l = lines[i]
+    m = re.match(r'^(?:\.LBB\d+_\d+:|; %bb\.\d+:)(.*)', l)
     if m:
-        d = re.search(r'Depth=(\d+)', m.group(2))
+        d = re.search(r'in Loop: Header=\S+ Depth=(\d+)', m.group(1))
         depth = int(d.group(1)) if d else 0
+        if not d:                                              # a loop header: its parents' lines, then its own depth
+            for j in range(i, min(i + 16, en)):
+                if j > i and not lines[j].lstrip().startswith(';'):
+                    break
+                h = re.search(r'This (?:Inner )?Loop Header: Depth=(\d+)', lines[j])
+                if h:
+                    depth = int(h.group(1))
+                    break
         continue
     s = l.strip()
     if not s or s.startswith(('.', ';')):
@@ -36,7 +45,32 @@ for l in lines[st:en]:
     if op == 'v_writelane_b32' and 'm0' not in s:
         per[(depth, 'save')] += 1
 print('instructions', n_inst)
-names = {0: 'kernel prologue/epilogue', 1: 'group loop', 2: 'state machine (per wave query)',
-         3: 'traversal step', 4: 'leaf / triangle loops', 5: 'inner loops'}
+# Loop names by depth relative to the traversal step, whose depth is read from the listing (the loop
+# whose header block reads a node record's child pair): the kernels differ in how many loops enclose
+# it (the hot kernel has a loop over sample rounds between the group loop and the state machine).
+step = None
+for i in range(st, en):
+    if 'ds_read_b64' in lines[i] and 'offset:48' in lines[i]:
+        for j in range(i, max(st, i - 40), -1):
+            m = re.search(r'This (?:Inner )?Loop Header: Depth=(\d+)', lines[j])
+            if m:
+                step = int(m.group(1))
+                break
+        if step is not None:
+            break
+rel = {-3: 'group loop', -2: 'sample rounds', -1: 'state machine (per wave query)', 0: 'traversal step',
+       1: 'leaf site', 2: 'triangle loop'}
+
+
+def name(d):
+    if d == 0:
+        return 'kernel prologue/epilogue'
+    if step is None:
+        return 'loop'
+    if d == 1 and step >= 3:
+        return 'group loop'
+    return rel.get(d - step, 'outer loop' if d < step else 'deeper loops')
+
+
 for (d, k), v in sorted(per.items()):
-    print('  depth %d %-32s %-8s %d (static)' % (d, names.get(d, 'deeper loops'), k, v))
+    print('  depth %d %-32s %-8s %d (static)' % (d, name(d), k, v))
