@@ -4,6 +4,7 @@
 //           [--width W --height H] [--out frame.ppm] [--debug X,Y] [--textures [ATLAS.png]]
 //           [--gpus N [--ranks R]] [--in-flight D] [--pick X,Y] [--accumulate N [--adaptive [THR]]]
 //           [--occlusion N [--radius R] [--interleave] [--filter] [--history [M] [--pan D]]]
+//           [--panorama WxH [--rays-out FILE]]
 //
 // -c config (worldN.json), -b benchmark (one timed frame, "Time: X ms" as main.cc:210-216),
 // -r unoptimize (brute force, no BVH), -d kernel dimension (accepted; the HIP path
@@ -38,7 +39,15 @@
 // rt_camera_translate) before every call but the first, so that every call after the first is a
 // move that keeps the samples by reprojection; prints the moves and the sample cursor after each
 // call, and --out writes the last frame.
+// --panorama WxH [--rays-out FILE] (build extension, rt_shade): an equirectangular view of W x H
+// pixels from the camera's position in the camera's axes -- pixel (x, y) looks along longitude
+// ((x + 0.5) / W - 0.5) 2 pi (0: forward, positive: to the right) and latitude (0.5 - (y + 0.5) / H) pi
+// (positive: up); the directions are formed here in double and rounded to float32, and shaded with
+// one rt_shade call in sorted order.  --out writes the frame, --rays-out the n * 6 float32 rays
+// (origin, direction as given) it shaded.  A camera model the frame path cannot produce.
 #include <hip/hip_runtime_api.h>
+
+#include <cmath>
 
 #include <algorithm>
 #include <chrono>
@@ -57,7 +66,7 @@ static void usage() {
                  "               [--out FILE.ppm] [--debug X,Y] [--textures [ATLAS.png]] [--gpus N [--ranks R]]\n"
                  "               [--in-flight D [--readback] [--overlap stream|half|full]] [--pick X,Y]\n"
                  "               [--accumulate N [--adaptive [THR]]] [--occlusion N [--radius R] [--interleave] [--filter]\n"
-                 "               [--history [M] [--pan D]]]\n");
+                 "               [--history [M] [--pan D]]] [--panorama WxH [--rays-out FILE]]\n");
 }
 
 static bool write_ppm(const char* path, const uint32_t* px, int w, int h) {
@@ -77,7 +86,8 @@ static bool write_ppm(const char* path, const uint32_t* px, int w, int h) {
 }
 
 int main(int argc, char** argv) {
-    std::string config, out;
+    std::string config, out, rays_out;
+    int pano_w = 0, pano_h = 0;
     bool bench = false, unopt = false, serial = false, textures = false, readback = false, adaptive = false, interleave = false, filter = false, history = false, pan_given = false;
     int max_history = RT_AO_HISTORY_DEFAULT;
     float pan = 0.05f;
@@ -138,6 +148,10 @@ int main(int argc, char** argv) {
             if (end == v || *end) { usage(); return 2; }
         }
         else if (a == "--readback") readback = true;
+        else if (a == "--panorama") {
+            if (std::sscanf(val("--panorama"), "%dx%d", &pano_w, &pano_h) != 2 || pano_w < 1 || pano_h < 1) { usage(); return 2; }
+        }
+        else if (a == "--rays-out") rays_out = val("--rays-out");
         else if (a == "--overlap") {
             overlap = val("--overlap");
             if (overlap != "stream" && overlap != "half" && overlap != "full") { usage(); return 2; }
@@ -164,6 +178,7 @@ int main(int argc, char** argv) {
     if ((interleave || filter) && occlusion < 1) { std::fprintf(stderr, "--interleave and --filter need --occlusion N\n"); usage(); return 2; }
     if (history && occlusion < 1) { std::fprintf(stderr, "--history needs --occlusion N\n"); usage(); return 2; }
     if (pan_given && !history) { std::fprintf(stderr, "--pan needs --history\n"); usage(); return 2; }
+    if (!rays_out.empty() && pano_w < 1) { std::fprintf(stderr, "--rays-out needs --panorama WxH\n"); usage(); return 2; }
     // frames in flight use a stream each: HIP maps streams round-robin onto GPU_MAX_HW_QUEUES
     // hardware queues (4 by default), and streams sharing a queue serialise.
     // The HIP runtime reads it when librt_amd.so's kernels are registered, before main: set it
@@ -200,6 +215,50 @@ int main(int argc, char** argv) {
         else std::printf("pick %d %d miss\n", pick_x, pick_y);
         rt_scene_free(handle);
         return 0;
+    }
+    if (pano_w > 0) {                                      // an equirectangular view, one rt_shade call
+        float pos[3], r[3], u[3], f[3];
+        rtamd_detail::check(rt_camera_get(handle, pos, nullptr), "rt_camera_get");
+        rtamd_detail::check(rt_camera_axes(handle, r, u, f), "rt_camera_axes");
+        const size_t n = (size_t)pano_w * pano_h;
+        const double pi = 3.14159265358979323846;
+        std::vector<float> rays(6 * n), origin(3 * n), dir(3 * n);
+        for (int y = 0; y < pano_h; y++)
+            for (int x = 0; x < pano_w; x++) {
+                const size_t i = (size_t)y * pano_w + x;
+                const double lon = ((x + 0.5) / pano_w - 0.5) * 2.0 * pi, lat = (0.5 - (y + 0.5) / pano_h) * pi;
+                const double cf = std::cos(lat) * std::cos(lon), cr = std::cos(lat) * std::sin(lon), cu = std::sin(lat);
+                for (int a = 0; a < 3; a++) {
+                    origin[3 * i + a] = pos[a];
+                    dir[3 * i + a] = (float)(cf * (double)f[a] + cr * (double)r[a] + cu * (double)u[a]);
+                    rays[6 * i + a] = origin[3 * i + a]; rays[6 * i + 3 + a] = dir[3 * i + a];
+                }
+            }
+        std::vector<uint32_t> frame(n);
+        rt_shade_opts o;
+        rt_shade_opts_default(&o);
+        o.n = (int64_t)n; o.origin = origin.data(); o.dir = dir.data(); o.host = 1;
+        o.use_bvh = unopt ? 0 : 1; o.textures = textures ? 1 : 0; o.order = RT_QUERY_ORDER_SORTED;
+        o.rgba = frame.data();
+        auto from = std::chrono::high_resolution_clock::now();
+        if (rt_shade(handle, &o) != RT_OK) {
+            std::fprintf(stderr, "panorama failed: %s\n", rt_last_error());
+            rt_scene_free(handle);
+            return 1;
+        }
+        auto to = std::chrono::high_resolution_clock::now();
+        if (bench) std::printf("Time: %g ms\n", std::chrono::duration<double, std::milli>(to - from).count());
+        std::printf("Panorama: %d x %d, %lld rays\n", pano_w, pano_h, (long long)n);
+        bool ok = out.empty() || write_ppm(out.c_str(), frame.data(), pano_w, pano_h);
+        if (!ok) std::fprintf(stderr, "cannot write %s\n", out.c_str());
+        if (ok && !rays_out.empty()) {
+            FILE* fr = std::fopen(rays_out.c_str(), "wb");
+            ok = fr && std::fwrite(rays.data(), sizeof(float), rays.size(), fr) == rays.size();
+            if (fr) ok = (std::fclose(fr) == 0) && ok;
+            if (!ok) std::fprintf(stderr, "cannot write %s\n", rays_out.c_str());
+        }
+        rt_scene_free(handle);
+        return ok ? 0 : 1;
     }
     if (occlusion > 0) {                                   // the ambient-occlusion pass, one call
         int32_t info[10];

@@ -196,6 +196,21 @@ struct QueryParams {
     const uint32_t* order;                      // ORD kernels: lane l of chunk c traces ray order[64 c + l] (a permutation of [0, n))
 };
 
+// shade_kernel's third argument (rt_shade), after the TraceParams and the SceneView the integrator
+// reads in place: n caller-supplied rays (origin / dir, as QueryParams') or the camera's rays of
+// sample `sample` of n pixels, and the per-ray outputs, each optional.  Device pointers.
+struct ShadeParams {
+    rt::DCamera cam;          // pixel mode: camera_at
+    long long n;
+    const float* origin; const float* dir;      // [3n]
+    const int* pixel;                           // [2n] (x, y), or null
+    int sample, pad;                            // pixel mode: the frame's sample k (spp_offset_dev), uniform per call
+    float4* radiance;                           // [n] the integrator's unclamped sum (miss, rejected ray: zeros)
+    uint32_t* rgba;                             // [n] pack(clamp1(radiance)) (rt_accum.h)
+    float* rays_out;                            // [6n] origin, normalised direction
+    const uint32_t* order;                      // non-null: lane l of chunk c shades ray order[64 c + l] (a permutation of [0, n))
+};
+
 // The ambient-occlusion kernels' arguments (rt_occlusion): occl_surface_kernel (cam -> surf),
 // occlusion_kernel (surf, table -> count and, resolving, the outputs) and occl_rays_kernel (the
 // test hook: sample k0's rays -> rays); occlusion_il_kernel / occl_rays_il_kernel are theirs in the
@@ -269,6 +284,13 @@ hipError_t launch_query_kernel(const QueryVariant& v, QueryParams& Q, SceneView&
 // ray_key_kernel (RT_QUERY_ORDER_SORTED): keys[i] = ray_key of ray i of the batch as query_kernel
 // would trace it (Q's origin / dir or pixel and camera) in `box`, idx[i] = i.
 hipError_t launch_ray_keys(QueryParams& Q, const rtk::KeyBox& box, unsigned long long* keys, uint32_t* idx, hipStream_t st);
+// The shade kernel for a batch (rt_shade): shade_plan's key looked up in the table of shade kernels
+// (null fn: no kernel with this key, a programming error) and its launch.  P: the fields
+// trace_sample reads (rt_shade.cpp lists them); S: caller_ray_view's scene.
+struct ShadeVariant : ShadeKey { const void* fn; };
+ShadeVariant choose_shade_variant(long long n_rays, const SceneView& S, int ns, bool tex);
+hipError_t launch_shade_kernel(const ShadeVariant& v, TraceParams& P, SceneView& S, ShadeParams& Q, hipStream_t st,
+                               hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
 // The single-workgroup BVH build (A.n <= BVH_WG_LEAVES) with `lds` bytes of dynamic LDS.
 hipError_t launch_bvh_build(rtb::BvhArgs& A, bool lds_tree, size_t lds, hipStream_t st, hipEvent_t e0, hipEvent_t e1);
 size_t scene_image_bytes(const SceneView& S);   // the scene image a fast kernel's block stages in LDS

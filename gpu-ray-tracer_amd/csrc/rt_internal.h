@@ -1,6 +1,6 @@
 // rt_internal.h — the scene object and what the host translation units share: rt_runtime.cpp
 // (upload, frame slots, BVH build and trace launch, rt_render), rt_build.cpp (scene creation,
-// exports, camera), rt_accumulate.cpp, rt_occlusion.cpp, rt_query.cpp (one entry family each),
+// exports, camera), rt_accumulate.cpp, rt_occlusion.cpp, rt_query.cpp, rt_shade.cpp (one entry family each),
 // rt_hooks.cpp (debugging, profiling and test hooks), rt_multi.cpp (multi-device frames) and
 // rt_copy.cpp (copy-engine entries).  Internal functions live in namespace rti: the
 // library's rt_* C symbols (rt_amd.h) stay its only interface.
@@ -174,6 +174,15 @@ struct rt_scene {
         const uint32_t* last_order = nullptr;
         void release() { rti::dfree(dev); rti::hfree(host); rti::dfree(qo_dev); cap = 0; qo_rays = 0; qo_temp = 0; last_order = nullptr; }
     } query;
+    struct Shade {
+        // rt_shade with host pointers: its own pinned image of the batch and device copy, as Query's
+        unsigned char* host = nullptr; unsigned char* dev = nullptr; size_t cap = 0;
+        // the most recent rt_shade (rt_shade_last): its kernel and launch, whether the batch was sorted, its size
+        rtd::ShadeVariant last{};
+        bool has_last = false, last_sorted = false;
+        long long last_n = 0;
+        void release() { rti::dfree(dev); rti::hfree(host); cap = 0; }
+    } shade;
     std::vector<hipEvent_t> tev;    // timing=1 events, 4 per frame: bvh start/stop, trace start/stop (pool)
     size_t tev_used = 0;
     size_t d_out_px = 0;
@@ -344,6 +353,15 @@ int clear_stats(rt_scene* s, hipStream_t st);
 int read_frame_stats(rt_scene* s, rt_stats* stats);
 std::vector<rtm::Box> mesh_boxes(const rt::Scene& h);
 int warm_scene(rt_scene* s);
+int scene_atlas(rt_scene* s);     // the atlas texels on the device, as a textured trace launch ensures them (RT_ERR_STATE without an atlas)
+// rt_query.cpp: the coherence sort's pieces, shared with rt_shade.cpp.  refresh_query_box: the keys'
+// quantisation box (rt_scene::Query::box) for the current poses.  ensure_order_scratch: the scene's
+// sort scratch for a batch of n rays (query_order_plan's layout at the capacity, then hipCUB's
+// temporary storage); `who` names the entry in the error text.  sort_rays: key, sort, index on `st`
+// for the batch Q describes; the device array of the batch's order (in the scene's scratch).
+void refresh_query_box(rt_scene* s);
+int ensure_order_scratch(rt_scene* s, long long n, const char* who);
+int sort_rays(rt_scene* s, rtd::QueryParams& Q, int key_bits, hipStream_t st, const uint32_t** order);
 // rt_multi.cpp
 int render_multi(rt_scene* s, const rt_render_opts* o, rt_stats* stats);
 void free_multi(rt_scene* s);

@@ -2429,6 +2429,80 @@ __global__ __launch_bounds__(KEY_BLOCK) void ray_key_kernel(QueryParams Q, rtk::
 }
 
 // ---------------------------------------------------------------------------
+// Shading caller-supplied rays (rt_shade): the integrator (trace_sample) for rays
+// the caller forms, or for the camera's rays of one sample of given pixels.  query_kernel's small
+// form: 256-thread blocks, one ray per lane, wave c of the grid takes rays 64 c .. 64 c + 63 (with
+// an order: the rays order[64 c .. 64 c + 63]), tail lanes inactive, nothing staged.  The rays are
+// formed and accepted as query_kernel forms and accepts them; a rejected ray is inactive from the
+// start and its radiance is the integrator's initial zero.  The sample runs unparked and uncounted
+// (no LDS, no counters), with the scene as rt_query's (camera-ray shortcuts, hints and near-first
+// off), so its radiance is what trace_kernel computes for the same ray.
+// trace_sample, hit_kd and dbg read the launch's TraceParams and SceneView in place from the
+// kernel-argument segment (kparams(), kscene()): they are this kernel's first two arguments, as
+// trace_kernel's, and ShadeParams follows them, read in place as well.
+// The order is a wave-uniform run-time branch, not a template parameter (trace_sample is large).
+// ---------------------------------------------------------------------------
+typedef __attribute__((address_space(4))) const ShadeParams KSP;
+static_assert((sizeof(TraceParams) + sizeof(SceneView)) % alignof(ShadeParams) == 0 && sizeof(TraceParams) + sizeof(SceneView) == 552,
+              "ShadeParams follows TraceParams and SceneView in the kernarg segment");
+__device__ __forceinline__ KSP& sparams() {
+    const __attribute__((address_space(4))) char* p =
+        (const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return *(KSP*)(p + sizeof(TraceParams) + sizeof(SceneView));   // the third kernel argument
+}
+
+template <int NS, int TREE, bool TEX>
+__global__ __launch_bounds__(SHADE_BLOCK) void shade_kernel(TraceParams P_arg, SceneView S, ShadeParams Q_arg) {
+    (void)P_arg; (void)Q_arg;                                  // read in place: kparams(), sparams()
+    constexpr bool FT = TREE == QT_ORDERED, BRUTE = TREE == QT_BRUTE;
+    const BvhRefs bv = stage_bvh<false, FT, false, BRUTE>(S, nullptr);
+    const int lane = threadIdx.x & 63;
+    const long long c = (long long)blockIdx.x * (SHADE_BLOCK / 64) + (long long)(threadIdx.x >> 6);   // this wave's chunk
+    const long long slot = c * 64 + lane;
+    const bool in = slot < sparams().n;
+    long long i = slot;
+    if (sparams().order != nullptr && in) i = (long long)sparams().order[slot];   // the sorted batch: this slot's ray
+    Ray r{v3(0, 0, 0), v3(0, 0, 1)};
+    bool ok = in;
+    if (in) {
+        KSP& Q = sparams();
+        if (Q.pixel) {                                         // the camera's ray of sample k (trace_kernel's primary)
+            const float2 o = spp_offset_dev(Q.sample);
+            r = camera_at(kld(Q.cam), (float)Q.pixel[2 * i] + o.x, (float)Q.pixel[2 * i + 1] + o.y);
+        } else {
+            const V3 o = v3(Q.origin[3 * i], Q.origin[3 * i + 1], Q.origin[3 * i + 2]);
+            const V3 d = v3(Q.dir[3 * i], Q.dir[3 * i + 1], Q.dir[3 * i + 2]);
+            r = make_ray(o, d);                                // Ray ctor (geometry.h:216)
+            ok = rtk::finite3(d);
+        }
+        ok = ok && rtk::ray_traceable(r);                      // (rtk::caller_ray's value, as query_kernel)
+        if (Q.rays_out) {
+            float* ro = Q.rays_out + 6 * i;
+            ro[0] = r.o.x; ro[1] = r.o.y; ro[2] = r.o.z; ro[3] = r.d.x; ro[4] = r.d.y; ro[5] = r.d.z;
+        }
+        if (!ok) r = Ray{v3(0, 0, 0), v3(0, 0, 1)};            // nothing non-finite enters the wave's arithmetic
+    }
+    WaveCounters wc{0, 0, 0, 0};
+    int nq = 0;
+    // unparked, uncounted, no axis-plane path, no profiling: one sample per lane, no hit ids, no debug pixel
+    const V4 acc = trace_sample<NS, false, false, TEX, FT, false, false, BRUTE, false>(S, bv, ok, r, false, false, 0, wc, nullptr, nq);
+    if (in) {
+        KSP& Q = sparams();
+        long long j = slot;                                    // the ray's own index, read again (not held across the trace)
+        if (Q.order != nullptr) j = (long long)Q.order[slot];
+        // the 1-spp frame's resolve (rt_accum.h): the sums of one sample, raw and clamped, and their mean
+        V4 sum_r = v4(0, 0, 0, 0), sum_c = v4(0, 0, 0, 0);
+        rta::fold(sum_r, sum_c, acc);
+        if (Q.radiance) {
+            const V4 m = rta::resolve_radiance(sum_r, 1);
+            Q.radiance[j] = make_float4(m.x, m.y, m.z, m.w);
+        }
+        if (Q.rgba) Q.rgba[j] = rta::resolve_rgba(sum_c, 1);
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Ambient occlusion (rt_occlusion; rt_occl.h): how much of the hemisphere above
 // every pixel's primary hit is unoccluded within a radius.  Three kernels beside the query
 // kernels, none of which touches them: the surface record once per accumulation, the occlusion
@@ -3237,6 +3311,30 @@ hipError_t launch_query_kernel(const QueryVariant& v, QueryParams& Q, SceneView&
 hipError_t launch_ray_keys(QueryParams& Q, const rtk::KeyBox& box, unsigned long long* keys, uint32_t* idx, hipStream_t st) {
     hipLaunchKernelGGL(ray_key_kernel, dim3((unsigned)((Q.n + KEY_BLOCK - 1) / KEY_BLOCK)), dim3(KEY_BLOCK), 0, st, Q, box, keys, idx);
     return hipGetLastError();
+}
+
+// The shade kernels (rt_shade): every instantiation of shade_kernel, named here once.  shade_plan
+// (rt_plan.h) decides which of them a batch gets.
+struct ShadeEntry { int ns, tree; bool tex; const void* fn; };
+#define SK(NS, TREE, TEX) ShadeEntry{NS, TREE, TEX, (const void*)shade_kernel<NS, TREE, TEX>}
+#define SK4(TREE) SK(0, TREE, false), SK(0, TREE, true), SK(NG, TREE, false), SK(NG, TREE, true)
+static const ShadeEntry shade_kernels[] = {SK4(QT_ORDERED), SK4(QT_HEAP), SK4(QT_BRUTE)};
+#undef SK4
+#undef SK
+static_assert(sizeof shade_kernels / sizeof *shade_kernels == 12, "the shade kernels of the build");
+
+ShadeVariant choose_shade_variant(long long n_rays, const SceneView& S, int ns, bool tex) {
+    ShadeVariant v{};
+    static_cast<ShadeKey&>(v) = shade_plan(n_rays, S, ns, tex);
+    for (const ShadeEntry& e : shade_kernels)
+        if (e.ns == v.ns_bucket && e.tree == v.tree && e.tex == v.tex) v.fn = e.fn;
+    return v;
+}
+
+hipError_t launch_shade_kernel(const ShadeVariant& v, TraceParams& P, SceneView& S, ShadeParams& Q, hipStream_t st,
+                               hipEvent_t e0, hipEvent_t e1) {
+    void* args[] = {&P, &S, &Q};
+    return hipExtLaunchKernel(v.fn, dim3(v.blocks), dim3(v.block), args, 0, st, e0, e1, 0);
 }
 
 hipError_t launch_sky(bool brute, int blocks, TraceParams& P, SceneView& S, unsigned char* gsky, int* live,

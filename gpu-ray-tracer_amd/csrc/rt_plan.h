@@ -383,6 +383,29 @@ inline QueryKey query_plan(long long n_rays, const SceneView& S, bool any_hit, b
     return k;
 }
 
+// ---- Shading caller-supplied rays (rt_shade): which shade_kernel a batch gets
+// The tree form is query_plan's rule for an uncounted query; the form is query_plan's small one only
+// (256-thread blocks over ceil(n / 256) blocks, one ray per lane, nothing staged: DESIGN §3.5 found
+// no crossover to the persistent form).  ns: shade_shortcuts' suspended frames; the NS = 0 kernels
+// (no frame stack) are for scenes without a refractive material only, as the trace plan's, and
+// every other scene takes the generic depth MAX_FRAMES - 1.
+constexpr int SHADE_BLOCK = QUERY_BLOCK_SMALL;
+struct ShadeKey {
+    int tree;                 // QT_*
+    int ns_bucket;            // 0 or MAX_FRAMES - 1
+    bool tex;                 // the textured integrator (hit_kd)
+    int block, blocks;        // the launch: dim3(blocks), dim3(block)
+};
+inline ShadeKey shade_plan(long long n_rays, const SceneView& S, int ns, bool tex) {
+    ShadeKey k{};
+    k.tree = query_plan(n_rays, S, false, false, 0, 0).tree;
+    k.ns_bucket = ns == 0 ? 0 : MAX_FRAMES - 1;
+    k.tex = tex;
+    k.block = SHADE_BLOCK;
+    k.blocks = (int)std::max(1ll, std::min((n_rays + SHADE_BLOCK - 1) / SHADE_BLOCK, (long long)INT32_MAX));
+    return k;
+}
+
 // ---- The ambient-occlusion pass (rt_occlusion): its kernels' tree form and grid
 // The tree form is query_plan's rule; the form is the small one only (256-thread blocks, nothing
 // staged: DESIGN §3.5 found no crossover to the persistent form).  One pixel per lane; a wave takes

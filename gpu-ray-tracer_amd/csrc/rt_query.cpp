@@ -12,13 +12,11 @@ using namespace rtd;
 using namespace rti;
 using rt::DInst;
 
-namespace {
-
 // The quantisation box of rt_query's coherence keys (rt_raykey.h): the instances' world boxes
 // (bvh_inst_box's arithmetic: the mesh box moved by the instance pose) merged, on the host,
 // for the current poses; the same box with and without the BVH.  Degenerate and non-finite
 // boxes are left out (no box at all: zeros, every origin in cell 0).
-void refresh_query_box(rt_scene* s) {
+void rti::refresh_query_box(rt_scene* s) {
     rt_scene::Query& qs = s->query;
     if (qs.box_gen == s->inst_gen) return;
     const std::vector<Box> mbox = mesh_boxes(s->h);
@@ -38,7 +36,7 @@ void refresh_query_box(rt_scene* s) {
 // The sorted mode's scratch for a batch of n rays (query_order_plan's layout at the capacity,
 // then hipCUB's temporary storage, whose size is asked once per capacity).  A failed allocation
 // leaves the scene without scratch, otherwise as it was.
-int ensure_order_scratch(rt_scene* s, long long n) {
+int rti::ensure_order_scratch(rt_scene* s, long long n, const char* who) {
     rt_scene::Query& qs = s->query;
     if (n <= qs.qo_rays) return RT_OK;
     const long long cap = std::min<long long>(std::max(n, 2 * qs.qo_rays), INT32_MAX);
@@ -48,14 +46,30 @@ int ensure_order_scratch(rt_scene* s, long long n) {
     qs.last_order = nullptr;                                   // (rt_query_last: the last order went with the buffer)
     if (hipMalloc((void**)&qs.qo_dev, P.scratch_bytes + temp) != hipSuccess) {
         qs.qo_dev = nullptr;
-        return fail(RT_ERR_HIP, std::string("rt_query: no memory for the sort of ") + std::to_string(n) + " rays: " +
+        return fail(RT_ERR_HIP, std::string(who) + ": no memory for the sort of " + std::to_string(n) + " rays: " +
                                     hipGetErrorString(hipGetLastError()));
     }
     qs.qo_rays = cap; qs.qo_temp = temp;
     return RT_OK;
 }
 
-}  // namespace
+// Key, sort, index: stream-ordered, no host synchronisation between them.  The buffers are laid out
+// for the scratch's capacity (ensure_order_scratch came first); the sort looks at the key bits in
+// use only.
+int rti::sort_rays(rt_scene* s, QueryParams& Q, int key_bits, hipStream_t st, const uint32_t** order) {
+    rt_scene::Query& qs = s->query;
+    refresh_query_box(s);
+    const QueryOrderPlan CP = query_order_plan(qs.qo_rays, QUERY_ORDER_SORTED, false);
+    unsigned char* p = qs.qo_dev;
+    unsigned long long* k_in = (unsigned long long*)p; p += CP.keys_bytes;
+    unsigned long long* k_out = (unsigned long long*)p; p += CP.keys_bytes;
+    uint32_t* v_in = (uint32_t*)p; p += CP.idx_bytes;
+    uint32_t* v_out = (uint32_t*)p; p += CP.idx_bytes;
+    HIPCHK(launch_ray_keys(Q, qs.box, k_in, v_in, st));
+    HIPCHK(ray_sort_pairs(p, qs.qo_temp, k_in, k_out, v_in, v_out, Q.n, key_bits, st));
+    *order = v_out;
+    return RT_OK;
+}
 
 extern "C" {
 
@@ -94,7 +108,7 @@ int rt_query(rt_scene* s, const rt_query_opts* o, rt_stats* stats) {
     const bool counted = stats != nullptr;
     // the sorted mode's scratch, before anything of this call is in flight
     const QueryOrderPlan OP = query_order_plan(o->n, qs.order, counted);
-    if (OP.sort && (r = ensure_order_scratch(s, o->n)) != RT_OK) return r;
+    if (OP.sort && (r = ensure_order_scratch(s, o->n, "rt_query")) != RT_OK) return r;
     if (counted) { HIPCHK(hipMemsetAsync(s->d_stats, 0, STATS_N * sizeof(unsigned long long), st)); HIPCHK(hipEventRecord(s->ev[0], st)); }
     if (s->builds_bvh(o->use_bvh, o->rebuild_bvh) && (r = build_bvh(s, st)) != RT_OK) return r;
     if (counted) HIPCHK(hipEventRecord(s->ev[1], st));
@@ -149,18 +163,8 @@ int rt_query(rt_scene* s, const rt_query_opts* o, rt_stats* stats) {
                                       std::to_string((int)V.ordered) + ">");
     bool trace = true;
     if (OP.sort) {
-        // key, sort, trace: stream-ordered, no host synchronisation between them.  The buffers
-        // are laid out for the scratch's capacity; the sort looks at the key bits in use only.
-        refresh_query_box(s);
-        const QueryOrderPlan CP = query_order_plan(qs.qo_rays, QUERY_ORDER_SORTED, false);
-        unsigned char* p = qs.qo_dev;
-        unsigned long long* k_in = (unsigned long long*)p; p += CP.keys_bytes;
-        unsigned long long* k_out = (unsigned long long*)p; p += CP.keys_bytes;
-        uint32_t* v_in = (uint32_t*)p; p += CP.idx_bytes;
-        uint32_t* v_out = (uint32_t*)p; p += CP.idx_bytes;
-        HIPCHK(launch_ray_keys(Q, qs.box, k_in, v_in, st));
-        HIPCHK(ray_sort_pairs(p, qs.qo_temp, k_in, k_out, v_in, v_out, o->n, OP.key_bits, st));
-        Q.order = v_out;
+        // key, sort, trace: stream-ordered, no host synchronisation between them
+        if ((r = sort_rays(s, Q, OP.key_bits, st, &Q.order)) != RT_OK) return r;
         // RT_QUERY_SORT_ONLY (measurements, tools/query_bench.py): stop after the sort; no output is written
         if (const char* e = getenv("RT_QUERY_SORT_ONLY")) trace = atoi(e) == 0;
     }

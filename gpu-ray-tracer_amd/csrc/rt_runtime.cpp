@@ -604,6 +604,8 @@ CallerView rti::caller_ray_view(const rt_scene* s, bool use_bvh) {
     return c;
 }
 
+int rti::scene_atlas(rt_scene* s) { return ensure_atlas(s); }
+
 // Fill TraceParams from the launch plan (rt_plan.h), ensure the slot's buffers, launch.
 int rti::launch_trace(rt_scene* s, const rt_render_opts& o, const TraceRequest& q) {
     hipStream_t st = q.stream;
@@ -763,6 +765,7 @@ rt_scene::~rt_scene() {
     dfree(d_mesh_box); dfree(d_spp); dfree(d_stats); dfree(d_hint); dfree(d_canvas); dfree(d_dbg);
     for (auto& p : d_out) dfree(p);
     query.release();
+    shade.release();
     accum.release();
     occl.release();
     for (auto& e : ev) if (e) (void)hipEventDestroy(e);

@@ -43,7 +43,7 @@ SYMBOLS = [
     "rt_scene_atlas_info", "rt_scene_set_frame_slots", "rt_scene_set_overlap", "rt_frame_work",
     "rt_scene_set_devices", "rt_profile_marker", "rt_host_alloc", "rt_host_free", "rt_copy_to_host_async",
     "rt_copy_engines_warm", "rt_scene_last_trace", "rt_query_opts_default", "rt_query",
-    "rt_query_set_order", "rt_query_last",
+    "rt_query_set_order", "rt_query_last", "rt_shade_opts_default", "rt_shade", "rt_shade_last",
     "rt_accum_opts_default", "rt_accumulate", "rt_accumulate_reset", "rt_accumulate_info",
     "rt_accumulate_set_adaptive", "rt_accumulate_adaptive_info", "rt_accumulate_pass_fill", "rt_accumulate_pass_read",
     "rt_scene_history_info",
@@ -107,6 +107,18 @@ class QueryOpts(ctypes.Structure):
 # rt_query's outputs: name -> (components per ray, dtype)
 QUERY_OUTPUTS = {"t": (1, np.float32), "inst": (1, np.int32), "tri": (1, np.int32), "uv": (2, np.float32),
                  "normal": (3, np.float32), "hit": (1, np.uint8), "rays_out": (6, np.float32)}
+
+
+class ShadeOpts(ctypes.Structure):
+    _fields_ = [("n", ctypes.c_int64), ("origin", ctypes.c_void_p), ("dir", ctypes.c_void_p), ("pixel", ctypes.c_void_p),
+                ("sample", ctypes.c_int), ("use_bvh", ctypes.c_int), ("rebuild_bvh", ctypes.c_int),
+                ("textures", ctypes.c_int), ("order", ctypes.c_int), ("host", ctypes.c_int),
+                ("radiance", ctypes.c_void_p), ("rgba", ctypes.c_void_p), ("rays_out", ctypes.c_void_p)]
+
+
+# rt_shade's outputs: name -> (components per ray, dtype)
+SHADE_OUTPUTS = {"radiance": (4, np.float32), "rgba": (1, np.uint32), "rays_out": (6, np.float32)}
+SHADE_TREES = {0: "ordered", 1: "heap", 2: "brute"}         # rt_shade_last's TREE
 
 
 class Stats(ctypes.Structure):
@@ -239,6 +251,11 @@ def lib():
     if hasattr(L, "rt_query_set_order"):        # (absent from libraries before the coherence sort: A/B runs)
         L.rt_query_set_order.argtypes = [vp, ip]
         L.rt_query_last.argtypes = [vp, vp, vp, vp, ctypes.c_int64]
+    if hasattr(L, "rt_shade"):                  # (absent from libraries before rt_shade: A/B runs)
+        L.rt_shade_opts_default.argtypes = [ctypes.POINTER(ShadeOpts)]
+        L.rt_shade_opts_default.restype = None
+        L.rt_shade.argtypes = [vp, ctypes.POINTER(ShadeOpts)]
+        L.rt_shade_last.argtypes = [vp, vp]
     if hasattr(L, "rt_profile_marker"):         # (absent from libraries older than ABI 3's round 5: A/B runs)
         L.rt_profile_marker.argtypes = [ip, vp]
     if hasattr(L, "rt_copy_to_host_async"):     # ABI 4
@@ -874,6 +891,57 @@ class Scene:
         st = Stats()
         self._query(o, st if stats else None, reorder)
         return st.as_dict() if stats else None
+
+    # ---- shading caller-supplied rays (rt_shade) ----
+    def shade(self, origins=None, dirs=None, pixels=None, sample=0, textures=False, use_bvh=True, rebuild_bvh=True,
+              reorder=False, want=("radiance",)):
+        """What each ray sees (rt_shade): the integrator's radiance along caller-supplied rays, origins /
+        dirs (n, 3), or along the camera's rays of sample `sample` of pixels (n, 2).  Returns a dict of
+        numpy arrays, one per name in `want` (SHADE_OUTPUTS).  reorder=True: this call sorts the batch
+        into coherent waves on the device first (RT_QUERY_ORDER_SORTED); the arrays are the same."""
+        o = ShadeOpts()
+        lib().rt_shade_opts_default(ctypes.byref(o))
+        keep = []
+        if pixels is not None:
+            keep.append(np.ascontiguousarray(pixels, dtype=np.int32).reshape(-1, 2))
+            o.pixel, n = _ptr(keep[-1]), keep[-1].shape[0]
+        if origins is not None:
+            keep.append(_f(origins).reshape(-1, 3))
+            o.origin, n = _ptr(keep[-1]), keep[-1].shape[0]
+        if dirs is not None:
+            keep.append(_f(dirs).reshape(-1, 3))
+            o.dir, n = _ptr(keep[-1]), keep[-1].shape[0]
+        if not keep:
+            raise RtError(RT_ERR_ARG, "shade: give origins and dirs, or pixels")
+        assert all(a.shape[0] == n for a in keep), "origins and dirs differ in length"
+        o.n, o.sample, o.textures, o.use_bvh, o.rebuild_bvh = n, int(sample), int(textures), int(use_bvh), int(rebuild_bvh)
+        o.order, o.host = (RT_QUERY_ORDER_SORTED if reorder else RT_QUERY_ORDER_CALLER), 1
+        out = {}
+        for k in want:
+            c, dt = SHADE_OUTPUTS[k]
+            out[k] = np.zeros((n, c) if c > 1 else (n,), dt)
+            setattr(o, k, _ptr(out[k]))
+        _check(lib().rt_shade(self._h, ctypes.byref(o)))
+        return out
+
+    def shade_device(self, n, origin_ptr=None, dir_ptr=None, pixel_ptr=None, sample=0, textures=False, use_bvh=True,
+                     rebuild_bvh=True, reorder=False, radiance_ptr=None, rgba_ptr=None, rays_out_ptr=None):
+        """rt_shade on caller-owned DEVICE buffers (e.g. torch tensors' data_ptr()): float32 origins /
+        dirs / radiance / rays_out, int32 pixels, uint32 rgba.  Returns when the results are written."""
+        o = ShadeOpts()
+        lib().rt_shade_opts_default(ctypes.byref(o))
+        o.n, o.origin, o.dir, o.pixel, o.sample = int(n), origin_ptr, dir_ptr, pixel_ptr, int(sample)
+        o.textures, o.use_bvh, o.rebuild_bvh, o.host = int(textures), int(use_bvh), int(rebuild_bvh), 0
+        o.order = RT_QUERY_ORDER_SORTED if reorder else RT_QUERY_ORDER_CALLER
+        o.radiance, o.rgba, o.rays_out = radiance_ptr, rgba_ptr, rays_out_ptr
+        _check(lib().rt_shade(self._h, ctypes.byref(o)))
+
+    def shade_last(self):
+        """The scene's most recent rt_shade (rt_shade_last): its kernel's NS / TREE / TEX, whether the
+        batch was sorted, the grid and the batch size."""
+        v = np.zeros(8, np.int32)
+        _check(lib().rt_shade_last(self._h, _ptr(v)))
+        return dict(zip(["ns", "tree", "tex", "sorted", "blocks", "n"], [int(x) for x in v[:6]]))
 
     def pick(self, x, y):
         """The instance under pixel (x, y): (inst, tri, t) of the camera's sample-0 ray, or

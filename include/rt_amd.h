@@ -42,7 +42,9 @@ extern "C" {
  *    (still 5: additive -- rt_occlusion_set_pattern / rt_occlusion_set_filter / rt_occlusion_config
  *    and the measurement hook rt_occlusion_filter_timing; rt_occlusion_opts keeps its layout, both switches are scene state)
  *    (still 5: additive -- rt_occlusion_set_history / rt_occlusion_history_info, the test hook
- *    rt_occlusion_history_weights and the measurement hook rt_occlusion_history_timing; scene state) */
+ *    rt_occlusion_history_weights and the measurement hook rt_occlusion_history_timing; scene state)
+ *    (still 5: additive -- rt_shade / rt_shade_opts_default and the test hook rt_shade_last; no
+ *    existing entry or struct changed) */
 #define RT_ABI_VERSION 5
 
 enum {
@@ -358,6 +360,63 @@ int rt_query_set_order(rt_scene* s, int mode);
  * (copied from the device; nothing is written if the batch was not sorted).  Each may be NULL.
  * RT_ERR_STATE before the first rt_query; RT_ERR_ARG if order_cap < n. */
 int rt_query_last(const rt_scene* s, int32_t out8[8], float bounds6[6], uint32_t* order, int64_t order_cap);
+
+/* ---- shading caller-supplied rays: what a ray sees (build-defined; the reference has no counterpart) ----
+ * The reference's integrator (propagate_ray, scene.cu:92-188) is reachable only for the rays of its
+ * one pinhole camera.  This entry runs it for a batch of rays from anywhere: each ray's result is
+ * what propagate_ray returns for it as a primary ray, with the depth, environment, lights and
+ * materials of the scene as rt_env_set left them.  `radiance` is that unclamped sum and `rgba` its
+ * 8-bit encoding as a 1-sample frame's (each channel clamped to 1, then truncated).  A ray that
+ * misses, and a ray rt_query would reject (a non-finite component, a direction that normalises to
+ * the zero vector), give (0, 0, 0, 0) and that value packed.
+ * Pixel mode (`pixel`, with `sample` = k): the camera's ray of sample k of each pixel, offset as
+ * rt_spp_offset(k), so the result is the radiance of sample k of rt_render; with k = 0 it is
+ * rt_render(spp = 1)'s radiance and rgba, bit for bit, and `rays_out` is rt_query's.
+ * A side entry like rt_query: it runs on the scene's own stream after the frames in flight, rotates
+ * no frame slot, launches no trace kernel (rt_scene_last_trace, the scheduling history, the hint
+ * table and the hint and near-first counters are untouched), builds the BVH at most once and
+ * returns when the outputs are complete.  A call that builds the tree (rebuild_bvh = 1, or no valid
+ * tree yet) leaves the build's own note behind, as rt_query's build does: the history slot the
+ * build zeroes for the next frame (rt_scene_history_info's second value), which that frame
+ * clears; a call on the frames' tree (rebuild_bvh = 0) changes no value rt_scene_history_info
+ * reports.  A scene split by rt_scene_set_devices answers on its own device.
+ * order = RT_QUERY_ORDER_SORTED, per call: the batch is keyed, sorted and indexed exactly as
+ * rt_query's sorted mode (pixel mode: by the pixels' sample-0 rays) and every output is written at
+ * the ray's own index, so the arrays are RT_QUERY_ORDER_CALLER's bit for bit; batches of n <= 64
+ * run in caller order.  The sort uses the scene's sort scratch, the one rt_query's sorted mode
+ * uses: a sorted rt_shade clears the order rt_query_last would copy out (that call then reports
+ * RT_ERR_STATE for `order` until the next sorted rt_query), so rt_query_last never hands out an
+ * order an rt_shade call wrote.
+ * host = 1: every pointer is host memory, staged through one pinned image owned by the scene that
+ * grows on demand and is freed with it; if it cannot be allocated the call returns RT_ERR_HIP and
+ * the scene stays usable. */
+typedef struct rt_shade_opts {
+    int64_t n;              /* rays */
+    const float* origin;    /* n*3 */
+    const float* dir;       /* n*3, any length > 0: normalised as rmath::Ray(o, d) does */
+    const int32_t* pixel;   /* n*2 (x, y): the camera's ray of sample `sample` of that pixel; exclusive with origin/dir */
+    int sample;             /* pixel mode: k >= 0 */
+    int use_bvh, rebuild_bvh, textures;   /* as rt_render_opts */
+    int order;              /* RT_QUERY_ORDER_CALLER (default) or RT_QUERY_ORDER_SORTED, for this call */
+    int host;               /* 1: every pointer is host memory (staged); 0: device pointers */
+    /* outputs, each may be NULL */
+    float* radiance;        /* n*4 */
+    uint32_t* rgba;         /* n */
+    float* rays_out;        /* n*6: origin and normalised direction the kernel shaded */
+} rt_shade_opts;
+/* zeros, use_bvh = rebuild_bvh = 1 */
+void rt_shade_opts_default(rt_shade_opts* o);
+/* Checked before any device work -- RT_ERR_ARG: null opts, n < 0, neither pixel nor both of origin
+ * and dir, pixel together with either, sample < 0, no output requested, an unknown order, and with
+ * host = 1 a pixel outside the canvas (device pixels are the caller's to keep inside it);
+ * RT_ERR_LIMIT: sample >= 65536, RT_QUERY_ORDER_SORTED with n > 2^31 - 1, n > 256 (2^31 - 1) (one
+ * 256-ray block per grid slot); RT_ERR_STATE: textures = 1
+ * without an atlas.  n = 0: RT_OK, nothing is done.  RT_ERR_NODEV: no usable device. */
+int rt_shade(rt_scene* s, const rt_shade_opts* opts);
+/* The scene's most recent rt_shade that reached its launch (test hook, as rt_query_last): out8 =
+ * {NS, TREE, TEX of the shade kernel used, batch was sorted 0/1, blocks, n's low 31 bits, 0, 0}.
+ * RT_ERR_STATE before the first rt_shade. */
+int rt_shade_last(const rt_scene* s, int32_t out8[8]);
 
 /* ---- ambient occlusion (build-defined; the reference has no counterpart) ----
  * For every pixel of the current camera: how much of the hemisphere above its primary hit is

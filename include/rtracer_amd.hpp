@@ -280,6 +280,22 @@ inline void set_occlusion_history(renv::gpu::Scene* scene, bool on = true, int m
                                   float normal_min = RT_AO_FILTER_NORMAL_DEFAULT, float plane_tol = RT_AO_FILTER_PLANE_DEFAULT) {
     rtamd_detail::check(rt_occlusion_set_history(scene->handle(), on ? 1 : 0, max_history, normal_min, plane_tol), "set_occlusion_history");
 }
+// Build extension (rt_shade): what each of n caller-supplied rays sees -- `origins` and `dirs` hold
+// 3 floats a ray (host memory); `radiance` receives 4 floats a ray, the integrator's unclamped sum
+// for the ray as a primary ray, and `rgba`, if given, its 8-bit encoding.  sorted: the batch is
+// sorted into coherent waves on the device first (the arrays are the same either way).
+inline void shade(renv::gpu::Scene* scene, const std::vector<float>& origins, const std::vector<float>& dirs,
+                  std::vector<float>& radiance, std::vector<uint32_t>* rgba = nullptr, bool sorted = false) {
+    const size_t n = origins.size() / 3;
+    radiance.resize(4 * n);
+    if (rgba) rgba->resize(n);
+    rt_shade_opts o;
+    rt_shade_opts_default(&o);
+    o.n = (int64_t)n; o.origin = origins.data(); o.dir = dirs.data(); o.host = 1;
+    o.order = sorted ? RT_QUERY_ORDER_SORTED : RT_QUERY_ORDER_CALLER;
+    o.radiance = radiance.data(); o.rgba = rgba ? rgba->data() : nullptr;
+    rtamd_detail::check(dirs.size() == origins.size() ? rt_shade(scene->handle(), &o) : RT_ERR_ARG, "shade");
+}
 // raytracer.cu:91-100: one-pixel trace with the reference's event log on stdout.
 inline void debug_cast(renv::gpu::Scene* scene, int x, int y) {
     std::vector<char> buf(1 << 16);
