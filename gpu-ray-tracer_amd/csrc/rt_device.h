@@ -211,6 +211,10 @@ struct ShadeParams {
     const uint32_t* order;                      // non-null: lane l of chunk c shades ray order[64 c + l] (a permutation of [0, n))
 };
 
+// The rays of a batch as the coherence sort sees them (sort_rays, launch_ray_keys, ray_key_kernel):
+// the inputs QueryParams and ShadeParams share, copied from either; the fields mean what theirs do.
+struct RayBatch { rt::DCamera cam; long long n; const float* origin; const float* dir; const int* pixel; };
+
 // The ambient-occlusion kernels' arguments (rt_occlusion): occl_surface_kernel (cam -> surf),
 // occlusion_kernel (surf, table -> count and, resolving, the outputs) and occl_rays_kernel (the
 // test hook: sample k0's rays -> rays); occlusion_il_kernel / occl_rays_il_kernel are theirs in the
@@ -282,8 +286,8 @@ QueryVariant choose_query_variant(long long n_rays, const SceneView& S, bool any
                                   bool ordered = false);
 hipError_t launch_query_kernel(const QueryVariant& v, QueryParams& Q, SceneView& S, hipStream_t st);
 // ray_key_kernel (RT_QUERY_ORDER_SORTED): keys[i] = ray_key of ray i of the batch as query_kernel
-// would trace it (Q's origin / dir or pixel and camera) in `box`, idx[i] = i.
-hipError_t launch_ray_keys(QueryParams& Q, const rtk::KeyBox& box, unsigned long long* keys, uint32_t* idx, hipStream_t st);
+// would trace it (B's origin / dir or pixel and camera) in `box`, idx[i] = i.
+hipError_t launch_ray_keys(const RayBatch& B, const rtk::KeyBox& box, unsigned long long* keys, uint32_t* idx, hipStream_t st);
 // The shade kernel for a batch (rt_shade): shade_plan's key looked up in the table of shade kernels
 // (null fn: no kernel with this key, a programming error) and its launch.  P: the fields
 // trace_sample reads (rt_shade.cpp lists them); S: caller_ray_view's scene.

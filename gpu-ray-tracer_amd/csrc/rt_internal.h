@@ -2,8 +2,11 @@
 // (upload, frame slots, BVH build and trace launch, rt_render), rt_build.cpp (scene creation,
 // exports, camera), rt_accumulate.cpp, rt_occlusion.cpp, rt_query.cpp, rt_shade.cpp (one entry family each),
 // rt_hooks.cpp (debugging, profiling and test hooks), rt_multi.cpp (multi-device frames) and
-// rt_copy.cpp (copy-engine entries).  Internal functions live in namespace rti: the
-// library's rt_* C symbols (rt_amd.h) stay its only interface.
+// rt_copy.cpp (copy-engine entries).  What rt_query and rt_shade share is written once here: the
+// staging of a batch with host pointers (BatchStage, stage_inputs, fetch_outputs, copy_outputs), the argument
+// checks (check_ray_inputs, check_host_pixels, check_sorted_limit) and the sort (sort_rays).
+// Internal functions live in namespace rti: the library's rt_* C symbols (rt_amd.h) stay its only
+// interface.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -11,6 +14,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstdlib>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -35,6 +39,27 @@ template <class T> struct DevBuf {
     DevBuf& operator=(const DevBuf&) = delete;
     ~DevBuf() { dfree(p); }
     hipError_t alloc(size_t n) { return hipMalloc((void**)&p, n * sizeof(T)); }   // n elements
+};
+// The staging of an entry that takes a batch with host pointers (rt_query, rt_shade: one each): a
+// pinned host image of the batch (rtd::batch_plan: inputs, then outputs) and its device copy.  They
+// grow and are kept, so a warm call allocates nothing; a failed growth leaves the entry without
+// staging, otherwise as it was.  `who` names the entry and n the batch in the error text.
+struct BatchStage {
+    unsigned char* host = nullptr; unsigned char* dev = nullptr; size_t cap = 0;
+    rtd::BatchPlan plan{};                       // the layout of the batch it holds (stage_inputs)
+    void release() { dfree(dev); hfree(host); cap = 0; }
+    int ensure(size_t total, const char* who, long long n) {
+        if (total <= cap) return RT_OK;
+        const size_t grown = std::max(total, 2 * cap);
+        release();
+        if (hipMalloc((void**)&dev, grown) != hipSuccess || hipHostMalloc((void**)&host, grown, hipHostMallocDefault) != hipSuccess) {
+            const std::string why = hipGetErrorString(hipGetLastError());
+            release();
+            return fail(RT_ERR_HIP, std::string(who) + ": no memory to stage " + std::to_string(n) + " rays: " + why);
+        }
+        cap = grown;
+        return RT_OK;
+    }
 };
 
 // Host framebuffer in pinned memory: rt_update_scene's device-to-host copy of the frame (the
@@ -156,12 +181,10 @@ struct rt_scene {
     bool atlas_dirty = false;
     void* d_out[4] = {nullptr, nullptr, nullptr, nullptr};   // staging for host_outputs
     struct Query {
-        // rt_query with host pointers: one pinned host image of the batch (inputs, then outputs) and
-        // its device copy; they grow and are kept, so a warm call allocates nothing
-        unsigned char* host = nullptr; unsigned char* dev = nullptr; size_t cap = 0;
+        rti::BatchStage stage;                   // rt_query with host pointers
         // rt_query_set_order: the mode (host state), and the sorted mode's scratch for qo_rays rays
         // (query_order_plan: keys and ray indices, double-buffered, then hipCUB's qo_temp bytes); it
-        // grows like dev and is kept.  box: the keys' quantisation box, for the poses of box_gen.
+        // grows like the staging and is kept.  box: the keys' quantisation box, for the poses of box_gen.
         int order = RT_QUERY_ORDER_CALLER;
         unsigned char* qo_dev = nullptr; long long qo_rays = 0; size_t qo_temp = 0;
         rtk::KeyBox box{{0, 0, 0}, {0, 0, 0}};
@@ -172,16 +195,15 @@ struct rt_scene {
         bool has_last = false, last_sorted = false;
         long long last_n = 0;
         const uint32_t* last_order = nullptr;
-        void release() { rti::dfree(dev); rti::hfree(host); rti::dfree(qo_dev); cap = 0; qo_rays = 0; qo_temp = 0; last_order = nullptr; }
+        void release() { stage.release(); rti::dfree(qo_dev); qo_rays = 0; qo_temp = 0; last_order = nullptr; }
     } query;
     struct Shade {
-        // rt_shade with host pointers: its own pinned image of the batch and device copy, as Query's
-        unsigned char* host = nullptr; unsigned char* dev = nullptr; size_t cap = 0;
+        rti::BatchStage stage;                   // rt_shade with host pointers: its own, not Query's
         // the most recent rt_shade (rt_shade_last): its kernel and launch, whether the batch was sorted, its size
         rtd::ShadeVariant last{};
         bool has_last = false, last_sorted = false;
         long long last_n = 0;
-        void release() { rti::dfree(dev); rti::hfree(host); cap = 0; }
+        void release() { stage.release(); }
     } shade;
     std::vector<hipEvent_t> tev;    // timing=1 events, 4 per frame: bvh start/stop, trace start/stop (pool)
     size_t tev_used = 0;
@@ -358,10 +380,53 @@ int scene_atlas(rt_scene* s);     // the atlas texels on the device, as a textur
 // quantisation box (rt_scene::Query::box) for the current poses.  ensure_order_scratch: the scene's
 // sort scratch for a batch of n rays (query_order_plan's layout at the capacity, then hipCUB's
 // temporary storage); `who` names the entry in the error text.  sort_rays: key, sort, index on `st`
-// for the batch Q describes; the device array of the batch's order (in the scene's scratch).
+// for the batch B describes; the device array of the batch's order (in the scene's scratch).
 void refresh_query_box(rt_scene* s);
 int ensure_order_scratch(rt_scene* s, long long n, const char* who);
-int sort_rays(rt_scene* s, rtd::QueryParams& Q, int key_bits, hipStream_t st, const uint32_t** order);
+int sort_rays(rt_scene* s, const rtd::RayBatch& B, int key_bits, hipStream_t st, const uint32_t** order);
+
+// ---- What rt_query and rt_shade share; `who` names the entry in the error texts.
+// The argument checks, each entry in its own order: a batch comes by pixel, or by origin and dir;
+// pixels in host memory lie on the W x H canvas; the sorted order's ray indices are 32-bit.
+inline int check_ray_inputs(const char* who, const void* origin, const void* dir, const void* pixel) {
+    if (pixel ? (origin || dir) : !(origin && dir)) return fail(RT_ERR_ARG, std::string(who) + ": give either pixel, or both origin and dir");
+    return RT_OK;
+}
+inline int check_host_pixels(const char* who, const int32_t* pixel, size_t n, int W, int H) {
+    for (size_t i = 0; i < n; i++)
+        if (pixel[2 * i] < 0 || pixel[2 * i + 1] < 0 || pixel[2 * i] >= W || pixel[2 * i + 1] >= H)
+            return fail(RT_ERR_ARG, std::string(who) + ": pixel " + std::to_string(i) + " is outside the canvas");
+    return RT_OK;
+}
+inline int check_sorted_limit(const char* who, int order, int64_t n) {
+    if (order == RT_QUERY_ORDER_SORTED && n > (int64_t)INT32_MAX)
+        return fail(RT_ERR_LIMIT, std::string(who) + ": RT_QUERY_ORDER_SORTED takes at most 2^31 - 1 rays (32-bit ray indices)");
+    return RT_OK;
+}
+// A batch with host pointers through the staging g.  stage_inputs: the parts laid out (g.plan), g
+// grown to hold them, the inputs copied into the image, its host-to-device copy issued and every
+// present part's parameter field pointed at the part's device copy.  fetch_outputs, after the
+// kernel: the outputs' device-to-host copy issued.  copy_outputs, after the stream's
+// synchronisation: the outputs into the caller's arrays.
+inline int stage_inputs(BatchStage& g, rtd::BatchPart* parts, size_t n_parts, const char* who, long long n, hipStream_t st) {
+    g.plan = rtd::batch_plan(parts, n_parts);
+    if (int r = g.ensure(g.plan.total, who, n)) return r;
+    for (const rtd::BatchPart* p = parts; p < parts + n_parts; p++) {
+        if (p->present && !p->output) memcpy(g.host + p->off, p->host, p->bytes);
+        if (p->present) p->bind(p->field, g.dev + p->off);
+    }
+    HIPCHK(hipMemcpyAsync(g.dev, g.host, g.plan.in_bytes, hipMemcpyHostToDevice, st));
+    return RT_OK;
+}
+inline int fetch_outputs(BatchStage& g, hipStream_t st) {
+    const size_t in = g.plan.in_bytes;
+    if (g.plan.total > in) HIPCHK(hipMemcpyAsync(g.host + in, g.dev + in, g.plan.total - in, hipMemcpyDeviceToHost, st));
+    return RT_OK;
+}
+inline void copy_outputs(const BatchStage& g, const rtd::BatchPart* parts, size_t n_parts) {
+    for (const rtd::BatchPart* p = parts; p < parts + n_parts; p++)
+        if (p->present && p->output) memcpy(p->host, g.host + p->off, p->bytes);
+}
 // rt_multi.cpp
 int render_multi(rt_scene* s, const rt_render_opts* o, rt_stats* stats);
 void free_multi(rt_scene* s);

@@ -2293,7 +2293,7 @@ __global__ __launch_bounds__(SKY_THREADS) void sky_kernel(TraceParams P, SceneVi
 // in, and a caller's origin is anywhere.  What stays on is exact for every
 // ray: the filtered slab and plane tests with their exact fallbacks, the per-query direction
 // chain of identity-pose scenes (dir_pre: a function of the direction only), and the zero-axis
-// cut with a slack formed per ray from its own origin (below).
+// cut with a slack formed per ray from its own origin (ray_zcut_slack).
 // A ray with a non-finite component, or whose direction normalises to zero (rmath::Ray:
 // shorter than 1e-5, or too long for its length to be finite), is inactive from the start: it
 // reports a miss and takes no part in the wave's ballots.  That test is rtk::caller_ray /
@@ -2310,6 +2310,25 @@ __device__ __forceinline__ KQP& qparams() {
     KQP* p = (KQP*)__builtin_amdgcn_kernarg_segment_ptr();     // the first kernel argument
     asm volatile("" : "+s"(p));
     return *p;
+}
+
+// The zero-axis cut's slack for a ray from `o` (zero_axis_cut; ordered tree, pure translations: zcut_scene >= 0, the
+// scene's term), or -1: no cut.  The bound is the camera rays' with this origin in the camera's place: on an axis where
+// d_a = 0 the ray keeps its coordinate o_a exactly, world and local, so an accepted point is within the triangle
+// tolerance and the origin's rounding of the leaf box there; 4e-4 x the largest vertex coordinate + 2^-14 x (scene
+// radius + |o|) is 20x that.  Without it one axis-parallel ray (a frame's centre column, a line of sight along an axis)
+// visits every leaf of its row: the 1024-ray batch holding the centre column's end measured 333 us without the cut, 92 us
+// with it.  Origins beyond 2^64 (where K x slack leaves the float range) go without.  PARAMS is the
+// kernel's accessor, qparams or oparams (plain functions, so each can be a template argument), not zcut_scene by value:
+// the term is read in place at each of its two uses as before; with one read the occlusion kernels compiled to other code.
+template <auto PARAMS>
+__device__ __forceinline__ float ray_zcut_slack(V3 o) {
+    float zc = -1.0f;
+    if (PARAMS().zcut_scene >= 0.0f) {
+        const float oa = fmaxf(fabsf(o.x), fmaxf(fabsf(o.y), fabsf(o.z)));
+        if (oa <= 0x1p64f) zc = PARAMS().zcut_scene + 0x1p-14f * oa;
+    }
+    return zc;
 }
 
 template <int TREE, bool LDS, bool ANY, bool STATS, bool ORD = false>
@@ -2331,6 +2350,7 @@ __global__ __launch_bounds__(TRACE_BLOCK_P) void query_kernel(QueryParams Q_arg,
         const long long i = (ORD && in) ? (long long)qparams().order[slot] : slot;   // the sorted batch: this slot's ray
         Ray r{v3(0, 0, 0), v3(0, 0, 1)};
         bool ok = in;
+        // (shade_kernel's lines too: a shared inline function changed both kernels' code, profiles/caller_rays/helper_forms.txt)
         if (in) {
             KQP& Q = qparams();
             if (Q.pixel) {                                     // the camera's sample-0 ray (trace_kernel's primary)
@@ -2360,20 +2380,7 @@ __global__ __launch_bounds__(TRACE_BLOCK_P) void query_kernel(QueryParams Q_arg,
         if (ANY && qparams().any_margin >= 0.0f && tm > 0.0f) occl = tm * (1.0f - qparams().any_margin);
         Best b;
         b.time = INFINITY; b.inst = -1; b.tri = -1; b.u = 0.0f; b.v = 0.0f;
-        // Zero-axis cut with the ray's own slack (zero_axis_cut; ordered tree, pure translations:
-        // zcut_scene >= 0).  Its bound is the camera rays' with this origin in the camera's place:
-        // on an axis where d_a = 0 the ray keeps its coordinate o_a exactly, world and local, so an
-        // accepted point is within the triangle tolerance and the origin's rounding of the leaf
-        // box there; 4e-4 x the largest vertex coordinate + 2^-14 x (scene radius + |o|) is 20x
-        // that.  Without it one axis-parallel ray (a frame's centre column, a line of sight along
-        // an axis) visits every leaf of its row: the 1024-ray batch holding the centre column's
-        // end measured 333 us without the cut, 92 us with it.
-        // Origins beyond 2^64 (where K x slack leaves the float range) go without.
-        float zc = -1.0f;
-        if (FT && qparams().zcut_scene >= 0.0f) {
-            const float oa = fmaxf(fabsf(r.o.x), fmaxf(fabsf(r.o.y), fabsf(r.o.z)));
-            if (oa <= 0x1p64f) zc = qparams().zcut_scene + 0x1p-14f * oa;
-        }
+        const float zc = FT ? ray_zcut_slack<qparams>(r.o) : -1.0f;
         closest_hit<false, STATS, FT, false, false, BRUTE && !STATS>(S, bv, ok, r, b, wc, occl, INFINITY, zc);
         const bool hit = ok && b.time < tm;                    // (nothing accepted: b.time = +inf)
         if (in) {
@@ -2410,7 +2417,7 @@ __global__ __launch_bounds__(TRACE_BLOCK_P) void query_kernel(QueryParams Q_arg,
 // same 768 contiguous bytes, so every fetched line is used whole, and the key and index stores
 // are contiguous (8 and 4 bytes a lane).  The box and pointers come as kernel arguments.
 constexpr int KEY_BLOCK = 256;
-__global__ __launch_bounds__(KEY_BLOCK) void ray_key_kernel(QueryParams Q, rtk::KeyBox box, unsigned long long* __restrict__ keys,
+__global__ __launch_bounds__(KEY_BLOCK) void ray_key_kernel(RayBatch Q, rtk::KeyBox box, unsigned long long* __restrict__ keys,
                                                             uint32_t* __restrict__ idx) {
     const long long i = (long long)blockIdx.x * KEY_BLOCK + threadIdx.x;
     if (i >= Q.n) return;
@@ -2465,7 +2472,7 @@ __global__ __launch_bounds__(SHADE_BLOCK) void shade_kernel(TraceParams P_arg, S
     if (sparams().order != nullptr && in) i = (long long)sparams().order[slot];   // the sorted batch: this slot's ray
     Ray r{v3(0, 0, 0), v3(0, 0, 1)};
     bool ok = in;
-    if (in) {
+    if (in) {                                                  // (query_kernel's lines, with the sample's offset: see there)
         KSP& Q = sparams();
         if (Q.pixel) {                                         // the camera's ray of sample k (trace_kernel's primary)
             const float2 o = spp_offset_dev(Q.sample);
@@ -2565,11 +2572,7 @@ __global__ __launch_bounds__(OCCL_BLOCK) void occl_surface_kernel(OcclParams P_a
     }
     Best b;
     b.time = INFINITY; b.inst = -1; b.tri = -1; b.u = 0.0f; b.v = 0.0f;
-    float zc = -1.0f;                                          // the zero-axis cut's per-ray slack (query_kernel)
-    if (FT && oparams().zcut_scene >= 0.0f) {
-        const float oa = fmaxf(fabsf(r.o.x), fmaxf(fabsf(r.o.y), fabsf(r.o.z)));
-        if (oa <= 0x1p64f) zc = oparams().zcut_scene + 0x1p-14f * oa;
-    }
+    const float zc = FT ? ray_zcut_slack<oparams>(r.o) : -1.0f;
     WaveCounters wc{0, 0, 0, 0};
     closest_hit<false, false, FT, false, false, BRUTE>(S, bv, ok, r, b, wc, -1.0f, INFINITY, zc);
     if (!in) return;
@@ -2623,11 +2626,7 @@ __device__ __forceinline__ void occlusion_samples(const SceneView& S) {
         f = rto::make_frame(v3(a.x, a.y, a.z), v3(c.x, c.y, c.z));
     }
     f.p = rto::ray_origin(f, oparams().bias);                  // every sample's origin
-    float zc = -1.0f;
-    if (FT && oparams().zcut_scene >= 0.0f) {
-        const float oa = fmaxf(fabsf(f.p.x), fmaxf(fabsf(f.p.y), fabsf(f.p.z)));
-        if (oa <= 0x1p64f) zc = oparams().zcut_scene + 0x1p-14f * oa;
-    }
+    const float zc = FT ? ray_zcut_slack<oparams>(f.p) : -1.0f;
     int cnt = 0;
     WaveCounters wc{0, 0, 0, 0};
     const int k0 = oparams().k0, k1 = k0 + oparams().samples;
@@ -3308,8 +3307,8 @@ hipError_t launch_query_kernel(const QueryVariant& v, QueryParams& Q, SceneView&
     return hipExtLaunchKernel(v.fn, dim3(v.blocks), dim3(v.block), args, v.shm, st, nullptr, nullptr, 0);
 }
 
-hipError_t launch_ray_keys(QueryParams& Q, const rtk::KeyBox& box, unsigned long long* keys, uint32_t* idx, hipStream_t st) {
-    hipLaunchKernelGGL(ray_key_kernel, dim3((unsigned)((Q.n + KEY_BLOCK - 1) / KEY_BLOCK)), dim3(KEY_BLOCK), 0, st, Q, box, keys, idx);
+hipError_t launch_ray_keys(const RayBatch& B, const rtk::KeyBox& box, unsigned long long* keys, uint32_t* idx, hipStream_t st) {
+    hipLaunchKernelGGL(ray_key_kernel, dim3((unsigned)((B.n + KEY_BLOCK - 1) / KEY_BLOCK)), dim3(KEY_BLOCK), 0, st, B, box, keys, idx);
     return hipGetLastError();
 }
 

@@ -6,10 +6,10 @@
 //    (trace_variant_key; the table of kernels it indexes is choose_trace_variant's, in
 //    rt_kernels.hip), the frame's lane mapping and group geometry (frame_geometry), its shading
 //    shortcuts (shade_shortcuts), its grid (grid_policy) and its scheduling history mode
-//    (history_mode), and which query kernel a batch of caller-supplied rays gets (query_plan,
-//    rt_query).  launch_trace (rt_runtime.cpp) and rt_query (rt_query.cpp) fill them in from
-//    them; tests/test_plan_host.py and tests/test_query_host.py check them on a machine without
-//    a GPU.
+//    (history_mode), which query kernel a batch of caller-supplied rays gets (query_plan,
+//    rt_query), and a host-pointer batch's layout in its staging (batch_plan).  launch_trace
+//    (rt_runtime.cpp) and rt_query (rt_query.cpp) fill them in from them; tests/test_plan_host.py,
+//    tests/test_query_host.py and tests/test_batch_stage_host.py check them without a GPU.
 #pragma once
 
 #include <algorithm>
@@ -486,6 +486,30 @@ inline QueryOrderPlan query_order_plan(long long n_rays, int mode, bool counted)
     p.keys_bytes = a256(8 * (size_t)n_rays);
     p.idx_bytes = a256(4 * (size_t)n_rays);
     p.scratch_bytes = 2 * p.keys_bytes + 2 * p.idx_bytes;
+    return p;
+}
+
+// ---- A batch given with host pointers (rt_query, rt_shade): its image in the entry's staging
+// (rti::BatchStage).  A part is one of the caller's arrays, made from the parameter field that
+// holds its pointer: `host` (the field's value then: an input's source, an output's destination),
+// its bytes, whether the call has it, and `bind`, which points the field at the part's device copy
+// (so a part and its field cannot come apart; the plan looks at neither).  A present part takes
+// a16(bytes) at `off`, an absent one nothing; the inputs come first, then the outputs, each in list
+// order, so one copy carries [0, in_bytes) in and one carries [in_bytes, total) out.
+struct BatchPart { void* host; size_t bytes; bool output, present; size_t off; void* field; void (*bind)(void* field, void* dev); };
+template <class T> BatchPart batch_part(T*& field, size_t bytes, bool output) {
+    return {(void*)field, bytes, output, field != nullptr, 0, &field, [](void* f, void* d) { *static_cast<T**>(f) = static_cast<T*>(d); }};
+}
+template <class T> BatchPart in_part(const T*& field, size_t bytes) { return batch_part(field, bytes, false); }
+template <class T> BatchPart out_part(T*& field, size_t bytes) { return batch_part(field, bytes, true); }
+struct BatchPlan { size_t in_bytes, total; };
+inline BatchPlan batch_plan(BatchPart* parts, size_t n_parts) {
+    BatchPlan p{0, 0};
+    for (const bool output : {false, true}) {
+        for (size_t i = 0; i < n_parts; i++)
+            if (parts[i].present && parts[i].output == output) { parts[i].off = p.total; p.total += a16(parts[i].bytes); }
+        if (!output) p.in_bytes = p.total;
+    }
     return p;
 }
 

@@ -3,6 +3,7 @@
 // Host code only (rt_internal.h); the state lives in rt_scene::Query.
 #include <cmath>
 #include <cstring>
+#include <iterator>
 
 #include "rt_internal.h"
 
@@ -56,7 +57,7 @@ int rti::ensure_order_scratch(rt_scene* s, long long n, const char* who) {
 // Key, sort, index: stream-ordered, no host synchronisation between them.  The buffers are laid out
 // for the scratch's capacity (ensure_order_scratch came first); the sort looks at the key bits in
 // use only.
-int rti::sort_rays(rt_scene* s, QueryParams& Q, int key_bits, hipStream_t st, const uint32_t** order) {
+int rti::sort_rays(rt_scene* s, const RayBatch& B, int key_bits, hipStream_t st, const uint32_t** order) {
     rt_scene::Query& qs = s->query;
     refresh_query_box(s);
     const QueryOrderPlan CP = query_order_plan(qs.qo_rays, QUERY_ORDER_SORTED, false);
@@ -65,8 +66,8 @@ int rti::sort_rays(rt_scene* s, QueryParams& Q, int key_bits, hipStream_t st, co
     unsigned long long* k_out = (unsigned long long*)p; p += CP.keys_bytes;
     uint32_t* v_in = (uint32_t*)p; p += CP.idx_bytes;
     uint32_t* v_out = (uint32_t*)p; p += CP.idx_bytes;
-    HIPCHK(launch_ray_keys(Q, qs.box, k_in, v_in, st));
-    HIPCHK(ray_sort_pairs(p, qs.qo_temp, k_in, k_out, v_in, v_out, Q.n, key_bits, st));
+    HIPCHK(launch_ray_keys(B, qs.box, k_in, v_in, st));
+    HIPCHK(ray_sort_pairs(p, qs.qo_temp, k_in, k_out, v_in, v_out, B.n, key_bits, st));
     *order = v_out;
     return RT_OK;
 }
@@ -86,23 +87,15 @@ int rt_query(rt_scene* s, const rt_query_opts* o, rt_stats* stats) {
     if (!o) return fail(RT_ERR_ARG, "null options");
     if (o->n < 0) return fail(RT_ERR_ARG, "rt_query: n >= 0 required");
     if (o->n == 0) return RT_OK;
-    const bool by_pixel = o->pixel != nullptr;
-    if (by_pixel ? (o->origin || o->dir) : !(o->origin && o->dir))
-        return fail(RT_ERR_ARG, "rt_query: give either pixel, or both origin and dir");
+    int r;
+    if ((r = check_ray_inputs("rt_query", o->origin, o->dir, o->pixel)) != RT_OK) return r;
     const bool any = o->any_hit != 0;
     if (any ? !o->hit : !(o->t || o->inst || o->tri || o->uv || o->normal || o->hit || o->rays_out))
         return fail(RT_ERR_ARG, any ? "rt_query: an occlusion query writes `hit`" : "rt_query: no output requested");
     const size_t n = (size_t)o->n;
     rt_scene::Query& qs = s->query;
-    if (qs.order == RT_QUERY_ORDER_SORTED && o->n > (int64_t)INT32_MAX)
-        return fail(RT_ERR_LIMIT, "rt_query: RT_QUERY_ORDER_SORTED takes at most 2^31 - 1 rays (32-bit ray indices)");
-    if (o->host && by_pixel)
-        for (size_t i = 0; i < n; i++) {
-            const int x = o->pixel[2 * i], y = o->pixel[2 * i + 1];
-            if (x < 0 || y < 0 || x >= s->h.cam.W || y >= s->h.cam.H)
-                return fail(RT_ERR_ARG, "rt_query: pixel " + std::to_string(i) + " is outside the canvas");
-        }
-    int r;
+    if ((r = check_sorted_limit("rt_query", qs.order, o->n)) != RT_OK) return r;
+    if (o->host && o->pixel && (r = check_host_pixels("rt_query", o->pixel, n, s->h.cam.W, s->h.cam.H)) != RT_OK) return r;
     if ((r = begin_side_entry(s, 1, false)) != RT_OK) return r;   // upload, frames in flight, current poses
     hipStream_t st = sstream(s);
     const bool counted = stats != nullptr;
@@ -120,37 +113,11 @@ int rt_query(rt_scene* s, const rt_query_opts* o, rt_stats* stats) {
     Q.uv = any ? nullptr : o->uv; Q.normal = any ? nullptr : o->normal;
     Q.hit = o->hit; Q.rays_out = o->rays_out;
     Q.stats = counted ? s->d_stats : nullptr;
-    // host pointers: the batch as one pinned image (inputs, then outputs) and its device copy
-    struct Part { const void* src; void* dst; size_t bytes, off; };
-    Part in[4] = {{o->origin, nullptr, 12 * n, 0}, {o->dir, nullptr, 12 * n, 0}, {o->tmax, nullptr, 4 * n, 0}, {o->pixel, nullptr, 8 * n, 0}};
-    Part out[7] = {{nullptr, Q.t, 4 * n, 0}, {nullptr, Q.inst, 4 * n, 0}, {nullptr, Q.tri, 4 * n, 0}, {nullptr, Q.uv, 8 * n, 0},
-                   {nullptr, Q.normal, 12 * n, 0}, {nullptr, Q.hit, n, 0}, {nullptr, Q.rays_out, 24 * n, 0}};
-    size_t in_bytes = 0, total = 0;
-    if (o->host) {
-        for (Part& p : in) if (p.src) { p.off = total; total += a16(p.bytes); }
-        in_bytes = total;
-        for (Part& p : out) if (p.dst) { p.off = total; total += a16(p.bytes); }
-        if (total > qs.cap) {
-            const size_t cap = std::max(total, 2 * qs.cap);
-            dfree(qs.dev); hfree(qs.host); qs.cap = 0;
-            HIPCHK(hipMalloc((void**)&qs.dev, cap));
-            HIPCHK(hipHostMalloc((void**)&qs.host, cap, hipHostMallocDefault));
-            qs.cap = cap;
-        }
-        for (const Part& p : in) if (p.src) memcpy(qs.host + p.off, p.src, p.bytes);
-        HIPCHK(hipMemcpyAsync(qs.dev, qs.host, in_bytes, hipMemcpyHostToDevice, st));
-        auto dev = [&](const Part& p) { return (void*)(qs.dev + p.off); };
-        if (o->origin) { Q.origin = (const float*)dev(in[0]); Q.dir = (const float*)dev(in[1]); }
-        if (o->tmax) Q.tmax = (const float*)dev(in[2]);
-        if (o->pixel) Q.pixel = (const int*)dev(in[3]);
-        if (Q.t) Q.t = (float*)dev(out[0]);
-        if (Q.inst) Q.inst = (int*)dev(out[1]);
-        if (Q.tri) Q.tri = (int*)dev(out[2]);
-        if (Q.uv) Q.uv = (float*)dev(out[3]);
-        if (Q.normal) Q.normal = (float*)dev(out[4]);
-        if (Q.hit) Q.hit = (unsigned char*)dev(out[5]);
-        if (Q.rays_out) Q.rays_out = (float*)dev(out[6]);
-    }
+    // host pointers: the batch staged (inputs, then outputs) and these fields pointed at its device copy
+    BatchPart parts[] = {in_part(Q.origin, 12 * n), in_part(Q.dir, 12 * n), in_part(Q.tmax, 4 * n), in_part(Q.pixel, 8 * n),
+                         out_part(Q.t, 4 * n), out_part(Q.inst, 4 * n), out_part(Q.tri, 4 * n), out_part(Q.uv, 8 * n),
+                         out_part(Q.normal, 12 * n), out_part(Q.hit, n), out_part(Q.rays_out, 24 * n)};
+    if (o->host && (r = stage_inputs(qs.stage, parts, std::size(parts), "rt_query", o->n, st)) != RT_OK) return r;
     CallerView cv = caller_ray_view(s, o->use_bvh != 0);          // a caller's origin is anywhere
     SceneView& S = cv.S;
     Q.zcut_scene = cv.zcut_scene; Q.any_margin = cv.any_margin;
@@ -164,7 +131,7 @@ int rt_query(rt_scene* s, const rt_query_opts* o, rt_stats* stats) {
     bool trace = true;
     if (OP.sort) {
         // key, sort, trace: stream-ordered, no host synchronisation between them
-        if ((r = sort_rays(s, Q, OP.key_bits, st, &Q.order)) != RT_OK) return r;
+        if ((r = sort_rays(s, RayBatch{Q.cam, Q.n, Q.origin, Q.dir, Q.pixel}, OP.key_bits, st, &Q.order)) != RT_OK) return r;
         // RT_QUERY_SORT_ONLY (measurements, tools/query_bench.py): stop after the sort; no output is written
         if (const char* e = getenv("RT_QUERY_SORT_ONLY")) trace = atoi(e) == 0;
     }
@@ -173,12 +140,10 @@ int rt_query(rt_scene* s, const rt_query_opts* o, rt_stats* stats) {
     qs.last = V; qs.has_last = true;                           // rt_query_last
     qs.last_sorted = OP.sort; qs.last_n = o->n; qs.last_order = Q.order;
     if (counted) HIPCHK(hipEventRecord(s->ev[2], st));
-    if (o->host && total > in_bytes)
-        HIPCHK(hipMemcpyAsync(qs.host + in_bytes, qs.dev + in_bytes, total - in_bytes, hipMemcpyDeviceToHost, st));
+    if (o->host && (r = fetch_outputs(qs.stage, st)) != RT_OK) return r;
     if ((r = end_frame(s, st)) != RT_OK) return r;
     HIPCHK(hipStreamSynchronize(st));
-    if (o->host)
-        for (const Part& p : out) if (p.dst) memcpy(p.dst, qs.host + p.off, p.bytes);   // (dst: the caller's arrays)
+    if (o->host) copy_outputs(qs.stage, parts, std::size(parts));
     return counted ? read_frame_stats(s, stats) : RT_OK;
 }
 

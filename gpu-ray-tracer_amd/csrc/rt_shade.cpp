@@ -3,6 +3,7 @@
 // Host code only (rt_internal.h); the state lives in rt_scene::Shade, the sort's scratch and key
 // box in rt_scene::Query (rt_query.cpp's helpers).
 #include <cstring>
+#include <iterator>
 
 #include "rt_internal.h"
 
@@ -25,30 +26,22 @@ int rt_shade(rt_scene* s, const rt_shade_opts* o) {
     CHECK_FINISHED(s);
     if (!o) return fail(RT_ERR_ARG, "null options");
     if (o->n < 0) return fail(RT_ERR_ARG, "rt_shade: n >= 0 required");
-    const bool by_pixel = o->pixel != nullptr;
-    if (by_pixel ? (o->origin || o->dir) : !(o->origin && o->dir))
-        return fail(RT_ERR_ARG, "rt_shade: give either pixel, or both origin and dir");
+    int r;
+    if ((r = check_ray_inputs("rt_shade", o->origin, o->dir, o->pixel)) != RT_OK) return r;
     if (o->sample < 0) return fail(RT_ERR_ARG, "rt_shade: sample >= 0 required");
     if (!(o->radiance || o->rgba || o->rays_out)) return fail(RT_ERR_ARG, "rt_shade: no output requested");
     if (o->order != RT_QUERY_ORDER_CALLER && o->order != RT_QUERY_ORDER_SORTED)
         return fail(RT_ERR_ARG, "rt_shade: order is RT_QUERY_ORDER_CALLER or RT_QUERY_ORDER_SORTED");
     const size_t n = (size_t)o->n;
-    if (o->host && by_pixel)
-        for (size_t i = 0; i < n; i++) {
-            const int x = o->pixel[2 * i], y = o->pixel[2 * i + 1];
-            if (x < 0 || y < 0 || x >= s->h.cam.W || y >= s->h.cam.H)
-                return fail(RT_ERR_ARG, "rt_shade: pixel " + std::to_string(i) + " is outside the canvas");
-        }
+    if (o->host && o->pixel && (r = check_host_pixels("rt_shade", o->pixel, n, s->h.cam.W, s->h.cam.H)) != RT_OK) return r;
     if (o->sample >= 65536) return fail(RT_ERR_LIMIT, "rt_shade: sample < 65536 required");
-    if (o->order == RT_QUERY_ORDER_SORTED && o->n > (int64_t)INT32_MAX)
-        return fail(RT_ERR_LIMIT, "rt_shade: RT_QUERY_ORDER_SORTED takes at most 2^31 - 1 rays (32-bit ray indices)");
+    if ((r = check_sorted_limit("rt_shade", o->order, o->n)) != RT_OK) return r;
     // one block per 256 rays, no stride loop: the grid's 2^31 - 1 blocks bound the batch (shade_plan)
     if (o->n > (int64_t)SHADE_BLOCK * INT32_MAX)
         return fail(RT_ERR_LIMIT, "rt_shade: at most 256 (2^31 - 1) rays a call");
     if (o->textures && s->h.atlas_rgba.empty())
         return fail(RT_ERR_STATE, "textured shading needs an atlas: rt_scene_load_atlas / rt_scene_set_atlas");
     if (o->n == 0) return RT_OK;
-    int r;
     if ((r = begin_side_entry(s, 1, false)) != RT_OK) return r;   // upload, frames in flight, current poses
     hipStream_t st = sstream(s);
     rt_scene::Shade& ss = s->shade;
@@ -62,35 +55,10 @@ int rt_shade(rt_scene* s, const rt_shade_opts* o) {
     Q.cam = s->h.d_cam; Q.n = o->n;
     Q.origin = o->origin; Q.dir = o->dir; Q.pixel = o->pixel; Q.sample = o->sample;
     Q.radiance = reinterpret_cast<float4*>(o->radiance); Q.rgba = o->rgba; Q.rays_out = o->rays_out;
-    // host pointers: the batch as one pinned image (inputs, then outputs) and its device copy
-    struct Part { const void* src; void* dst; size_t bytes, off; };
-    Part in[3] = {{o->origin, nullptr, 12 * n, 0}, {o->dir, nullptr, 12 * n, 0}, {o->pixel, nullptr, 8 * n, 0}};
-    Part out[3] = {{nullptr, o->radiance, 16 * n, 0}, {nullptr, o->rgba, 4 * n, 0}, {nullptr, o->rays_out, 24 * n, 0}};
-    size_t in_bytes = 0, total = 0;
-    if (o->host) {
-        for (Part& p : in) if (p.src) { p.off = total; total += a16(p.bytes); }
-        in_bytes = total;
-        for (Part& p : out) if (p.dst) { p.off = total; total += a16(p.bytes); }
-        if (total > ss.cap) {
-            const size_t cap = std::max(total, 2 * ss.cap);
-            ss.release();
-            if (hipMalloc((void**)&ss.dev, cap) != hipSuccess ||
-                hipHostMalloc((void**)&ss.host, cap, hipHostMallocDefault) != hipSuccess) {
-                const std::string why = hipGetErrorString(hipGetLastError());
-                ss.release();                                  // without staging, otherwise as it was
-                return fail(RT_ERR_HIP, "rt_shade: no memory to stage " + std::to_string(o->n) + " rays: " + why);
-            }
-            ss.cap = cap;
-        }
-        for (const Part& p : in) if (p.src) memcpy(ss.host + p.off, p.src, p.bytes);
-        HIPCHK(hipMemcpyAsync(ss.dev, ss.host, in_bytes, hipMemcpyHostToDevice, st));
-        auto dev = [&](const Part& p) { return (void*)(ss.dev + p.off); };
-        if (o->origin) { Q.origin = (const float*)dev(in[0]); Q.dir = (const float*)dev(in[1]); }
-        if (o->pixel) Q.pixel = (const int*)dev(in[2]);
-        if (Q.radiance) Q.radiance = (float4*)dev(out[0]);
-        if (Q.rgba) Q.rgba = (uint32_t*)dev(out[1]);
-        if (Q.rays_out) Q.rays_out = (float*)dev(out[2]);
-    }
+    // host pointers: the batch staged (inputs, then outputs) and these fields pointed at its device copy
+    BatchPart parts[] = {in_part(Q.origin, 12 * n), in_part(Q.dir, 12 * n), in_part(Q.pixel, 8 * n),
+                         out_part(Q.radiance, 16 * n), out_part(Q.rgba, 4 * n), out_part(Q.rays_out, 24 * n)};
+    if (o->host && (r = stage_inputs(ss.stage, parts, std::size(parts), "rt_shade", o->n, st)) != RT_OK) return r;
     // The scene for rays from anywhere: camera-ray shortcuts off; view_of leaves the hint table and
     // the counters unbound and near-first off (only launch_trace binds them), so the hint and
     // near-first counters do not move because of this call.
@@ -119,20 +87,16 @@ int rt_shade(rt_scene* s, const rt_shade_opts* o) {
         // key, sort and index as rt_query: the keys of the same inputs (pixel mode: the pixels'
         // sample-0 rays, whose order is every sample's).  The order lives in the scene's sort
         // scratch, which rt_query's last order may share: that order is gone (rt_query_last).
-        QueryParams K{};
-        K.cam = Q.cam; K.n = Q.n; K.origin = Q.origin; K.dir = Q.dir; K.pixel = Q.pixel;
         s->query.last_order = nullptr;
-        if ((r = sort_rays(s, K, OP.key_bits, st, &Q.order)) != RT_OK) return r;
+        if ((r = sort_rays(s, RayBatch{Q.cam, Q.n, Q.origin, Q.dir, Q.pixel}, OP.key_bits, st, &Q.order)) != RT_OK) return r;
     }
     HIPCHK(launch_shade_kernel(V, P, S, Q, st));
     HIPCHK(hipGetLastError());
     ss.last = V; ss.has_last = true; ss.last_sorted = OP.sort; ss.last_n = o->n;   // rt_shade_last
-    if (o->host && total > in_bytes)
-        HIPCHK(hipMemcpyAsync(ss.host + in_bytes, ss.dev + in_bytes, total - in_bytes, hipMemcpyDeviceToHost, st));
+    if (o->host && (r = fetch_outputs(ss.stage, st)) != RT_OK) return r;
     if ((r = end_frame(s, st)) != RT_OK) return r;
     HIPCHK(hipStreamSynchronize(st));
-    if (o->host)
-        for (const Part& p : out) if (p.dst) memcpy(p.dst, ss.host + p.off, p.bytes);   // (dst: the caller's arrays)
+    if (o->host) copy_outputs(ss.stage, parts, std::size(parts));
     return RT_OK;
 }
 

@@ -283,6 +283,31 @@ def _ptr(a):
     return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 
 
+def _ray_inputs(o, who, origins, dirs, pixels):
+    """A batch of caller rays into o.pixel / o.origin / o.dir (QueryOpts, ShadeOpts): its size n and
+    the arrays the pointers refer to, for the caller to keep alive across the call."""
+    given = [(k, np.ascontiguousarray(a, dtype=dt).reshape(-1, c))
+             for k, a, dt, c in (("pixel", pixels, np.int32, 2), ("origin", origins, np.float32, 3), ("dir", dirs, np.float32, 3))
+             if a is not None]
+    if not given:
+        raise RtError(RT_ERR_ARG, who + ": give origins and dirs, or pixels")
+    n = given[-1][1].shape[0]
+    assert all(a.shape[0] == n for _, a in given), "origins and dirs differ in length"
+    for k, a in given:
+        setattr(o, k, _ptr(a))
+    return n, [a for _, a in given]
+
+
+def _ray_outputs(o, n, want, table):
+    """A zeroed array per name in `want`, shaped by `table` (QUERY_OUTPUTS, SHADE_OUTPUTS), bound to o's field of that name."""
+    out = {}
+    for k in want:
+        c, dt = table[k]
+        out[k] = np.zeros((n, c) if c > 1 else (n,), dt)
+        setattr(o, k, _ptr(out[k]))
+    return out
+
+
 def device_count():
     n = ctypes.c_int()
     _check(lib().rt_device_count(ctypes.byref(n)))
@@ -849,28 +874,12 @@ class Scene:
         reorder=True: this call runs in RT_QUERY_ORDER_SORTED (set_query_order), whatever the scene's mode."""
         o = QueryOpts()
         lib().rt_query_opts_default(ctypes.byref(o))
-        keep = []
-        if pixels is not None:
-            keep.append(np.ascontiguousarray(pixels, dtype=np.int32).reshape(-1, 2))
-            o.pixel, n = _ptr(keep[-1]), keep[-1].shape[0]
-        if origins is not None:
-            keep.append(_f(origins).reshape(-1, 3))
-            o.origin, n = _ptr(keep[-1]), keep[-1].shape[0]
-        if dirs is not None:
-            keep.append(_f(dirs).reshape(-1, 3))
-            o.dir, n = _ptr(keep[-1]), keep[-1].shape[0]
-        if not keep:
-            raise RtError(RT_ERR_ARG, "query: give origins and dirs, or pixels")
-        assert all(a.shape[0] == n for a in keep), "origins and dirs differ in length"
+        n, keep = _ray_inputs(o, "query", origins, dirs, pixels)
         if tmax is not None:
             keep.append(_f(np.broadcast_to(np.asarray(tmax, np.float32), (n,)), n))
             o.tmax = _ptr(keep[-1])
         o.n, o.use_bvh, o.rebuild_bvh, o.any_hit, o.host = n, int(use_bvh), int(rebuild_bvh), int(any_hit), 1
-        out = {}
-        for k in want:
-            c, dt = QUERY_OUTPUTS[k]
-            out[k] = np.zeros((n, c) if c > 1 else (n,), dt)
-            setattr(o, k, _ptr(out[k]))
+        out = _ray_outputs(o, n, want, QUERY_OUTPUTS)
         st = Stats()
         self._query(o, st if stats else None, reorder)
         if stats:
@@ -901,26 +910,10 @@ class Scene:
         into coherent waves on the device first (RT_QUERY_ORDER_SORTED); the arrays are the same."""
         o = ShadeOpts()
         lib().rt_shade_opts_default(ctypes.byref(o))
-        keep = []
-        if pixels is not None:
-            keep.append(np.ascontiguousarray(pixels, dtype=np.int32).reshape(-1, 2))
-            o.pixel, n = _ptr(keep[-1]), keep[-1].shape[0]
-        if origins is not None:
-            keep.append(_f(origins).reshape(-1, 3))
-            o.origin, n = _ptr(keep[-1]), keep[-1].shape[0]
-        if dirs is not None:
-            keep.append(_f(dirs).reshape(-1, 3))
-            o.dir, n = _ptr(keep[-1]), keep[-1].shape[0]
-        if not keep:
-            raise RtError(RT_ERR_ARG, "shade: give origins and dirs, or pixels")
-        assert all(a.shape[0] == n for a in keep), "origins and dirs differ in length"
+        n, keep = _ray_inputs(o, "shade", origins, dirs, pixels)
         o.n, o.sample, o.textures, o.use_bvh, o.rebuild_bvh = n, int(sample), int(textures), int(use_bvh), int(rebuild_bvh)
         o.order, o.host = (RT_QUERY_ORDER_SORTED if reorder else RT_QUERY_ORDER_CALLER), 1
-        out = {}
-        for k in want:
-            c, dt = SHADE_OUTPUTS[k]
-            out[k] = np.zeros((n, c) if c > 1 else (n,), dt)
-            setattr(o, k, _ptr(out[k]))
+        out = _ray_outputs(o, n, want, SHADE_OUTPUTS)
         _check(lib().rt_shade(self._h, ctypes.byref(o)))
         return out
 

@@ -474,3 +474,55 @@ def test_pick_and_the_cli_agree_with_the_frame(gpu):
     r = subprocess.run([CLI, "-c", scene_path("world8_stress"), "--width", str(W), "--height", str(H), "--pick",
                         "%d,%d" % (W, 0)], capture_output=True, text=True, timeout=120)
     assert r.returncode == 1 and "outside the canvas" in r.stderr
+
+
+# ---- 9. host staging ------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("mode", ["origin_dir", "pixels"])
+def test_host_staging_matches_device_pointers(gpu, mode):
+    """Host-pointer batches through the entries' staging (rt_query with every output, rt_shade with
+    radiance, rgba and rays_out) against the same batches on device pointers, element for element.
+    n = 1, 65, 3 on a scene whose stagings no call has touched: each entry's first allocation, its
+    growth, then a smaller batch in the larger image; the two entries alternate, so a staging they
+    shared by mistake would show.  The rays come from a second scene object, and the reference calls
+    use device pointers, which stage nothing."""
+    import torch
+    tdt = {np.float32: torch.float32, np.int32: torch.int32, np.uint8: torch.uint8, np.uint32: torch.int32}
+    W = H = 16
+    s = gpu.Scene.load_json(scene_path("world1"), W, H)
+    pix_all = qc.all_pixels(W, H)
+    rays = gpu.Scene.load_json(scene_path("world1"), W, H).query(pixels=pix_all, want=("rays_out",))["rays_out"]
+
+    def device_outputs(n, table):
+        return {k: torch.full((n, c) if c > 1 else (n,), 77, dtype=tdt[dt], device="cuda") for k, (c, dt) in table.items()}
+
+    def to_numpy(out, table):
+        return {k: v.cpu().numpy().view(table[k][1]) for k, v in out.items()}
+
+    for n in (1, 65, 3):
+        idx = (np.arange(n) * 7 + n) % (W * H)                     # pixels all over the canvas, another set each time
+        if mode == "pixels":
+            host_in = dict(pixels=pix_all[idx])
+            dev_t = {"pixel": torch.from_numpy(np.ascontiguousarray(pix_all[idx], dtype=np.int32)).cuda()}
+            q_in = {}
+        else:
+            host_in = dict(origins=rays[idx, :3], dirs=rays[idx, 3:] * np.float32(2.5))
+            dev_t = {"origin": torch.from_numpy(np.ascontiguousarray(host_in["origins"])).cuda(),
+                     "dir": torch.from_numpy(np.ascontiguousarray(host_in["dirs"])).cuda()}
+            tmax = np.linspace(0.5, 40.0, n, dtype=np.float32)     # some rays cut short, some not
+            q_in = dict(tmax=tmax)
+            dev_t["tmax"] = torch.from_numpy(tmax).cuda()
+        ptrs = {k + "_ptr": v.data_ptr() for k, v in dev_t.items()}
+        # rt_query
+        out = device_outputs(n, gpu.QUERY_OUTPUTS)
+        torch.cuda.synchronize()
+        s.query_device(n, **ptrs, **{k + "_ptr": v.data_ptr() for k, v in out.items()})
+        want = to_numpy(out, gpu.QUERY_OUTPUTS)
+        assert_same(s.query(want=ALL, **host_in, **q_in), want, ctx="rt_query, %s, n = %d" % (mode, n))
+        # rt_shade
+        ptrs.pop("tmax_ptr", None)
+        out = device_outputs(n, gpu.SHADE_OUTPUTS)
+        torch.cuda.synchronize()
+        s.shade_device(n, **ptrs, **{k + "_ptr": v.data_ptr() for k, v in out.items()})
+        want = to_numpy(out, gpu.SHADE_OUTPUTS)
+        assert_same(s.shade(want=tuple(gpu.SHADE_OUTPUTS), **host_in), want, keys=tuple(gpu.SHADE_OUTPUTS),
+                    ctx="rt_shade, %s, n = %d" % (mode, n))

@@ -8,7 +8,7 @@ import sys
 def kernels(path):
     out, cur, body = {}, None, []
     for line in open(path):
-        m = re.match(r'^(_Z\S+):\s', line)
+        m = re.match(r'^(_Z\S+|\w+_kernel):\s', line)       # (the extern "C" kernels' names are not mangled)
         if m and not line.startswith('\t'):
             cur, body = m.group(1), []
             continue
